@@ -81,6 +81,10 @@ def parse_args():
                     help="HxW override of the crop size (diagnostics only, e.g. 64x128 makes the GPU "
                          "work negligible and exposes the host cost per step; the headline "
                          "number is always the config's 512x1024)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed back as "
+                         "DIR/<name>.npy (rank 0): its losses, a fixed sample of the updated weights "
+                         "and momentum, the BN running statistics (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -265,6 +269,46 @@ def first_step_check(model, cfg_path, seed, size, bs, arch_meta, batch, dev, str
         raise SystemExit("bench.py: the HIP path's losses differ from the oracle's on the first step: "
                          "%s vs %s" % (got, gold["log_vars"]))
     return res
+
+
+DUMP_SAMPLE = 1 << 22   # elements of the weight / momentum sample: 2 x 16 MB of float32
+DUMP_SAMPLE_SEED = 0    # fixed, independent of --seed: the same indices for every run and build
+
+
+def dump_outputs(out_dir, model, arena, outputs):
+    """--dump-outputs: what a caller of the timed path (IterBasedRunner.train_iter) holds after its
+    last step, as DIR/<name>.npy:
+      <log var>.npy      float64 scalars of the step's outputs (loss, decode.loss_seg, ...);
+      params.npy         float32, the parameters after the step's SGD update, flattened in logical
+                         (OIHW / plain) layout and concatenated in named_parameters() order, at
+                         DUMP_SAMPLE sorted indices drawn without replacement with DUMP_SAMPLE_SEED;
+      momentum.npy       float32, the SGD momentum buffers at the same indices;
+      bn_running.npy     float32, every floating-point buffer (BN running mean / var) in full, in
+                         named_buffers() order.
+    The inputs are seeded, so two runs with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for k, v in outputs["log_vars"].items():
+        np.save(os.path.join(out_dir, "%s.npy" % k), np.asarray(float(v), dtype=np.float64))
+    names = [n for n, _ in model.named_parameters()]
+    params = dict(model.named_parameters())
+    moms = arena.momentum_views()
+    total = sum(params[n].numel() for n in names)
+    idx = None
+    if total > DUMP_SAMPLE:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = torch.from_numpy(np.sort(rng.choice(total, DUMP_SAMPLE, replace=False)))
+    for fname, src in (("params", params), ("momentum", moms)):
+        flat = torch.cat([src[n].detach().reshape(-1) for n in names])
+        if idx is not None:
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, fname + ".npy"), flat.float().cpu().numpy())
+        del flat
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    if bufs:
+        np.save(os.path.join(out_dir, "bn_running.npy"), torch.cat(bufs).cpu().numpy())
 
 
 def step_flops(model, sampler, seed, steps, size, bs, fixed_meta):
@@ -570,6 +614,8 @@ def main():
             pstats.Stats(_rt.BACKWARD_PROFILE, stream=sys.stderr).sort_stats("tottime").print_stats(30)
     arch_log_end = arch_log_start + args.steps
     loss = float(runner.outputs["loss"].detach())
+    if args.dump_outputs and rank == 0:   # the last step of the passes above, before the K3 pass trains on
+        dump_outputs(args.dump_outputs, model, arena, runner.outputs)
     if runner.host_prof:
         hp = runner.host_prof
         n = max(hp.pop("iters", 1), 1)
