@@ -1,1 +1,1 @@
-from .train import set_random_seed, train_segmentor  # noqa: F401
+from .train import sandwich_train_sampler, set_random_seed, train_segmentor  # noqa: F401

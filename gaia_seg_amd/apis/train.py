@@ -21,7 +21,8 @@ import torch
 from ..core import dist as gdist
 from ..core.param_arena import ParamArena
 from ..core.runner import (ArenaOptimizerHook, CheckpointHook, FixedLrUpdaterHook,
-                           IterBasedRunner, ManipulateArchHook, PolyLrUpdaterHook, TextLoggerHook)
+                           IterBasedRunner, ManipulateArchHook, PolyLrUpdaterHook, SandwichHook,
+                           TextLoggerHook, check_sandwich_model)
 from ..core.synthetic import SyntheticLoader
 
 
@@ -33,6 +34,20 @@ def set_random_seed(seed, deterministic=False):
     torch.manual_seed(seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(seed)
+
+
+def sandwich_train_sampler(cfg):
+    """In-place distillation's train sampler (tools/train_supernet.py:180-187): with
+    ``use_distillation`` the config names ``max_net``, ``min_net`` and ``random_subnet`` samplers and
+    the train sampler becomes concat[max_net, min_net, random_subnet x sample_subnet_num (default 3)].
+    (The reference reads ``cfg.get(sample_subnet_num, 3)`` -- an undefined name -- meaning the key.)"""
+    assert cfg.get("max_net", False)
+    assert cfg.get("min_net", False)
+    assert cfg.get("random_subnet", False)
+    sampler = dict(type="concat", model_samplers=[cfg.max_net, cfg.min_net])
+    for _ in range(cfg.get("sample_subnet_num", 3)):
+        sampler["model_samplers"].append(cfg.random_subnet)
+    return sampler
 
 
 def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_classes=19,
@@ -95,7 +110,12 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
                              weight_decay=opt.get("weight_decay", 0.0),
                              max_iters=cfg.runner["max_iters"], work_dir=cfg.get("work_dir"),
                              logger=logger, meta=meta)
-    if cfg.get("manipulate_arch", True):  # :142-146
+    if cfg.get("use_distillation", False):
+        # the sandwich iteration takes the place of the one-subnet draw (core/runner.py SandwichHook);
+        # train_sampler is the concat of sandwich_train_sampler(cfg)
+        check_sandwich_model(model)
+        runner.register_hook(SandwichHook(train_sampler, cfg.get("distill_cfg")))
+    elif cfg.get("manipulate_arch", True):  # :142-146
         runner.register_hook(ManipulateArchHook(train_sampler))
     lrc = dict(cfg.get("lr_config") or dict(policy="fixed"))
     policy = lrc.pop("policy", "fixed")

@@ -70,6 +70,9 @@ class ParamArena:
         self._range_cache = {}
         # True while every gradient element is zero outside a running step (see zero_grad)
         self.grads_clean = False
+        # gradient accumulation buffer of the sandwich iterations (core/runner.py), allocated at
+        # first use; zero outside a running iteration
+        self.flat_acc = None
 
     @staticmethod
     def _view(flat, p, phys, off, n):
@@ -132,6 +135,24 @@ class ParamArena:
             _lib.check(L.gs_sgd_step(pb + 4 * a, gb + 4 * a, mb + 4 * a, b - a, lr, momentum,
                                      weight_decay, grad_scale, 1 if zero_grad else 0, st),
                        "gs_sgd_step")
+
+    def accumulate(self, ranges, into="buffer"):
+        """Move gradients between the gradient arena and the accumulation buffer over ``ranges``
+        (one gs_grad_accumulate launch per merged range):
+          into="buffer": flat_acc += flat_grad; flat_grad = 0  (after each member's backward: the
+                         weight-gradient kernels overwrite their gradient, they cannot add to it)
+          into="grad":   flat_grad += flat_acc; flat_acc = 0  (before the iteration's one SGD step)
+        Both sides are zero over ``ranges`` afterwards except the destination."""
+        if into not in ("buffer", "grad"):
+            raise ValueError("into must be 'buffer' or 'grad', got %r" % (into,))
+        if self.flat_acc is None:
+            self.flat_acc = torch.zeros_like(self.flat_grad)
+        L = _lib.load()
+        st = current_stream_ptr()
+        dst, src = (self.flat_acc, self.flat_grad) if into == "buffer" else (self.flat_grad, self.flat_acc)
+        db, sb = dst.data_ptr(), src.data_ptr()
+        for a, b in ranges:
+            _lib.check(L.gs_grad_accumulate(db + 4 * a, sb + 4 * a, b - a, st), "gs_grad_accumulate")
 
     def momentum_views(self):
         """{parameter name: momentum buffer as a LOGICAL (OIHW / plain) view of the flat arena}."""

@@ -6,6 +6,8 @@ the supernet trainer registers (gaiaseg/apis/train.py:115-186):
   ArenaOptimizerHook  zero_grad -> loss.backward() -> (RCCL bucket all-reduce) -> fused SGD step
   ManipulateArchHook  gaivision hook (gaiaseg/apis/train.py:142-146): before every train iteration
                       sample a meta, make it identical on all ranks, manipulate_arch
+  SandwichHook        in-place distillation (tools/train_supernet.py:180-187, US-Nets sandwich rule):
+                      every iteration trains [MAX, MIN, random x N] with one SGD step
   TextLoggerHook / CheckpointHook
 """
 import os
@@ -54,6 +56,79 @@ class ManipulateArchHook(Hook):
         self.history.append(meta.get("name", "random"))
 
 
+def full_arch_meta(model):
+    """The supernet's largest architecture in fold_dict form ({'backbone': {'stem': .., 'body': ..}})."""
+    bb = model.backbone
+    stem = bb.stem_width
+    return {"backbone": {"stem": {"width": list(stem) if isinstance(stem, (list, tuple)) else stem},
+                         "body": {"width": list(bb.body_width), "depth": list(bb.body_depth)}}}
+
+
+def _plain(v):
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    return v
+
+
+def check_sandwich_model(model):
+    """In-place distillation needs heads whose teacher kwargs line up with what the MAX member hands
+    out (the decode head's logits as 'teacher_logits', the auxiliary head's as 'aux_teacher_logits'):
+    a PSP decode head and at most one FCN auxiliary head.  Anything else is refused here rather than
+    guessed: an FCN decode head would read the auxiliary teacher's logits (another resolution), a
+    UPer head has no distillation branch (its reference forward_train takes no kwargs)."""
+    dec = model.decode_head
+    if getattr(dec, "kd_teacher_key", None) != "teacher_logits":
+        raise ValueError(
+            "use_distillation: the decode head must be a DynamicPSPHead (it reads 'teacher_logits'); "
+            "%s %s" % (type(dec).__name__,
+                       "reads the auxiliary teacher's logits 'aux_teacher_logits'"
+                       if getattr(dec, "kd_teacher_key", None) else "has no distillation branch"))
+    aux = getattr(model, "auxiliary_head", None)
+    if aux is None:
+        return
+    if isinstance(aux, torch.nn.ModuleList):
+        raise ValueError("use_distillation: a list of auxiliary heads has no teacher mapping "
+                         "(the reference hands out one 'aux_logits')")
+    if getattr(aux, "kd_teacher_key", None) != "aux_teacher_logits":
+        raise ValueError("use_distillation: the auxiliary head must be a DynamicFCNHead (it reads "
+                         "'aux_teacher_logits'); %s has no distillation branch" % type(aux).__name__)
+
+
+class SandwichHook(Hook):
+    """In-place distillation (tools/train_supernet.py:180-187; US-Nets' sandwich rule): before every
+    train iteration rank 0 draws the member list with ``ConcatSampler.candidates()`` -- MAX, MIN, then
+    the random draws -- and broadcasts it; the runner then trains every member on the same batch, the
+    students against the MAX member's detached logits, and takes ONE SGD step on the sum of their
+    gradients (IterBasedRunner._sandwich_iter).  ``kd_cfg``: T, distillation_weight, interpolation
+    (config key ``distill_cfg``; the reference's defaults 2, 0.5, False)."""
+
+    def __init__(self, sampler, kd_cfg=None):
+        from ..models.losses.distill_loss import KD_DEFAULTS
+        if not hasattr(sampler, "candidates"):
+            raise TypeError("SandwichHook needs a concat sampler (candidates()), got %s"
+                            % type(sampler).__name__)
+        unknown = set(kd_cfg or {}) - set(KD_DEFAULTS)
+        if unknown:
+            raise KeyError("distill_cfg: unknown keys %s (have %s)" % (sorted(unknown), sorted(KD_DEFAULTS)))
+        self.sampler = sampler
+        self.kd_cfg = dict(KD_DEFAULTS, **(kd_cfg or {}))
+        self.history = []
+
+    def before_run(self, runner):
+        check_sandwich_model(runner.model)
+
+    def before_train_iter(self, runner):
+        members = self.sampler.candidates() if gdist.rank() == 0 else None
+        members = gdist.broadcast_object(members, src=0)
+        if not members or _plain(fold_dict(members[0]).get("arch")) != full_arch_meta(runner.model):
+            raise AssertionError("sandwich: the first member must be the supernet's full arch %s, got %s"
+                                 % (full_arch_meta(runner.model), members[0] if members else None))
+        runner.sandwich = (members, self.kd_cfg)
+        self.history.append([m.get("name", "random") for m in members])
+
+
 class PolyLrUpdaterHook(Hook):
     def __init__(self, power=1.0, min_lr=0.0, by_epoch=False, **unused):
         self.power, self.min_lr = power, min_lr
@@ -95,6 +170,31 @@ def _ranges_subtract(a, b):
 
 def _ranges_intersect(a, b):
     return _ranges_subtract(a, _ranges_subtract(a, b))
+
+
+def _ranges_union(a, b):
+    out = []
+    for lo, hi in sorted(list(a) + list(b)):
+        if out and lo <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return [tuple(r) for r in out]
+
+
+def _member_backward(runner, loss):
+    """ArenaOptimizerHook.after_train_iter up to (not including) the SGD step: backward with the
+    gradient exchange, then every stream joined, so the member's gradients are final and reduced."""
+    from ..hip import ops
+    ops.SIDE_CHECKPOINT = None
+    ops.DEFER_JOIN = True
+    try:
+        loss.backward()
+    finally:
+        ops.DEFER_JOIN = False
+    ops.join_branch_streams()
+    runner.reducer.finish()
+    ops.join_side_streams()
 
 
 class ArenaOptimizerHook(Hook):
@@ -267,6 +367,7 @@ class IterBasedRunner:
         self._arch_seen = {}           # arch key -> eager steps run with it
         self.hyper = None              # device {lr, momentum, weight_decay, grad_scale} (graphs on)
         self.graph_stats = {"captured": 0, "replayed": 0, "eager": 0}
+        self.sandwich = None           # (members, kd_cfg) of THIS iteration, set by SandwichHook
         self.set_arch(None)
 
     def register_hook(self, hook):
@@ -517,6 +618,13 @@ class IterBasedRunner:
         if not self.model.training:   # (a full module walk: ~1.5 ms of host time per call)
             self.model.train()
         self.call_hook("before_train_iter")
+        if self.sandwich is not None:
+            members, kd_cfg = self.sandwich
+            self.sandwich = None
+            self._sandwich_iter(data_batch, members, kd_cfg)
+            self._after_hooks(False)
+            self.iter += 1
+            return self.outputs
         t1 = time.perf_counter() if prof is not None else 0.0
         gkey = self._graph_key(data_batch)
         if self.graphs_enabled and gdist.world_size() == 1:
@@ -557,6 +665,52 @@ class IterBasedRunner:
                 prof[k] = prof.get(k, 0.0) + v
             prof["iters"] = prof.get("iters", 0) + 1
         self.iter += 1
+        return self.outputs
+
+    # In-place distillation (SandwichHook): US-Nets' sandwich rule as the reference's train_step
+    # ("dynamic_encoder_decoder-distill-backup (1).py":52-64) + an optimizer that steps once per
+    # iteration (the reference's runner lived in the absent gaiavision package: DESIGN.md §15).
+    # Every member runs forward + backward (gradient exchange inside its own backward: all-reduce is
+    # linear), then its gradients are MOVED into the arena's accumulation buffer (the weight-gradient
+    # kernels overwrite, they cannot add); after the last member the buffer goes back into the
+    # gradients over the union of the members' ranges and one fused SGD step clears them again.
+    # Eager only: no step graphs, no early / split SGD instalments.
+    def _sandwich_iter(self, data_batch, members, kd_cfg):
+        total, log_vars, union, names = None, OrderedDict(), [], []
+        teacher = None
+        n_random = 0
+        for i, meta in enumerate(members):
+            self.set_arch(meta)
+            name = meta.get("name")
+            if name is None:
+                name, n_random = "random%d" % n_random, n_random + 1
+            names.append(name)
+            self.arena.zero_grad(self.active_ranges, trust_clean=True)
+            self.arena.grads_clean = False
+            self.reducer.begin(self.trainable_params, self.arch_key)
+            if i == 0:
+                out = self.model.train_step(data_batch, None, return_logits=True)
+                teacher = (out["logits"], out["aux_logits"])
+            else:
+                out = self.model.train_step(data_batch, None, teacher_logits=teacher[0],
+                                            aux_teacher_logits=teacher[1], **kd_cfg)
+            _member_backward(self, out["loss"])
+            self.arena.accumulate(self.active_ranges, into="buffer")
+            self.arena.grads_clean = True          # (the move left zeros behind)
+            union = _ranges_union(union, self.active_ranges)
+            loss, logged = out["loss"].detach(), out["log_vars"]["loss"]   # (local / rank-averaged)
+            total = (loss, logged) if total is None else (total[0] + loss, total[1] + logged)
+            for k, v in out["log_vars"].items():
+                log_vars["%s.%s" % (name, k)] = v
+        self.arena.accumulate(union, into="grad")
+        self.arena.grads_clean = False
+        self.arena.sgd_step(union, self.lr, self.momentum, self.weight_decay,
+                            1.0 / gdist.world_size(), True)
+        self.arena.grads_clean = True
+        self.arch_name = "sandwich"
+        log_vars["loss"] = total[1]
+        self.outputs = dict(loss=total[0], log_vars=log_vars, num_samples=len(data_batch["img_metas"]),
+                            members=names, teacher_logits=teacher)
         return self.outputs
 
     def run(self, data_loaders, workflow=(("train", 1),), max_iters=None):

@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class HipLibraryError(RuntimeError):
@@ -66,6 +66,15 @@ class CeDesc(Structure):
                 ("l_sc", c_int64), ("ignore_index", c_int32), ("align_corners", c_int32)]
 
 
+class KdDesc(Structure):
+    """Mirror of ``gs_kd_desc``."""
+    _fields_ = [("N", c_int32), ("h", c_int32), ("w", c_int32), ("Cls", c_int32), ("H", c_int32),
+                ("W", c_int32), ("s_sn", c_int64), ("s_sh", c_int64), ("s_sw", c_int64),
+                ("s_sc", c_int64), ("t_sn", c_int64), ("t_sh", c_int64), ("t_sw", c_int64),
+                ("t_sc", c_int64), ("T", c_float), ("align_corners", c_int32),
+                ("interpolation", c_int32), ("reserved", c_int32)]
+
+
 class SlideDesc(Structure):
     """Mirror of ``gs_slide_desc``."""
     _fields_ = [(k, c_int32) for k in ("N", "C", "ld", "hl", "wl", "hc", "wc", "H", "W", "Ho", "Wo",
@@ -85,7 +94,7 @@ class AugmentDesc(Structure):
 
 _P = c_void_p  # device pointers and the stream travel as plain addresses
 _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
-_CD, _CE, _BN = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs)
+_CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -140,6 +149,10 @@ PROTOTYPES = {
     "gs_ce_backward_ws": (_i32, [_CE, _P, _P, _P, _P, _P, _f32, _P, _i32, _P, _sz, _P]),
     "gs_ce_label_prob": (_i32, [_CE, _P, _P, _P, _P]),
     "gs_resize_argmax": (_i32, [_CE, _P, _P, _P, _P]),
+    "gs_kd_workspace_bytes": (_sz, [_KD]),
+    "gs_kd_forward": (_i32, [_KD, _P, _P, _P, _P, _f32, _P, _P, _sz, _P]),
+    "gs_kd_backward_workspace_bytes": (_sz, [_KD, _i32]),
+    "gs_kd_backward": (_i32, [_KD, _P, _P, _P, _P, _f32, _P, _i32, _P, _sz, _P]),
     "gs_slide_fuse": (_i32, [POINTER(SlideDesc), POINTER(_i32), POINTER(_i32), _P, _P, _P, _P, _P]),
     "gs_debug_set_slide_strip": (_i32, [_i32]),
     "gs_seg_augment": (_i32, [POINTER(AugmentDesc), _P, _P, _P, _P, _P]),
@@ -149,6 +162,7 @@ PROTOTYPES = {
     "gs_sgd_step": (_i32, [_P, _P, _P, _i64, _f32, _f32, _f32, _f32, _i32, _P]),
     "gs_sgd_step_hyper": (_i32, [_P, _P, _P, _i64, _P, _i32, _P]),
     "gs_sgd_set_hyper": (_i32, [_P, _f32, _f32, _f32, _f32, _P]),
+    "gs_grad_accumulate": (_i32, [_P, _P, _i64, _P]),
     "gs_debug_force_plan": (_i32, [_i32, _i32, _i32]),
     "gs_debug_query_plan": (_i32, [_i32, _i32, _i32, _i32, POINTER(_i32), POINTER(_i32), POINTER(_i32),
                                    POINTER(_i32)]),

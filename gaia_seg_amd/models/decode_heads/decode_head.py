@@ -114,13 +114,54 @@ class DynamicBaseDecodeHead(nn.Module, DynamicMixin, metaclass=ABCMeta):
             return [self.forward_acts(tape, self._transform_acts(tape, acts))]
         return tape_function(runner, selected, needs)[0]
 
+    # In-place distillation (sandwich rule): the kwarg that carries this head's teacher logits and the
+    # divisor D of its loss (dynamic_psp_head.py:197,224: 'teacher_logits', 1000;
+    # dynamic_fcn_head.py:182,210: 'aux_teacher_logits', 2000).  None: the head has no such branch.
+    kd_teacher_key = None
+    kd_divisor = None
+
     def forward_train(self, inputs, img_metas, gt_semantic_seg, train_cfg, **kwargs):
-        if kwargs.get("teacher_logits") is not None or kwargs.get("aux_teacher_logits") is not None:
-            raise NotImplementedError(
-                "the in-place distillation branch (dynamic_fcn_head.py:178-227) is outside the "
-                "supernet-training path: EncoderDecoder.forward_train never passes teacher logits")
+        """kwargs (the reference's distillation branch): <kd_teacher_key>, T, distillation_weight,
+        interpolation; ``return_logits=True`` adds the detached low-resolution logits as 'logits'."""
+        return_logits = kwargs.pop("return_logits", False)
+        teacher = None
+        if kwargs:
+            if self.kd_teacher_key is None:
+                if any(kwargs.get(k) is not None for k in ("teacher_logits", "aux_teacher_logits")):
+                    raise NotImplementedError(
+                        "%s has no in-place distillation branch (its reference forward_train takes "
+                        "no teacher logits)" % type(self).__name__)
+            else:
+                teacher = kwargs.get(self.kd_teacher_key)
         seg_logits = self.forward(inputs)
-        return self.losses(seg_logits, gt_semantic_seg)
+        if teacher is not None:
+            losses = self.distill_losses(seg_logits, teacher, gt_semantic_seg,
+                                         T=kwargs.get("T", 2),
+                                         distillation_weight=kwargs.get("distillation_weight", 0.5),
+                                         interpolation=kwargs.get("interpolation", False))
+        else:
+            losses = self.losses(seg_logits, gt_semantic_seg)
+        if return_logits:
+            losses["logits"] = seg_logits.detach()
+        return losses
+
+    def distill_losses(self, seg_logit, teacher_logit, seg_label, T=2, distillation_weight=0.5,
+                       interpolation=False):
+        """dynamic_psp_head.py:204-245: loss_seg = distillation_weight * mean_n(sum_{c,h,w}
+        -softmax(t/T) log softmax(s/T)) / D at the label size (interpolation) or at logit resolution
+        -- no ground-truth term; acc_seg = the TEACHER's accuracy at the label size."""
+        from ..losses.cross_entropy_loss import accuracy
+        from ..losses.distill_loss import kd_loss
+        if seg_label.dim() == 4:
+            seg_label = seg_label.squeeze(1)
+        teacher_logit = teacher_logit.detach()
+        loss = dict()
+        loss["loss_seg"] = kd_loss(seg_logit, teacher_logit, seg_label.shape[1:], T=T,
+                                   distillation_weight=distillation_weight, divisor=self.kd_divisor,
+                                   interpolation=interpolation, align_corners=self.align_corners)
+        loss["acc_seg"] = accuracy(teacher_logit, seg_label, align_corners=self.align_corners,
+                                   ignore_index=self.ignore_index)
+        return loss
 
     def forward_test(self, inputs, img_metas, test_cfg):
         return self.forward(inputs)

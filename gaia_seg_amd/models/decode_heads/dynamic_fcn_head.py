@@ -11,6 +11,7 @@ from .decode_head import DynamicBaseDecodeHead
 
 @HEADS.register_module()
 class DynamicFCNHead(DynamicBaseDecodeHead):
+    kd_teacher_key, kd_divisor = "aux_teacher_logits", 2000.0   # dynamic_fcn_head.py:182,210
     def __init__(self, in_channels, channels, num_classes, num_convs=2, kernel_size=3,
                  concat_input=True, dropout_ratio=0.1, conv_cfg=None, norm_cfg=None,
                  act_cfg=dict(type="ReLU"), in_index=-1, input_transform=None,

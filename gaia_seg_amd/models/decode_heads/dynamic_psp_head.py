@@ -53,6 +53,7 @@ def psp_concat(tape, ppm, x, channels):
 
 @HEADS.register_module()
 class DynamicPSPHead(DynamicBaseDecodeHead):
+    kd_teacher_key, kd_divisor = "teacher_logits", 1000.0   # dynamic_psp_head.py:197,224
     def __init__(self, in_channels, channels, num_classes, pool_scales=(1, 2, 3, 6),
                  dropout_ratio=0.1, conv_cfg=None, norm_cfg=None, act_cfg=dict(type="ReLU"),
                  in_index=-1, input_transform=None,

@@ -121,33 +121,38 @@ class EncoderDecoder(nn.Module):
         out = self._decode_head_forward_test(x, img_metas)
         return self._resize_logits(out, img.shape[2:])
 
-    def _decode_head_forward_train(self, x, img_metas, gt_semantic_seg):
-        loss_decode = self.decode_head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg)
+    def _decode_head_forward_train(self, x, img_metas, gt_semantic_seg, **kwargs):
+        loss_decode = self.decode_head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg,
+                                                     **kwargs)
         return add_prefix(loss_decode, "decode")
 
     def _decode_head_forward_test(self, x, img_metas):
         return self.decode_head.forward_test(x, img_metas, self.test_cfg)
 
-    def _auxiliary_head_forward_train(self, x, img_metas, gt_semantic_seg):
+    def _auxiliary_head_forward_train(self, x, img_metas, gt_semantic_seg, **kwargs):
         losses = dict()
         if isinstance(self.auxiliary_head, nn.ModuleList):
             for idx, aux_head in enumerate(self.auxiliary_head):
-                loss_aux = aux_head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg)
+                loss_aux = aux_head.forward_train(x, img_metas, gt_semantic_seg, self.train_cfg,
+                                                  **kwargs)
                 losses.update(add_prefix(loss_aux, "aux_%d" % idx))
         else:
             loss_aux = self.auxiliary_head.forward_train(x, img_metas, gt_semantic_seg,
-                                                         self.train_cfg)
+                                                         self.train_cfg, **kwargs)
             losses.update(add_prefix(loss_aux, "aux"))
         return losses
 
     def forward_dummy(self, img):
         return self.encode_decode(img, None)
 
-    def forward_train(self, img, img_metas, gt_semantic_seg):
+    def forward_train(self, img, img_metas, gt_semantic_seg, **kwargs):
+        """kwargs go to the decode head and the auxiliary head(s) alike, as in
+        "dynamic_encoder_decoder-distill-backup (1).py":52-64 (the in-place distillation branch:
+        teacher_logits / aux_teacher_logits, T, distillation_weight, interpolation; return_logits)."""
         x = self.extract_feat(img)
         losses = dict()
         if not self.with_auxiliary_head:
-            losses.update(self._decode_head_forward_train(x, img_metas, gt_semantic_seg))
+            losses.update(self._decode_head_forward_train(x, img_metas, gt_semantic_seg, **kwargs))
             return losses
         # The decode head and the auxiliary head(s) are independent consumers of x
         # ("dynamic_encoder_decoder-distill-backup (1).py":85-143; same call order here): the
@@ -159,11 +164,18 @@ class EncoderDecoder(nn.Module):
         branch = ops.BRANCH_AUX and dev.type == "cuda"
         if branch and not getattr(getattr(self, "backbone", None), "_aux_forked", False):
             ops.prefork_branch(dev, ops.SLOT_AUX)
-        losses.update(self._decode_head_forward_train(x, img_metas, gt_semantic_seg))
+        losses.update(self._decode_head_forward_train(x, img_metas, gt_semantic_seg, **kwargs))
         with ops.branch_scope(dev, branch, forked=True):
-            loss_aux = self._auxiliary_head_forward_train(x, img_metas, gt_semantic_seg)
+            loss_aux = self._auxiliary_head_forward_train(x, img_metas, gt_semantic_seg, **kwargs)
         if branch:
             ops.join_branch(dev, ops.SLOT_AUX)     # whoever sums the losses reads both
+            if kwargs.get("return_logits"):
+                # the auxiliary logits were allocated on the branch stream and are read by later
+                # sandwich members on this one: complete (the join above) and kept alive until then
+                cur = torch.cuda.current_stream(dev)
+                for k, v in loss_aux.items():
+                    if k.endswith(".logits"):
+                        v.record_stream(cur)
         losses.update(loss_aux)
         return losses
 
@@ -252,9 +264,18 @@ class EncoderDecoder(nn.Module):
 
     # ---- runner interface ----
     def train_step(self, data_batch, optimizer=None, **kwargs):
-        losses = self(**data_batch)
+        """kwargs reach both heads' forward_train ("dynamic_encoder_decoder-distill-backup (1).py":
+        52-64).  With ``return_logits=True`` the output also carries the heads' detached
+        low-resolution logits as 'logits' (decode head) and 'aux_logits' (auxiliary head, or None):
+        the teacher logits of a sandwich iteration, outside the loss sum and log_vars."""
+        losses = self(**data_batch, **kwargs)
+        logits = losses.pop("decode.logits", None)
+        aux_logits = losses.pop("aux.logits", None)
         loss, log_vars = self._parse_losses(losses)
-        return dict(loss=loss, log_vars=log_vars, num_samples=len(data_batch["img_metas"]))
+        out = dict(loss=loss, log_vars=log_vars, num_samples=len(data_batch["img_metas"]))
+        if kwargs.get("return_logits"):
+            out["logits"], out["aux_logits"] = logits, aux_logits
+        return out
 
     def val_step(self, data_batch, **kwargs):
         return self(**data_batch, **kwargs)

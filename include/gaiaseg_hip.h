@@ -410,6 +410,47 @@ int gs_ohem_weights(const float* prob, int64_t n, int64_t batch_kept, float thre
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* In-place distillation (sandwich rule) — the student members' loss                           */
+/* ------------------------------------------------------------------------------------------ */
+/* The distillation branch of the decode heads' forward_train (gaiaseg/models/decode_heads/
+ * dynamic_psp_head.py:176-245, dynamic_fcn_head.py:161-231), fed by the MAX subnet's logits
+ * (train_step of dynamic_encoder_decoder-distill-backup (1).py:52-64, tools/train_supernet.py:180-187):
+ *   out[0] = scale * sum_{n,c,Y,X} -softmax(t/T)[c] * log softmax(s/T)[c]
+ * with the host's scale = distillation_weight / (N * D) (D = 1000 for the PSP head, 2000 for the FCN
+ * head): the reference's (-bmm(student_score.log(), teacher_score)).mean() / D, a sum over classes and
+ * pixels and a mean over the batch; labels do not enter it.  log softmax is s/T - lse(s/T), finite
+ * where the reference's log(softmax) is not.  Student and teacher share N, h, w, Cls and have their
+ * own element strides.  interpolation = 1: both are bilinearly resized to (H, W) (align_corners as
+ * given) on the fly; interpolation = 0: the loss is taken at logit resolution and (H, W) must equal
+ * (h, w).  Per-pixel losses are summed in double in a fixed order (bit-reproducible). */
+typedef struct gs_kd_desc {
+  int32_t N, h, w, Cls;        /* logits, both tensors                                          */
+  int32_t H, W;                /* evaluation grid: the label size, or (h, w) without interpolation */
+  int64_t s_sn, s_sh, s_sw, s_sc;   /* student strides (elements)                               */
+  int64_t t_sn, t_sh, t_sw, t_sc;   /* teacher strides                                          */
+  float T;                     /* temperature (> 0)                                             */
+  int32_t align_corners;
+  int32_t interpolation;
+  int32_t reserved;
+} gs_kd_desc;
+size_t gs_kd_workspace_bytes(const gs_kd_desc* d);
+/* lse_s / lse_t: optional float [N,H,W]; when non-NULL the per-pixel log-sum-exp of s/T and t/T is
+ * saved there for gs_kd_backward (which requires both).  out: one float. */
+int gs_kd_forward(const gs_kd_desc* d, const float* student, const float* teacher, float* lse_s,
+                  float* lse_t, float scale, float* out, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* ds[n,y,x,c] = adjoint of the resize of grad_scale / T * (softmax(s/T) - softmax(t/T)), written
+ * densely (pixel stride ld_d, columns Cls..ld_d-1 zeroed); the teacher receives no gradient.  With
+ * interpolation and workspace >= gs_kd_backward_workspace_bytes(d, ld_d) the tile form runs (every
+ * term evaluated once, then a fixed-order gather of four corner sums per logit pixel); with a smaller
+ * workspace the gather form (one workgroup per logit pixel).  The workspace size is 0 without
+ * interpolation (pointwise). */
+size_t gs_kd_backward_workspace_bytes(const gs_kd_desc* d, int32_t ld_d);
+int gs_kd_backward(const gs_kd_desc* d, const float* student, const float* teacher,
+                   const float* lse_s, const float* lse_t, float grad_scale, float* ds, int32_t ld_d,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Inference epilogue — K17                                                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* argmax over classes of bilinearly resized logits (softmax is monotone):
@@ -486,6 +527,11 @@ int gs_sgd_set_hyper(float* hyper, float lr, float momentum, float weight_decay,
                      void* stream);
 int gs_sgd_step_hyper(float* param, float* grad, float* momentum_buf, int64_t n, const float* hyper,
                       int32_t zero_grad, void* stream);
+/* Gradient accumulation of a sandwich iteration (one SGD step over several subnets, US-Nets): the
+ * weight-gradient kernels overwrite their gradient, so each member's gradients are moved into an
+ * accumulation arena:  dst[i] += src[i]; src[i] = 0  for i in [0, n).  One launch per range; float4
+ * when both pointers are 16-byte aligned.  dst and src must not overlap. */
+int gs_grad_accumulate(float* dst, float* src, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Training input pipeline                                             */

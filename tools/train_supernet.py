@@ -20,7 +20,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from gaia_seg_amd import __version__  # noqa: E402
-from gaia_seg_amd.apis import set_random_seed, train_segmentor  # noqa: E402
+from gaia_seg_amd.apis import sandwich_train_sampler, set_random_seed, train_segmentor  # noqa: E402
 from gaia_seg_amd.core.config import Config, DictAction  # noqa: E402
 from gaia_seg_amd.core.model_space import build_model_sampler  # noqa: E402
 from gaia_seg_amd.models import build_segmentor  # noqa: E402
@@ -128,6 +128,8 @@ def main():
 
     model = build_segmentor(cfg.model, train_cfg=cfg.get("train_cfg"), test_cfg=cfg.get("test_cfg"))
     logger.info("parameters: %.2f M" % (sum(p.numel() for p in model.parameters()) / 1e6))
+    if cfg.get("use_distillation", False):   # :180-187 (in-place distillation, sandwich rule)
+        cfg.train_sampler = sandwich_train_sampler(cfg)
     train_sampler = build_model_sampler(cfg.train_sampler)
     val_sampler = build_model_sampler(cfg.val_sampler)
     if args.seed is not None:
