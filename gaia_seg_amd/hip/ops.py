@@ -15,6 +15,39 @@ from .runtime import WORKSPACE, Act, _Workspace, current_stream_ptr, round_up
 
 _ws = WORKSPACE
 
+# ---- stream state ------------------------------------------------------------------------------
+# Besides the training stream a device has one weight-gradient side stream and up to two branch
+# streams.  Every order between them is set by ``_fork`` (one event recorded on one stream, waited
+# for on another); the dirty flags say which of them hold work that the training stream has not
+# joined yet.  (More weight-gradient streams, an optimizer stream inside backward, stream priorities
+# and an earlier fork of the auxiliary head were measured and removed: profiles/r04_stream_experiments.md.)
+class _DeviceStreams:
+    __slots__ = ("side", "side_dirty", "branch", "origin", "branch_dirty")
+
+    def __init__(self):
+        self.side = None           # the weight-gradient stream (created on first use)
+        self.side_dirty = False
+        self.branch = {}           # slot -> branch stream (created on first use)
+        self.origin = {}           # slot -> raw handle of the stream the branch was last forked from
+        self.branch_dirty = set()  # slots with work the origin has not joined yet
+
+
+_streams = {}   # (device type, index) -> _DeviceStreams
+
+
+def _state(dev):
+    st = _streams.get((dev.type, dev.index))
+    if st is None:
+        st = _streams[(dev.type, dev.index)] = _DeviceStreams()
+    return st
+
+
+def _fork(src, dst, dev):
+    """Stream ``dst`` waits for everything queued on stream ``src`` so far (raw handles)."""
+    with torch.cuda.device(dev):
+        _lib.check(_L().gs_stream_fork(src, dst), "gs_stream_fork")
+
+
 # ---- weight gradients on a side stream -------------------------------------------------------
 # In backward the weight gradient of a conv is needed only by the optimizer (and the gradient
 # all-reduce), while the data gradient is on the critical path.  The wgrad kernels (MFMA-bound) are
@@ -23,38 +56,20 @@ _ws = WORKSPACE
 # stream joins the side stream at the end of every tape backward and before a gradient bucket is
 # handed to RCCL.  GS_SIDE_WGRAD=0 keeps everything on one stream.
 SIDE_WGRAD = os.environ.get("GS_SIDE_WGRAD", "1") != "0"
-# Weight-gradient streams per device.  r04: the events of the un-profiled step (GS_STEP_EVENTS) put the
-# end of the weight-gradient stream 0.45-0.52 ms BEHIND the end of backward on the training stream —
-# it is the critical path of the step's last half millisecond, where the stage-1 / stem weight
-# gradients (K = 65 536 pixels, a few output tiles, each followed by its slab reduce) run one after the
-# other.  GS_SIDE_STREAMS = N deals the jobs round-robin to N streams, so that one job's slab reduce
-# (HBM-bound) runs beside the next job's contraction (MFMA-bound).  MEASURED (r04, A/B/A/B on one box,
-# profiles/r04_stream_experiments.md): R50 9.54 / 9.63 / 9.68 ms and the sampled mix 12.49 / 12.59 /
-# 12.73 ms per step for N = 1 / 2 / 3 — the end of the step does not move with the queue layout: with
-# two or three kernels resident the chip is throughput-bound during backward, more streams only add
-# contention for the training stream.  Default 1.
-N_SIDE = max(1, int(os.environ.get("GS_SIDE_STREAMS", "1")))
-_side_streams = {}     # (device type, index) -> [torch.cuda.Stream] * N_SIDE
-_side_dirty = {}
-_side_next = {}        # round-robin position per device
 _ws_side = _Workspace()
 
 
-SIDE_PRIORITY = int(os.environ.get("GS_SIDE_PRIORITY", "0"))   # A/B knob: priority of the weight-gradient stream(s)
-
-
-def _side_list(dev):
-    key = (dev.type, dev.index)
-    lst = _side_streams.get(key)
-    if lst is None:
-        # (stream priorities made no difference, r01 A/B)
-        lst = _side_streams[key] = [torch.cuda.Stream(device=dev, priority=SIDE_PRIORITY) for _ in range(N_SIDE)]
-    return lst
-
-
 def _side_stream(dev):
-    """The primary weight-gradient stream (gradient buckets are issued in its context)."""
-    return _side_list(dev)[0]
+    st = _state(dev)
+    if st.side is None:
+        st.side = torch.cuda.Stream(device=dev)
+    return st.side
+
+
+def side_stream(dev):
+    """The weight-gradient stream of ``dev``, or None while nothing has used it."""
+    st = _streams.get((dev.type, dev.index))
+    return st.side if st is not None else None
 
 
 # Weight gradients are handed to the side stream in BATCHES: every hand-over costs one event on the
@@ -91,18 +106,11 @@ def flush_wgrads():
     jobs, _wgrad_jobs = _wgrad_jobs, []
     L = _L()
     dev = jobs[0][6]
-    sides = _side_list(dev)
-    key = (dev.type, dev.index)
-    pos = _side_next.get(key, 0)
+    side = _side_stream(dev)
+    _fork(_wgrad_stream, side.cuda_stream, dev)
     with torch.cuda.device(dev):
-        for i in range(min(len(jobs), len(sides))):     # every stream that gets a job waits for the batch
-            _lib.check(L.gs_stream_fork(_wgrad_stream, sides[(pos + i) % len(sides)].cuda_stream),
-                       "gs_stream_fork")
         for d, x, dy, weight, gw, need, _ in jobs:
-            slot = pos % len(sides)
-            side = sides[slot]
-            pos += 1
-            ws_s = _side_workspace(need, dev, side, slot)
+            ws_s = _side_workspace(need, dev, side)
             # dy and x must outlive the side-stream kernel that reads them: they are kept referenced
             # until the main stream has joined the side stream (join_side_streams) instead of being
             # handed to the caching allocator with record_stream (two calls and one pending event
@@ -113,8 +121,7 @@ def flush_wgrads():
             _lib.check(L.gs_conv2d_wgrad(ctypes.byref(d), x.ptr, dy.data_ptr(), gw.data_ptr(),
                                          ws_s.data_ptr(), ws_s.numel(), side.cuda_stream),
                        "gs_conv2d_wgrad")
-    _side_next[key] = pos % len(sides)
-    _side_dirty[key] = True
+    _state(dev).side_dirty = True
     for job in jobs:
         _notify(job[3])
 
@@ -133,75 +140,19 @@ def side_checkpoint(tape):
         if not DEFER_JOIN:
             return
         flush_wgrads()
-        events = [s.record_event() for key, lst in _side_streams.items() if _side_dirty.get(key)
-                  for s in lst]
+        events = [st.side.record_event() for st in _streams.values() if st.side_dirty]
         SIDE_CHECKPOINT = events or None
     tape.record(backward)
-
-
-# ---- the optimizer stream ------------------------------------------------------------------------
-# At the end of backward the weight-gradient stream is the critical path (it lags the training stream
-# by the stem / stage-1 weight gradients, r04 trace: ~0.4 ms), and the optimizer step of everything
-# else — ~95 % of the parameters, HBM-bound — used to run right there, beside those kernels.  The
-# runner now updates the parameters of stages 3-4 and the heads on a THIRD stream as soon as backward
-# has crossed into stage 2 (their gradients are final then), i.e. in the middle of backward.
-BACKWARD_MARK_CB = None     # set by the runner for the duration of backward: called with the mark's tag
-_opt_streams = {}
-
-
-def opt_stream(dev):
-    key = (dev.type, dev.index)
-    s = _opt_streams.get(key)
-    if s is None:
-        s = _opt_streams[key] = torch.cuda.Stream(device=dev)
-    return s
-
-
-def backward_mark(tape, tag):
-    """Record a point of the tape; when the backward replay crosses it, the runner's callback (if any)
-    is told.  Everything recorded AFTER the mark has run its backward by then."""
-    def backward():
-        cb = BACKWARD_MARK_CB
-        if cb is not None:
-            cb(tag)
-    tape.record(backward)
-
-
-def fork_to(stream, dev):
-    """``stream`` waits for everything queued so far on the current stream, on the weight-gradient
-    stream (queued jobs are handed over first) and on the branch streams of ``dev``."""
-    flush_wgrads()
-    key = (dev.type, dev.index)
-    L = _L()
-    with torch.cuda.device(dev):
-        cur = current_stream_ptr()
-        srcs = {cur}
-        if _side_dirty.get(key):
-            srcs.update(sd.cuda_stream for sd in _side_streams.get(key, ()))
-        for bkey, br in _branch_streams.items():
-            if bkey[:2] == key and _branch_dirty.get(bkey):
-                srcs.add(br.cuda_stream)
-        for src in srcs:
-            if src != stream.cuda_stream:
-                _lib.check(L.gs_stream_fork(src, stream.cuda_stream), "gs_stream_fork")
-
-
-def join_from(stream, dev):
-    """The current stream waits for everything queued on ``stream``."""
-    with torch.cuda.device(dev):
-        _lib.check(_L().gs_stream_fork(stream.cuda_stream, current_stream_ptr()), "gs_stream_fork")
 
 
 def join_side_streams(dev=None):
     """Make the current stream wait for the weight-gradient kernels queued on the side stream."""
     flush_wgrads()
-    for key, lst in _side_streams.items():
-        if _side_dirty.get(key) and (dev is None or (dev.type, dev.index) == key):
-            with torch.cuda.device(lst[0].device):
-                for s in lst:
-                    _lib.check(_L().gs_stream_fork(s.cuda_stream, current_stream_ptr()), "gs_stream_fork")
-            _side_dirty[key] = False
-    if dev is None or not any(_side_dirty.values()):
+    for key, st in _streams.items():
+        if st.side_dirty and (dev is None or (dev.type, dev.index) == key):
+            _fork(st.side.cuda_stream, current_stream_ptr(), st.side.device)
+            st.side_dirty = False
+    if dev is None or not any(st.side_dirty for st in _streams.values()):
         # everything the side stream read is now ordered before whatever the current stream does
         # next: the operands may go back to the allocator
         _side_keep.clear()
@@ -209,38 +160,32 @@ def join_side_streams(dev=None):
 
 def side_stream_after_main(dev):
     """The side stream, made to wait for everything queued so far on the current stream and on the
-    other compute stream of this device (a gradient bucket holds BatchNorm gradients written on the
+    branch streams of this device (a gradient bucket holds BatchNorm gradients written on the
     training stream and, where a branch ran, on the branch stream)."""
     s = _side_stream(dev)
-    key = (dev.type, dev.index)
-    with torch.cuda.device(dev):
-        cur = current_stream_ptr()
-        _lib.check(_L().gs_stream_fork(cur, s.cuda_stream), "gs_stream_fork")
-        others = {sd.cuda_stream for sd in _side_list(dev)[1:]} if _side_dirty.get(key) else set()
-        for bkey, br in _branch_streams.items():
-            if bkey[:2] == key and _branch_dirty.get(bkey):
-                others.add(br.cuda_stream)
-                others.add(_branch_origin.get(bkey))
-        for other in others:
-            if other is not None and other != cur:
-                _lib.check(_L().gs_stream_fork(other, s.cuda_stream), "gs_stream_fork")
-    _side_dirty[key] = True   # the main stream joins it at the end of backward
+    st = _state(dev)
+    cur = current_stream_ptr()
+    _fork(cur, s.cuda_stream, dev)
+    others = set()
+    for slot, br in st.branch.items():
+        if slot in st.branch_dirty:
+            others.add(br.cuda_stream)
+            others.add(st.origin[slot])
+    for other in others:
+        if other != cur:
+            _fork(other, s.cuda_stream, dev)
+    st.side_dirty = True   # the main stream joins it at the end of backward
     return s
 
 
-def _side_workspace(need, dev, side, slot=0):
-    """Split-K scratch of a side stream (allocated under that stream, so the caching allocator
-    orders its reuse against that stream's kernels; one buffer per stream)."""
-    buf = _ws_side._buf.get((dev.type, dev.index, slot))
+def _side_workspace(need, dev, side):
+    """Split-K scratch of the side stream (allocated under that stream, so the caching allocator
+    orders its reuse against that stream's kernels)."""
+    buf = _ws_side._buf.get((dev.type, dev.index, 0))
     if buf is not None and buf.numel() >= need:
         return buf
-    keep = _ws_side.slot
-    _ws_side.slot = slot
-    try:
-        with torch.cuda.stream(side):
-            return _ws_side.get(need, dev)
-    finally:
-        _ws_side.slot = keep
+    with torch.cuda.stream(side):
+        return _ws_side.get(need, dev)
 
 
 def reserve_workspaces(dev, nbytes=192 << 20):
@@ -248,9 +193,7 @@ def reserve_workspaces(dev, nbytes=192 << 20):
     the supernet can make (96 MiB of split-K slabs + reduction partials), so that a step graph
     capture never sees a workspace being (re)allocated."""
     _ws.get(nbytes, dev)
-    for slot, side in enumerate(_side_list(dev)):
-        _side_workspace(nbytes, dev, side, slot)
-
+    _side_workspace(nbytes, dev, _side_stream(dev))
 
 
 # ---- the branch stream -------------------------------------------------------------------------
@@ -260,7 +203,7 @@ def reserve_workspaces(dev, nbytes=192 << 20):
 # queue, fenced by events:
 #   * the projection shortcut (conv + BN) of a stage's first block, beside conv1 -> conv2, forward
 #     and backward (gaiaseg/models/utils/dynamic_res_layer.py:70-125);
-#   * the auxiliary head with its loss, beside stage 4 / the decode head
+#   * the auxiliary head with its loss, beside the decode head
 #     ("dynamic_encoder_decoder-distill-backup (1).py":85-143: two independent consumers of x).
 # Same kernels, same operands, same results; only the queue differs.  GS_BRANCH=0 keeps one queue;
 # GS_BRANCH_SHORTCUT / GS_BRANCH_AUX switch the two uses separately.
@@ -268,27 +211,16 @@ BRANCH = os.environ.get("GS_BRANCH", "1") != "0"
 BRANCH_SHORTCUT = BRANCH and os.environ.get("GS_BRANCH_SHORTCUT", "1") != "0"
 BRANCH_AUX = BRANCH and os.environ.get("GS_BRANCH_AUX", "1") != "0"
 BRANCH_SHORTCUT_MAX_GFLOP = float(os.environ.get("GS_BRANCH_SHORTCUT_MAX_GFLOP", "8"))
-# GS_AUX_PREFORK=1: the auxiliary heads' stream forks behind the stage they read (they then run beside
-# the later stages too) instead of behind the whole backbone (beside the decode head only).  Measured
-# (profiles/r04_stream_experiments.md): no faster, and the stage-4 K3 launches share the chip with the
-# auxiliary head's 3x3 (K3 0.574 vs 0.582 of peak on R50) -- default off.
-AUX_PREFORK = os.environ.get("GS_AUX_PREFORK", "0") == "1"
 SLOT_SHORTCUT, SLOT_AUX = 1, 2   # scratch slot / branch stream index (0 = the training stream)
-_branch_streams = {}     # (device type, index, slot) -> torch.cuda.Stream
 _branch_slot_of = {}     # raw stream handle -> slot (adopt_current_stream)
-_branch_origin = {}      # branch key -> raw handle of the stream it was last forked from
-_branch_dirty = {}
 _branch_cb_armed = False
-BRANCH_PRIORITY = os.environ.get("GS_BRANCH_PRIORITY", "0") == "1"
 
 
 def _branch_stream(dev, slot):
-    key = (dev.type, dev.index, slot)
-    s = _branch_streams.get(key)
+    st = _state(dev)
+    s = st.branch.get(slot)
     if s is None:
-        # (GS_BRANCH_PRIORITY=1: the branch streams at the training stream's high priority — A/B knob)
-        s = torch.cuda.Stream(device=dev, priority=-1 if BRANCH_PRIORITY else 0)
-        _branch_streams[key] = s
+        s = st.branch[slot] = torch.cuda.Stream(device=dev)
         _branch_slot_of[s.cuda_stream] = slot
     return s
 
@@ -300,17 +232,16 @@ def on_branch():
 def prefork_branch(dev, slot):
     """Make branch stream ``slot`` wait for what is queued on the current stream NOW; a later
     ``branch_scope(..., forked=True)`` then starts from this point of the current stream instead of
-    from its tail at that time (the auxiliary head forks behind stage 3 while the host goes on to
-    queue stage 4)."""
+    from its tail at that time (the auxiliary head forks behind the backbone while the host goes on
+    to queue the decode head)."""
     if not BRANCH or dev.type != "cuda" or on_branch():
         return
     br = _branch_stream(dev, slot)
-    key = (dev.type, dev.index, slot)
+    st = _state(dev)
     cur = current_stream_ptr()
-    with torch.cuda.device(dev):
-        _lib.check(_L().gs_stream_fork(cur, br.cuda_stream), "gs_stream_fork")
-    _branch_origin[key] = cur
-    _branch_dirty[key] = True
+    _fork(cur, br.cuda_stream, dev)
+    st.origin[slot] = cur
+    st.branch_dirty.add(slot)
 
 
 def _enter_branch(dev, slot, fork=True):
@@ -318,13 +249,12 @@ def _enter_branch(dev, slot, fork=True):
     the current stream (with its own scratch buffers).  Returns the stream to go back to."""
     flush_wgrads()            # (backward) queued weight gradients belong to the stream we leave
     br = _branch_stream(dev, slot)
+    st = _state(dev)
     prev = torch.cuda.current_stream(dev)
-    key = (dev.type, dev.index, slot)
-    if fork or _branch_origin.get(key) != prev.cuda_stream:
-        with torch.cuda.device(dev):
-            _lib.check(_L().gs_stream_fork(prev.cuda_stream, br.cuda_stream), "gs_stream_fork")
-        _branch_origin[key] = prev.cuda_stream
-    _branch_dirty[key] = True
+    if fork or st.origin.get(slot) != prev.cuda_stream:
+        _fork(prev.cuda_stream, br.cuda_stream, dev)
+        st.origin[slot] = prev.cuda_stream
+    st.branch_dirty.add(slot)
     torch.cuda.set_stream(br)
     _ws.slot = slot
     return prev
@@ -338,23 +268,20 @@ def _leave_branch(prev):
 
 def join_branch(dev, slot):
     """The current stream waits for everything queued on branch stream ``slot`` so far."""
-    key = (dev.type, dev.index, slot)
-    br = _branch_streams.get(key)
-    if br is None or not _branch_dirty.get(key):
-        return
-    with torch.cuda.device(dev):
-        _lib.check(_L().gs_stream_fork(br.cuda_stream, current_stream_ptr()), "gs_stream_fork")
+    st = _state(dev)
+    if slot in st.branch_dirty:
+        _fork(st.branch[slot].cuda_stream, current_stream_ptr(), dev)
 
 
 def join_branch_streams():
     """End of a step's backward: the stream the branches were forked from waits for them."""
     global _branch_cb_armed
     _branch_cb_armed = False
-    for key, br in _branch_streams.items():
-        if _branch_dirty.get(key) and _branch_origin.get(key) is not None:
-            with torch.cuda.device(br.device):
-                _lib.check(_L().gs_stream_fork(br.cuda_stream, _branch_origin[key]), "gs_stream_fork")
-            _branch_dirty[key] = False
+    for st in _streams.values():
+        for slot, br in st.branch.items():
+            if slot in st.branch_dirty:
+                _fork(br.cuda_stream, st.origin[slot], br.device)
+        st.branch_dirty.clear()
 
 
 def adopt_current_stream():
