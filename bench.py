@@ -3,7 +3,7 @@
 FCN decode head + aux FCN head on the dynamic R50..R101 supernet, bs 2 per GPU, one randomly sampled
 subnet per step (the reference's train sampler), fp32, synthetic data, random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run)
 
 A step = sample arch -> zero grads of the active ranges -> forward (HIP kernels) -> backward
 (HIP kernels) with the bucketed RCCL all-reduce of the active gradient ranges overlapped ->
@@ -13,12 +13,16 @@ fused SGD(momentum, weight decay) with poly LR.  Nothing is skipped inside the t
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD (before anything touches
 the GPU) and exits with its code; the ranks are one process per GPU over RCCL.
 
-Rank 0 prints ONE JSON line.  `value` comes from K un-instrumented steps.  Besides the contract
-fields the line carries
-  check        : before any timing, the first timed step's subnet and batch are run once from the
-                 initial weights (dropout off: device RNG streams cannot match the CPU) and the
-                 losses compared with the committed oracle values (tests/golden/bench_check.json,
-                 made by tests/golden/make_bench_check.py); a mismatch > 1e-3 aborts the benchmark;
+Rank 0 prints ONE JSON line.  `value` comes from K un-instrumented steps.  Before any timing, the
+first timed step's subnet and batch are run once from the initial weights (dropout off: device RNG
+streams cannot match the CPU); this untimed step is part of the state the timed steps start from.
+A plain run does only what the headline needs: set-up, that step, the W warm-up steps, the timed
+passes, --dump-outputs, and the result line with the contract fields, `config` and `distributed`.
+
+`--full` adds the measurements and checks that cost time of their own; the line then also carries
+  check        : the losses of that first step compared with the committed oracle values
+                 (tests/golden/bench_check.json, made by tests/golden/make_bench_check.py); a
+                 mismatch > 1e-3 aborts the benchmark (a plain run reports it as skipped);
   roofline     : the dynamic 3x3 bottleneck conv forward, timed with HIP events on the
                  launch stream in a SEPARATE instrumented pass over the same K draws (so the
                  instrumentation never sits inside `value`): achieved = sum(2*M*N*K FLOPs) / sum(time)
@@ -62,12 +66,16 @@ def parse_args():
                     help="'pipeline' (diagnostics): every timed step's batch is produced by the GPU input "
                          "pipeline (gs_seg_augment, datasets/gpu_pipeline.py) from resident uint8 "
                          "2048x1024 images, so the input stage's cost per step is on record")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the oracle check of "
+                         "the first step, the K3 roofline pass, roofline_step and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-baseline-size", default="512x1024",
                     help="HxW of the bounded CPU sample (config batch size, R50 anchor)")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the oracle check of the first step (diagnostics only)")
-    ap.add_argument("--no-k3-timer", action="store_true")
+                    help="skip the first step from the initial weights and, with --full, its oracle "
+                         "check (diagnostics only)")
+    ap.add_argument("--no-k3-timer", action="store_true", help="with --full: no K3 roofline pass")
     ap.add_argument("--step-graphs", action="store_true",
                     help="replay recurring subnets' training step from a captured HIP graph "
                          "(IterBasedRunner.train_iter; off by default: slower on ROCm 7.2, see "
@@ -213,14 +221,32 @@ def launch_ranks(n):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def first_step_check(model, cfg_path, seed, size, bs, arch_meta, batch, dev, strict=False):
+def first_step(model, arch_meta, batch):
     """Run the first timed step's subnet and batch once from the initial weights with dropout off and
-    compare the losses with the committed oracle values.  Returns the `check` entry; raises on a
-    mismatch.  strict (the default configuration, seed and crop): a missing or stale fixture is an
-    error too, so the gate cannot disappear silently; diagnostic overrides report "skipped".  (The BN running statistics it moves and the gradients it leaves are part of the
-    warm-up state; nothing of it is timed.)"""
+    return its log variables.  (The BN running statistics it moves and the gradients it leaves are
+    part of the warm-up state; nothing of it is timed.)"""
     import torch
     from gaia_seg_amd.core.dynamic import fold_dict
+    heads = [h for h in (model.decode_head, getattr(model, "auxiliary_head", None)) if h is not None]
+    saved_h = [h.dropout for h in heads]
+    for h in heads:
+        h.dropout = None
+    try:
+        model.manipulate_arch(fold_dict(arch_meta)["arch"])
+        out = model.train_step(batch, None)
+        out["loss"].backward()
+        torch.cuda.synchronize()
+    finally:
+        for h, d in zip(heads, saved_h):
+            h.dropout = d
+    return {k: float(v) for k, v in out["log_vars"].items()}
+
+
+def first_step_check(model, cfg_path, seed, size, bs, arch_meta, got, strict=False):
+    """--full: compare first_step()'s log variables `got` and the initial weights (the step moves no
+    parameter) with the committed oracle values.  Returns the `check` entry; raises on a mismatch.
+    strict (the default configuration, seed and crop): a missing or stale fixture is an error too, so
+    the gate cannot disappear silently; diagnostic overrides report "skipped"."""
     key = "%s|seed%d|%dx%d|bs%d|%s" % (os.path.basename(cfg_path), seed, size[0], size[1], bs,
                                        arch_meta.get("name", "random"))
     path = os.path.join(ROOT, "tests", "golden", "bench_check.json")
@@ -242,19 +268,6 @@ def first_step_check(model, cfg_path, seed, size, bs, arch_meta, batch, dev, str
             raise SystemExit("bench.py: %s; regenerate tests/golden/bench_check.json (tests/golden/"
                              "make_bench_check.py) or pass --no-check" % msg)
         return dict(status="skipped", reason=msg)
-    heads = [h for h in (model.decode_head, getattr(model, "auxiliary_head", None)) if h is not None]
-    saved_h = [h.dropout for h in heads]
-    for h in heads:
-        h.dropout = None
-    try:
-        model.manipulate_arch(fold_dict(arch_meta)["arch"])
-        out = model.train_step(batch, None)
-        out["loss"].backward()
-        torch.cuda.synchronize()
-    finally:
-        for h, d in zip(heads, saved_h):
-            h.dropout = d
-    got = {k: float(v) for k, v in out["log_vars"].items()}
     worst = 0.0
     for k, want in gold["log_vars"].items():
         if k.endswith("acc_seg"):
@@ -498,18 +511,23 @@ def main():
     if args.crop:
         size = tuple(int(v) for v in args.crop.split("x"))
 
-    # ---- parity gate: the first timed step's subnet and batch against the committed oracle losses
+    # ---- the first timed step's subnet and batch from the initial weights; --full: the parity gate
+    # against the committed oracle losses
     check = dict(status="skipped", reason="--no-check")
     if not args.no_check:
         first_meta = fixed_meta if fixed_meta is not None else sampler.sample()
         sampler.seed(args.seed)
         b0 = make_batch(bs, size[0], size[1], 19, args.seed * 1000003, dev)   # rank 0's first batch
-        default_cfg = os.path.join(ROOT, "configs/supernet/fcn_ar50to101v2.py")
-        strict = (os.path.abspath(args.config) == default_cfg and args.seed == 0 and not args.crop
-                  and args.arch in ("sample", "R50"))
-        check = first_step_check(model, args.config, args.seed, size, bs, first_meta, b0, dev, strict)
+        got = first_step(model, first_meta, b0)
         arena.zero_grad()
         del b0
+        if args.full:
+            default_cfg = os.path.join(ROOT, "configs/supernet/fcn_ar50to101v2.py")
+            strict = (os.path.abspath(args.config) == default_cfg and args.seed == 0 and not args.crop
+                      and args.arch in ("sample", "R50"))
+            check = first_step_check(model, args.config, args.seed, size, bs, first_meta, got, strict)
+        else:
+            check = dict(status="skipped", reason="the oracle comparison runs with --full")
 
     if fixed_meta is None:
         runner.register_hook(ManipulateArchHook(sampler))
@@ -584,8 +602,9 @@ def main():
         prof.enable()
     seg0 = torch.cuda.memory_stats(dev).get("segment.all.allocated", 0)
     import ctypes
-    L.gs_debug_conv_launch_flops(None, 1)
-    L.gs_debug_k3_flops(None, 1)
+    if args.full:
+        L.gs_debug_conv_launch_flops(None, 1)
+        L.gs_debug_k3_flops(None, 1)
     if runner.step_events is not None:
         runner.step_events.clear()
     passes = [timed_pass(False)]                     # <- `value`: nothing but the training steps
@@ -595,9 +614,10 @@ def main():
                                                           key=lambda kv: kv[1])), file=sys.stderr)
         runner.step_events = None
     kl = (ctypes.c_double * 15)()
-    L.gs_debug_conv_launch_flops(kl, 1)              # which MFMA path carried the first pass's FLOPs
     k3kl = (ctypes.c_double * 5)()
-    L.gs_debug_k3_flops(k3kl, 1)
+    if args.full:
+        L.gs_debug_conv_launch_flops(kl, 1)          # which MFMA path carried the first pass's FLOPs
+        L.gs_debug_k3_flops(k3kl, 1)
     seg_new = torch.cuda.memory_stats(dev).get("segment.all.allocated", 0) - seg0
     bytes_per_step = (reducer.bytes_reduced - bytes0) / max(args.steps, 1)
     collectives_per_step = reducer.collectives / max(args.steps, 1) if world > 1 else 0.0
@@ -629,7 +649,7 @@ def main():
                               for k, v in sorted(call_prof.items(), key=lambda kv: -kv[1][1])[:12]),
                   file=sys.stderr)
     k3 = None
-    if not args.no_k3_timer:
+    if args.full and not args.no_k3_timer:
         # separate pass over the same draws with HIP events on the launch stream around every
         # bottleneck-conv2 forward (gs_k3_timer_*, include/gaiaseg_hip.h)
         elapsed_instr = timed_pass(True)
@@ -677,7 +697,7 @@ def main():
                                "of both operands, fp32 accumulation (GS_X3=0 / GS_X3_FWD=0 turn them "
                                "off; the unsplit forwards stay on the fp32 MFMA for parity margin: "
                                "DESIGN.md section 11); the measured FLOP shares are in "
-                               "roofline.flop_share_by_k_loop and roofline_step.flop_share_by_k_loop",
+                               "roofline.flop_share_by_k_loop and roofline_step.flop_share_by_k_loop (--full)",
                 "step_graphs": dict(runner.graph_stats, built_at_startup=graphs_built,
                                     what="HIP-graph replay of recurring subnets' whole training "
                                          "step (same kernels as the eager step); counts cover "
@@ -699,28 +719,28 @@ def main():
         hooks = [h for h in runner.hooks if isinstance(h, ManipulateArchHook)]
         if hooks:
             out["config"]["archs"] = hooks[0].history[arch_log_start:arch_log_end]
-        fl, k3_alg = step_flops(model, sampler, args.seed, args.steps, size, bs, fixed_meta)
-        fl *= world
-        # share of the launched contraction FLOPs per K loop (library counters over the first pass)
-        kl_tot = sum(kl) or 1.0
-        x3_share = sum(kl[o * 5 + 3] for o in range(3)) / kl_tot
-        fwd_tot = sum(kl[0:5]) or 1.0
-        blended = 1.0 / ((1.0 - x3_share) / FP32_MFMA_PEAK_TFLOPS + x3_share / X3_LDS_BOUND_TFLOPS)
-        ach_step = fl / elapsed / 1e12 / world
-        out["roofline_step"] = {
-            "what": "all convolutions of the %d timed steps, fwd + dgrad + wgrad (BN / pooling / loss "
-                    "/ SGD carry no credited FLOPs)" % args.steps,
-            "bound": "mfma", "achieved": round(ach_step, 2),
-            "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s per GPU",
-            "frac": round(ach_step / FP32_MFMA_PEAK_TFLOPS, 4),
-            "algorithmic_gflop_per_step_per_gpu": round(fl / args.steps / world / 1e9, 1),
-            "flop_share_by_k_loop": {"fp32_mfma": round(1.0 - x3_share, 4), "bf16x3": round(x3_share, 4)},
-            "blended_bound": round(blended, 1),
-            "frac_of_blended_bound": round(ach_step / blended, 4),
-            "bound_note": "`frac` divides fp32-equivalent FLOPs by the fp32 MFMA peak (157.3); the share "
-                          "of the FLOPs launched on the bf16x3 loop (stride-1 data gradients) is bounded "
-                          "by LDS bandwidth at %.0f fp32-equivalent TFLOP/s instead, so the step's "
-                          "bound is the harmonic blend above" % X3_LDS_BOUND_TFLOPS}
+        if args.full:
+            fl, k3_alg = step_flops(model, sampler, args.seed, args.steps, size, bs, fixed_meta)
+            fl *= world
+            # share of the launched contraction FLOPs per K loop (library counters over the first pass)
+            kl_tot = sum(kl) or 1.0
+            x3_share = sum(kl[o * 5 + 3] for o in range(3)) / kl_tot
+            blended = 1.0 / ((1.0 - x3_share) / FP32_MFMA_PEAK_TFLOPS + x3_share / X3_LDS_BOUND_TFLOPS)
+            ach_step = fl / elapsed / 1e12 / world
+            out["roofline_step"] = {
+                "what": "all convolutions of the %d timed steps, fwd + dgrad + wgrad (BN / pooling / loss "
+                        "/ SGD carry no credited FLOPs)" % args.steps,
+                "bound": "mfma", "achieved": round(ach_step, 2),
+                "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s per GPU",
+                "frac": round(ach_step / FP32_MFMA_PEAK_TFLOPS, 4),
+                "algorithmic_gflop_per_step_per_gpu": round(fl / args.steps / world / 1e9, 1),
+                "flop_share_by_k_loop": {"fp32_mfma": round(1.0 - x3_share, 4), "bf16x3": round(x3_share, 4)},
+                "blended_bound": round(blended, 1),
+                "frac_of_blended_bound": round(ach_step / blended, 4),
+                "bound_note": "`frac` divides fp32-equivalent FLOPs by the fp32 MFMA peak (157.3); the share "
+                              "of the FLOPs launched on the bf16x3 loop (stride-1 data gradients) is bounded "
+                              "by LDS bandwidth at %.0f fp32-equivalent TFLOP/s instead, so the step's "
+                              "bound is the harmonic blend above" % X3_LDS_BOUND_TFLOPS}
         if k3 is not None:
             launches, ms, flops, el_i = k3
             achieved = flops / (ms * 1e-3) / 1e12
@@ -759,7 +779,7 @@ def main():
                                "`value` is from the un-instrumented pass)"
                                % (args.steps, 1e3 * el_i / args.steps),
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             h, w = (int(v) for v in args.cpu_baseline_size.split("x"))
             out["cpu_baseline"] = cpu_baseline(cfg, (h, w), args.seed, bs)
         print(json.dumps(out))
