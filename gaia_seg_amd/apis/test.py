@@ -82,3 +82,31 @@ def multi_gpu_test(model, data_loader, size=None, **kw):
     if size is None:
         size = len(part) * gdist.world_size()
     return collect_results(part, size)
+
+
+def test_model_space(model, loader, metas, num_batches, num_classes, ignore_index=255,
+                     calib_cfg=None, metric_tag="direct", logger=None):
+    """Evaluate every subnet of a model space (the loop of the reference's tools/test_supernet.py).
+
+    For each flat meta: ``manipulate_arch`` with its arch, ``apply_bn_calibration(.., 'test')`` with
+    ``calib_cfg`` (``cfg.caliberate_bn``: use_minibatch_stats), then ``core.evaluation.evaluate_model``
+    over ``num_batches`` batches of ``loader`` (on-device confusion matrix, one all-reduce when
+    distributed: every rank returns the same rows).  Returns one row per meta: the meta (other
+    metric tags included) plus ``metric.<tag>.mIoU`` / ``.mAcc`` / ``.aAcc``.  The model's
+    ``fp16_enabled`` (core.fp16_utils.wrap_fp16_model) decides the conv precision."""
+    from ..core.dynamic import fold_dict
+    from ..core.evaluation import evaluate_model
+    from ..core.model_space import _listify
+    apply_bn_calibration(model, calib_cfg, "test")
+    rows = []
+    for i, meta in enumerate(metas):
+        model.manipulate_arch(_listify(fold_dict(meta).get("arch", {})))
+        res = evaluate_model(model, loader, num_batches, num_classes, ignore_index)
+        row = dict(meta)
+        for k in ("mIoU", "mAcc", "aAcc"):
+            row["metric.%s.%s" % (metric_tag, k)] = res[k]
+        rows.append(row)
+        if logger is not None and gdist.rank() == 0:
+            logger.info("subnet %d/%d %s: mIoU %.4f mAcc %.4f aAcc %.4f"
+                        % (i + 1, len(metas), meta.get("name", i), res["mIoU"], res["mAcc"], res["aAcc"]))
+    return rows

@@ -9,6 +9,7 @@ SURVEY.md Appendix A15.  A *meta* is a flat dict with dotted keys
 ``manipulate_arch`` consumes.
 """
 import copy
+import json
 import random
 
 from .registry import Registry, build_from_cfg
@@ -216,3 +217,189 @@ def arch_key(meta):
             return tuple(sorted((k, freeze(x)) for k, x in v.items()))
         return v
     return tuple(sorted((k, freeze(v)) for k, v in meta.items() if k.startswith("arch")))
+
+
+# ------------------------------------------------------------------------------------------------
+# Model-space files and sampling rules (tools/test_supernet.py)
+#
+# A reconstruction: gaiavision's ``ModelSpaceManager`` / ``build_sample_rule`` are absent
+# dependencies.  Their behaviour is restated from what the reference's configs and tools ask of them
+# (``model_space_path`` + ``model_sampling_rules`` of the test configs, tools/test_supernet.py's
+# ``ModelSpaceManager.load(path).ms_manager.apply_rule(rule).pack()``), with the semantics below
+# (DESIGN.md section 16):
+#   * a model-space file is a JSON list of flat metas with dotted keys (what tools/count_flops.py
+#     writes) or the same metas as JSON lines; lists become tuples before any rule sees them;
+#   * the rules work on a list of GROUPS (lists of rows), starting from one group of every row;
+#   * filter (``func_str``; no type or type='eval'): keep the rows of each group the lambda accepts;
+#   * 'sequential': its ``rules`` in order;  'parallel': every sub-rule on every input group, one
+#     output group per (input group, sub-rule), input-group-major;
+#   * 'sample': per group, ``operation`` 'random' (a draw from random.Random(seed, group index):
+#     identical on every rank and every call) or 'top' (sorted by ``key``, largest first), of
+#     ``value`` rows (mode 'number') or int(value * len(group)) rows (mode 'ratio'); the
+#     rows keep the drawn / sorted order;
+#   * 'merge': the groups concatenated in order, later duplicates (same arch_key) dropped: one group.
+# ------------------------------------------------------------------------------------------------
+
+
+def _tuplify(v):
+    if isinstance(v, (list, tuple)):
+        return tuple(_tuplify(x) for x in v)
+    if isinstance(v, dict):
+        return {k: _tuplify(x) for k, x in v.items()}
+    return v
+
+
+def _listify(v):
+    if isinstance(v, (list, tuple)):
+        return [_listify(x) for x in v]
+    if isinstance(v, dict):
+        return {k: _listify(x) for k, x in v.items()}
+    return v
+
+
+def load_model_space(path):
+    """Rows of a model-space file (JSON list or JSON lines) with list values as tuples."""
+    with open(path) as fh:
+        text = fh.read()
+    if text.lstrip().startswith("["):
+        rows = json.loads(text)
+    else:
+        rows = [json.loads(line) for line in text.splitlines() if line.strip()]
+    for i, r in enumerate(rows):
+        if not isinstance(r, dict):
+            raise ValueError("%s: row %d is a %s, not a flat meta" % (path, i, type(r).__name__))
+    return [_tuplify(r) for r in rows]
+
+
+def dump_model_space(rows, path):
+    """Write rows as a JSON list (tools/count_flops.py's format); tuples are written as lists."""
+    with open(path, "w") as fh:
+        json.dump([_listify(r) for r in rows], fh, indent=1)
+
+
+class ModelSpace:
+    """The rows of a model space; ``apply_rule`` narrows them, ``pack`` hands them to the model."""
+
+    def __init__(self, rows):
+        self.rows = [_tuplify(dict(r)) for r in rows]
+
+    @classmethod
+    def load(cls, path):
+        return cls(load_model_space(path))
+
+    def dump(self, path):
+        dump_model_space(self.rows, path)
+
+    def apply_rule(self, rule):
+        if isinstance(rule, dict):
+            rule = build_sample_rule(rule)
+        groups = rule([list(self.rows)])
+        return ModelSpace([r for g in groups for r in g])
+
+    def pack(self):
+        """The nested arch of every row, the form ``manipulate_arch`` takes (fold_dict(meta)['arch'])."""
+        from .dynamic import fold_dict
+        return [_listify(fold_dict(r).get("arch", {})) for r in self.rows]
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __iter__(self):
+        return iter(self.rows)
+
+
+class _FilterRule:
+    def __init__(self, func_str):
+        self.func_str = func_str
+        self.fn = eval(func_str, {"__builtins__": __builtins__}, {})  # config text, like the config
+        if not callable(self.fn):
+            raise ValueError("func_str must evaluate to a callable, got %r" % (func_str,))
+
+    def __call__(self, groups):
+        return [[r for r in g if self.fn(r)] for g in groups]
+
+
+class _SequentialRule:
+    def __init__(self, rules):
+        self.rules = [build_sample_rule(r) for r in rules]
+
+    def __call__(self, groups):
+        for r in self.rules:
+            groups = r(groups)
+        return groups
+
+
+class _ParallelRule:
+    def __init__(self, rules):
+        self.rules = [build_sample_rule(r) for r in rules]
+
+    def __call__(self, groups):
+        out = []
+        for g in groups:
+            for r in self.rules:
+                out.extend(r([list(g)]))
+        return out
+
+
+class _SampleRule:
+    def __init__(self, operation, value, mode="number", key=None, seed=0, func_str=None):
+        if operation not in ("random", "top"):
+            raise ValueError("sample: operation must be 'random' or 'top', got %r" % (operation,))
+        if mode not in ("number", "ratio"):
+            raise ValueError("sample: mode must be 'number' or 'ratio', got %r" % (mode,))
+        if operation == "top" and key is None:
+            raise ValueError("sample: operation='top' needs a key")
+        self.operation, self.value, self.mode, self.key, self.seed = operation, value, mode, key, seed
+        self.filter = _FilterRule(func_str) if func_str else None
+
+    def _count(self, n):
+        k = int(self.value) if self.mode == "number" else int(self.value * n)
+        return max(0, min(n, k))
+
+    def __call__(self, groups):
+        if self.filter is not None:
+            groups = self.filter(groups)
+        out = []
+        for gi, g in enumerate(groups):
+            k = self._count(len(g))
+            if self.operation == "random":
+                out.append(random.Random(self.seed * 1000003 + gi).sample(list(g), k))
+            else:
+                out.append(sorted(g, key=lambda r: r[self.key], reverse=True)[:k])
+        return out
+
+
+class _MergeRule:
+    def __call__(self, groups):
+        seen, out = set(), []
+        for g in groups:
+            for r in g:
+                k = arch_key(r)
+                if k not in seen:
+                    seen.add(k)
+                    out.append(r)
+        return [out]
+
+
+def build_sample_rule(cfg):
+    """A callable list-of-groups -> list-of-groups from a rule config (see the section comment)."""
+    if callable(cfg) and not isinstance(cfg, dict):
+        return cfg
+    cfg = dict(cfg)
+    t = cfg.pop("type", None)
+    if t is None or t == "eval":
+        if set(cfg) != {"func_str"}:
+            raise ValueError("a filter rule takes exactly func_str, got %s" % sorted(cfg))
+        return _FilterRule(cfg["func_str"])
+    if t == "sequential":
+        return _SequentialRule(cfg.pop("rules"))
+    if t == "parallel":
+        return _ParallelRule(cfg.pop("rules"))
+    if t == "sample":
+        return _SampleRule(**cfg)
+    if t == "merge":
+        if cfg:
+            raise ValueError("merge takes no options, got %s" % sorted(cfg))
+        return _MergeRule()
+    raise ValueError("unknown model-sampling rule type %r (have eval, sequential, parallel, sample, "
+                     "merge)" % (t,))

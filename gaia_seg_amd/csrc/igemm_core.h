@@ -1355,6 +1355,144 @@ __device__ __forceinline__ void x3_k_loop(int nk16, float* ldsf,
 }
 
 // ------------------------------------------------------------------------------------------
+// f16 forward K loop (gs_set_forward_precision(1): inference only).  x3_k_loop<BFWD> with ONE piece:
+// both operands are rounded once to fp16 at the stage store (round to nearest even: a plain
+// _Float16 conversion, v_cvt_f16_f32 -- not the round-toward-zero v_cvt_pkrtz) and contracted with
+// one v_mfma_f32_16x16x32_f16 per 16x16x32 of work, accumulating in fp32.  Same step (two 16-channel
+// K steps), same interleaved chunk order and the same 80-byte LDS rows as the bf16x3 forward: the
+// f16 MFMA's A / B lane maps are the bf16 ones (lane l holds A[l & 15][8 (l >> 4) + j] and
+// B[8 (l >> 4) + j][l & 15]; tests/test_fwd_f16_gpu.py checks them with exact integer data).
+// AFF (in_affine): the loader's register set carries the BatchNorm coefficients of its K step (see
+// igemm_rows_fast_kernel) and relu((x - mean) * scale + beta) is evaluated in fp32 here, before the
+// rounding, with the padding select applied to the activation -- the bottleneck convs that consume
+// a deferred BN + ReLU (ops.DEFER_EDGES) reach the loop without an activation pass through HBM.
+// A stage is a third of the bf16x3 one (64 x 80 + BN x 80 bytes): kF16Stages = 2 stages (one
+// barrier per step) fit in 20 KB, so registers, not LDS, bound the workgroups per CU; kF16Sets = 2
+// register sets keep the global loads two steps ahead of the MFMAs.
+// ------------------------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ unsigned f16_pair(float lo, float hi) {
+  return __builtin_bit_cast(unsigned, f16x2{(_Float16)lo, (_Float16)hi});
+}
+// interleaved chunk [lo0, hi0, lo1, hi1, lo2, hi2, lo3, hi3] (the x3_pack_il order)
+__device__ __forceinline__ u32x4 f16_pack_il(const f32x4 lo4, const f32x4 hi4) {
+  return u32x4{f16_pair(lo4[0], hi4[0]), f16_pair(lo4[1], hi4[1]), f16_pair(lo4[2], hi4[2]),
+               f16_pair(lo4[3], hi4[3])};
+}
+
+#ifndef GS_F16_STAGES
+#define GS_F16_STAGES 2
+#endif
+constexpr int kF16Stages = GS_F16_STAGES;
+constexpr int kF16Sets = 2;
+
+template <int BN>
+struct F16Tile {
+  static constexpr int ROWB = 80;
+  static constexpr int PA = 64 * ROWB, PB = BN * ROWB;
+  static constexpr int STAGE = PA + PB;                    // bytes
+  static constexpr int LDS_FLOATS = kF16Stages * STAGE / 4;
+};
+
+// AS: the register-set size of the loader (1, or 1 + 4 coefficient quads with AFF)
+template <int BM, int BN, int AS, bool AFF, class LA, class LB>
+__device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
+                                           f32x4 (&acc)[Tile<BM, BN>::TM][Tile<BM, BN>::TN],
+                                           int wave, int lane, int t, int b_row, int b_kq,
+                                           LA&& load_a, LB&& load_b) {
+  using T = Tile<BM, BN>;
+  using X = F16Tile<BN>;
+  using G = ColGroups<T::TN>;
+  static_assert(BM == 64 && T::BV == 1 && AS == (AFF ? 5 : 1), "f16 loop: 64-row tiles, BN <= 64");
+  unsigned char* lds = reinterpret_cast<unsigned char*>(ldsf);
+  const int li = lane & 15, fk = lane >> 4;
+  const int row = t >> 2, kq = t & 3;
+  const bool b_on = b_row < BN;
+  f32x4 a0[kF16Sets][AS], a1[kF16Sets][AS], b0[kF16Sets][1], b1[kF16Sets][1];
+  auto gload = [&](int set) __attribute__((always_inline)) {
+    load_a(a0[set]); load_b(b0[set]);     // (load_b advances the K state)
+    load_a(a1[set]); load_b(b1[set]);
+  };
+  // the A operand of a register set: the gathered values, or relu(bn(.)) of them with the padding
+  // (and the K steps past the end) zeroed
+  auto act = [&](const f32x4 (&ra)[AS]) __attribute__((always_inline)) {
+    if constexpr (AFF) {
+      const unsigned okbits = __builtin_bit_cast(unsigned, ra[4][0]);
+      const f32x4 v = bn_relu_affine(ra[0], ra[1], ra[2], ra[3]);
+      return (okbits & 1u) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      return ra[0];
+    }
+  };
+  auto sstore = [&](int set, unsigned char* st) __attribute__((always_inline)) {
+    *reinterpret_cast<u32x4*>(st + row * X::ROWB + kq * 16) = f16_pack_il(act(a0[set]), act(a1[set]));
+    if (b_on) {
+      // column b_row + e, (step 1, step 2) of k row b_kq: one dword per column (see x3_k_loop<BFWD>)
+      const u32x4 pk = f16_pack_il(b0[set][0], b1[set][0]);
+      unsigned char* pb = st + X::PA + b_row * X::ROWB + (b_kq >> 2) * 16 + (b_kq & 3) * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) *reinterpret_cast<unsigned*>(pb + e * X::ROWB) = pk[e];
+    }
+  };
+  constexpr bool QUAD = BN == 64;   // 2 x 2 waves of 32 x 32 (the bf16x3 loop's layout)
+  int brow[T::TN];
+#pragma unroll
+  for (int j = 0; j < T::TN; ++j) brow[j] = G::base(j) + G::width(j) * li + (j - G::first(j));
+  auto compute = [&](const unsigned char* cb) __attribute__((always_inline)) {
+    if constexpr (QUAD) {
+      f16x8 qa[2], qb[2];
+      const int ar = (wave >> 1) * 32 + li, bc = (wave & 1) * 32 + li;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        qa[h] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
+            cb + (ar + h * 16) * X::ROWB + fk * 16));
+        qb[h] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
+            cb + X::PA + (bc + h * 16) * X::ROWB + fk * 16));
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qa[q >> 1], qb[q & 1], acc[0][q], 0, 0, 0);
+      return;
+    }
+    const f16x8 fa = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
+        cb + (wave * 16 + li) * X::ROWB + fk * 16));
+#pragma unroll
+    for (int j = 0; j < T::TN; ++j) {
+      const f16x8 fb = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
+          cb + X::PA + brow[j] * X::ROWB + fk * 16));
+      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, fb, acc[0][j], 0, 0, 0);
+    }
+  };
+  const int nst = (nk16 + 1) >> 1;
+  if (nst <= 0) return;
+  unsigned char* buf0 = lds;
+  unsigned char* buf1 = kF16Stages == 2 ? lds + X::STAGE : lds;
+  // (loads past the K range return zeros -- and AFF zeroes their activation: no prologue guard)
+#pragma unroll
+  for (int u = 0; u < kF16Sets; ++u) gload(u);
+  sstore(0, buf0);
+  __syncthreads();
+#define GS_F16_PHASE(I, CUR, NXT)                                 \
+  if (s + (I) < nst) {                                             \
+    gload((I) % kF16Sets);                                         \
+    compute(CUR);                                                  \
+    if (kF16Stages == 1) __syncthreads();                          \
+    sstore(((I) + 1) % kF16Sets, NXT);                             \
+    __syncthreads();                                               \
+  }
+  static_assert(12 % kF16Sets == 0 && kF16Sets >= 2, "the phase loop is unrolled by 12");
+  for (int s = 0; s < nst; s += 12) {
+    GS_F16_PHASE(0, buf0, buf1) GS_F16_PHASE(1, buf1, buf0) GS_F16_PHASE(2, buf0, buf1)
+    GS_F16_PHASE(3, buf1, buf0) GS_F16_PHASE(4, buf0, buf1) GS_F16_PHASE(5, buf1, buf0)
+    GS_F16_PHASE(6, buf0, buf1) GS_F16_PHASE(7, buf1, buf0) GS_F16_PHASE(8, buf0, buf1)
+    GS_F16_PHASE(9, buf1, buf0) GS_F16_PHASE(10, buf0, buf1) GS_F16_PHASE(11, buf1, buf0)
+  }
+#undef GS_F16_PHASE
+}
+
+// ------------------------------------------------------------------------------------------
 // Fast path of forward / stride-1 dgrad for the shapes that carry the FLOPs: NHWC source,
 // channels per tap a multiple of BK (every width of the search space is a multiple of 16), 1x1 or
 // 3x3.  Versus the general kernel above:
@@ -1385,13 +1523,17 @@ __device__ __forceinline__ unsigned long long gs_stamp() {
 // split-K slabs (IgemmArgs::tickets) and / or merge their tile partials (col_tickets) themselves.
 // A variant of its own because that code's loads in flight cost registers the many-round launches
 // would pay for in occupancy.
+// F16: the forward on f16_k_loop (gs_set_forward_precision(1)); AFF allowed.
 template <int BM, int BN, bool BTRANS, int KS, int ABL = 0, int ROLE = 0, bool PIPE = true,
-          bool PAIR = false, bool AFF = false, bool X3 = false, bool SK = false>
+          bool PAIR = false, bool AFF = false, bool X3 = false, bool SK = false, bool F16 = false>
 __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) {
   using T = Tile<BM, BN>;
   static_assert(!X3 || (PIPE && !PAIR && !AFF && ABL == 0 && BN <= 64), "bf16x3 loop: no loader fusion");
+  static_assert(!F16 || (PIPE && !PAIR && !X3 && !BTRANS && ABL == 0 && BM == 64 && BN <= 64),
+                "f16 loop: forward, 64-row tiles");
   constexpr int LDS_X3 = X3Tile<BN>::LDS_FLOATS > T::C_SZ + 512 ? X3Tile<BN>::LDS_FLOATS : T::C_SZ + 512;
-  constexpr int LDS_TILES = X3 ? LDS_X3 : (PAIR ? T::LDSF2 : T::LDSF);
+  constexpr int LDS_F16 = F16Tile<BN>::LDS_FLOATS > T::C_SZ + 512 ? F16Tile<BN>::LDS_FLOATS : T::C_SZ + 512;
+  constexpr int LDS_TILES = F16 ? LDS_F16 : (X3 ? LDS_X3 : (PAIR ? T::LDSF2 : T::LDSF));
   __shared__ __attribute__((aligned(16))) float lds[LDS_TILES + (AFF ? 3 * kAffMaxC : 0)];
   constexpr int AS = BM / 64;
   constexpr int AX = AFF ? AS + 4 : AS;   // register-set size handed to the pipelined loop
@@ -1602,7 +1744,7 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
     const int x3_boff = 4 * (x3_kr * p.d_row + x3_col);
     auto load_b = [&](f32x4 (&rb)[T::BV]) __attribute__((always_inline)) {
       const bool kvalid = k_left > 0;
-      if constexpr (X3 && !BTRANS) {
+      if constexpr ((X3 || F16) && !BTRANS) {
         const unsigned off = (x3_bok && kvalid) ? (unsigned)(x3_boff + bbase) : kOOB;
         rb[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dense, off, 0, 0));
       } else
@@ -1661,7 +1803,9 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
       }
     };
     GS_STAMP(st_l0)
-    if constexpr (X3)
+    if constexpr (F16)
+      f16_k_loop<BM, BN, AX, AFF>(nk, lds, acc, wave, lane, t, 4 * x3_nq, x3_kr, load_a, load_b);
+    else if constexpr (X3)
       x3_k_loop<BM, BN, AX, !BTRANS>(nk, lds, acc, wave, lane, t, BTRANS ? (t >> 2) : 4 * x3_nq,
                                      BTRANS ? (t & 3) : x3_kr, load_a, load_b);
     else if constexpr (PAIR)
@@ -1723,7 +1867,7 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
       (void)d_bar;
     }
   } else {
-    rows_epilogue<BM, BN, (X3 && BN == 64), SK>(p, lds, acc, m0, n0, t, wave, lane, split, tile);
+    rows_epilogue<BM, BN, ((X3 || F16) && BN == 64), SK>(p, lds, acc, m0, n0, t, wave, lane, split, tile);
   }
 #undef GS_STAMP
 }
@@ -2166,11 +2310,20 @@ extern double g_launch_flops[3][GS_KLOOP_COUNT];   // algorithmic 2*M*N*K per (o
 extern double g_k3_flops[GS_KLOOP_COUNT];          // the same for the role-1 (bottleneck conv2) forward launches
 // (the forward thread, the autograd thread and their side-stream launches all add to these:
 // flops_add in common.h)
+// GS_KLOOP_F16 lies outside the [GS_KLOOP_COUNT] tables (their layout is ABI): its launches and
+// FLOPs have counters of their own (gs_debug_f16_launches)
+extern long long g_f16_launches;
+extern double g_f16_flops;
 static inline void note_launch(int op, int kloop, const Plan& pl, bool aff, int bw_mode,
                                double flops = 0.0) {
-  flops_add(&g_launch_flops[op][kloop], flops);
   g_last_launch = gs_debug_launch{op, kloop, pl.bm, pl.bn, pl.splits, pl.nk_per_split, aff ? 1 : 0,
                                   bw_mode};
+  if (kloop == GS_KLOOP_F16) {
+    flops_add(&g_f16_flops, flops);
+    __atomic_fetch_add(&g_f16_launches, 1LL, __ATOMIC_RELAXED);
+    return;
+  }
+  flops_add(&g_launch_flops[op][kloop], flops);
   // (mode 3 = mode 2's mask read from bytes: counted with mode 2, the record keeps the 3)
   const int bwi = bw_mode == 3 ? 2 : (bw_mode < 0 || bw_mode > 2 ? 0 : bw_mode);
   __atomic_fetch_add(&g_launch_counts[op][kloop][bwi], 1LL, __ATOMIC_RELAXED);
@@ -2359,8 +2512,16 @@ static inline bool x3_grid_ok(const Plan& pl, int min_ksteps_) {
          (pl.splits == 1 || pl.nk_per_split >= split_min) &&
          (long)pl.tiles_m * pl.tiles_n * pl.splits >= 2L * num_cu();
 }
+// Forward precision (gs_set_forward_precision): 0 = fp32 (default), 1 = fp16 operands.
+extern int g_fwd_precision;   // capi_misc.hip
+static inline bool f16_fwd_on() { return g_fwd_precision == 1; }
+// The f16 loop's tiles: 64 rows, BN 64 or 48 (plan_fwd narrows the planner's 80 / 32 to them).
+static inline bool f16_plan_ok(const Plan& pl) { return pl.bm == 64 && (pl.bn == 64 || pl.bn == 48); }
+
 template <bool BTRANS>
 static inline int rows_fast_kloop(const Plan& pl, bool in_affine, int ks = 3) {
+  // fp16 mode: every fast forward launch on a 64-row tile, in_affine included
+  if (!BTRANS && f16_fwd_on() && f16_plan_ok(pl)) return GS_KLOOP_F16;
   if constexpr (BTRANS) {
     static const int x3_min = env_int("GS_X3", 4);
     if (x3_grid_ok(pl, x3_min) && (pl.bn == 64 || pl.bn == 48)) return GS_KLOOP_BF16X3;
@@ -2412,7 +2573,8 @@ static void launch_rows_fast(const Plan& pl, const IgemmArgs& a_in, hipStream_t 
   const bool pair = kloop == GS_KLOOP_FP32_PAIRS;
   note_launch(BTRANS ? GS_OP_DGRAD : GS_OP_FORWARD, kloop, pl, a.a_coeffs != nullptr, a.bw_mode,
               2.0 * a.M * (double)a.Nn * a.Ktot);
-  if (ROLE == 1 && !BTRANS) flops_add(&g_k3_flops[kloop], 2.0 * a.M * (double)a.Nn * a.Ktot);
+  if (ROLE == 1 && !BTRANS && kloop < GS_KLOOP_COUNT)
+    flops_add(&g_k3_flops[kloop], 2.0 * a.M * (double)a.Nn * a.Ktot);
   if (a.tickets && splitk_combine_ok(pl)) __atomic_fetch_add(&g_splitk_combined, 1LL, __ATOMIC_RELAXED);
   else a.tickets = nullptr;
   // (GS_SKL: the extended-epilogue instantiation when the launch carries arrival counters)
@@ -2430,6 +2592,29 @@ static void launch_rows_fast(const Plan& pl, const IgemmArgs& a_in, hipStream_t 
 #define GS_PLAIN(...) \
   launch_rows_kernel((igemm_rows_fast_kernel<__VA_ARGS__, false>), grid, block, lds_dyn, st, a, ev0, ev1)
   int lds_dyn = 0;
+  if constexpr (!BTRANS) {
+    if (kloop == GS_KLOOP_F16) {
+#define GS_F16L(BN_, AFF_)                                                                       \
+  do {                                                                                           \
+    if (a.tickets || a.col_tickets)                                                              \
+      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, false, KS, 0, ROLE, true, false, AFF_, \
+                                                 false, true, true>), grid, block, 0, st, a, ev0, ev1);  \
+    else                                                                                         \
+      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, false, KS, 0, ROLE, true, false, AFF_, \
+                                                 false, false, true>), grid, block, 0, st, a, ev0, ev1); \
+  } while (0)
+      if (a.a_coeffs) {
+        if (pl.bn == 64) GS_F16L(64, true);
+        else GS_F16L(48, true);
+      } else if (pl.bn == 64) {
+        GS_F16L(64, false);
+      } else {
+        GS_F16L(48, false);
+      }
+#undef GS_F16L
+      return;
+    }
+  }
   if (kloop == GS_KLOOP_BF16X3) {
     if constexpr (BTRANS) {
       if (pl.bn == 64) GS_SKL(64, 64, true, KS, 0, ROLE, true, false, false, true);
@@ -2561,8 +2746,21 @@ static bool x_is_vector(const gs_conv_desc* d) {
          (d->x_sn & 3) == 0;
 }
 
+// fp16 mode: a fast-kernel forward whose plan has 64-row tiles of 80 or 32 columns gets 64 or 48
+// columns instead (the f16 loop's tiles; the split-K factor, hence the workspace, is unchanged)
 static Plan plan_fwd(const gs_conv_desc* d) {
-  return make_plan(d->N * d->Ho * d->Wo, d->Co, d->KH * d->KW * d->Ci, true);
+  Plan pl = make_plan(d->N * d->Ho * d->Wo, d->Co, d->KH * d->KW * d->Ci, true);
+  if (f16_fwd_on() && pl.bm == 64 && (pl.bn == 80 || pl.bn == 32) && g_force_plan[0] == 0 &&
+      x_is_vector(d) && getenv("GS_NO_FAST") == nullptr) {
+    const int ks = (d->KH == 1 && d->KW == 1) ? 1 : ((d->KH == 3 && d->KW == 3) ? 3 : 0);
+    const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
+    const size_t dense_b = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
+    if (fast_rows_ok(d->Ci, ks, src_b, dense_b)) {
+      pl.bn = pl.bn == 80 ? 64 : 48;
+      pl.tiles_n = (int)ceil_div(d->Co, pl.bn);
+    }
+  }
+  return pl;
 }
 static Plan plan_dgrad(const gs_conv_desc* d) {
   return make_plan(d->N * d->H * d->W, d->Ci, d->KH * d->KW * d->Co, true);

@@ -555,10 +555,58 @@ def materialize_residual(tape, r):
     return z
 
 
+# ---- forward precision (inference) -----------------------------------------------------------
+# gs_set_forward_precision: 0 = fp32 (default), 1 = the fast forward launches contract fp16-rounded
+# operands with fp32 accumulation (include/gaiaseg_hip.h).  The library picks the K loop and the
+# tile at launch time from the switch: neither the workspace size nor anything in the conv_bn plan
+# cache (_ConvBnPlan) depends on it, so the cache keys do not carry it.  This mirror of the switch
+# lets conv2d / conv_bn refuse a recording tape without a library call per layer.
+_PRECISIONS = {"fp32": _lib.PRECISION_FP32, "fp16": _lib.PRECISION_FP16}
+FORWARD_PRECISION = _lib.PRECISION_FP32
+
+
+def set_forward_precision(mode):
+    """Set the library's forward precision ('fp32' / 'fp16'); returns the previous name."""
+    global FORWARD_PRECISION
+    if mode not in _PRECISIONS:
+        raise ValueError("forward precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
+    prev = "fp16" if FORWARD_PRECISION == _lib.PRECISION_FP16 else "fp32"
+    _lib.check(_L().gs_set_forward_precision(_PRECISIONS[mode]), "gs_set_forward_precision")
+    FORWARD_PRECISION = _PRECISIONS[mode]
+    return prev
+
+
+class forward_precision:
+    """``with forward_precision("fp16"): ...`` -- inference forwards with fp16 operands; the previous
+    precision is restored on exit, exceptions included.  A conv that records a tape (training)
+    inside raises: the backward kernels assume an fp32 forward."""
+
+    def __init__(self, mode):
+        if mode not in _PRECISIONS:
+            raise ValueError("forward precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
+        self.mode = mode
+        self._prev = None
+
+    def __enter__(self):
+        self._prev = set_forward_precision(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        set_forward_precision(self._prev)
+        return False
+
+
+def _check_precision(tape):
+    if FORWARD_PRECISION != _lib.PRECISION_FP32 and tape.enabled:
+        raise RuntimeError("fp16 forward precision is inference only: a conv was called with a "
+                           "recording tape (training) inside forward_precision('fp16')")
+
+
 def conv2d(tape, x, weight, bias, co, stride=1, pad=0, dil=1, out=None, tag=None):
     """DynConv2d forward: y = conv(x, weight[:co, :x.C]) (+ bias[:co]).
 
     ``co`` is the active output width; the active input width is x.C."""
+    _check_precision(tape)
     L = _L()
     x = materialize(tape, x)
     co_eff = round_up(co, 4)
@@ -880,6 +928,7 @@ def conv_bn(tape, x, weight, co, bn, stride=1, pad=0, dil=1, relu=False, residua
     included).  If x came out of a training-mode BN + ReLU (``x.bnb``), the dgrad epilogue then also
     applies that ReLU's mask and reduces that BN's backward sums (gs_bn_bwd_fuse): the producer's
     backward finds them in ``x.bnb_sums`` and skips its reduction pass over dz and y."""
+    _check_precision(tape)
     L = _L()
     co_eff = round_up(co, 4)
     if co_eff != co:   # channel counts that are not multiples of 4 keep the two-step path

@@ -6,6 +6,7 @@ reference tree at gaiaseg/models/segmentors/dynamic_encoder_decoder-distill-back
 (extract_feat, encode_decode, slide / whole inference, simple_test, aug_test), which this class
 follows.  ``train_step`` / ``_parse_losses`` follow SURVEY.md Appendix A12.
 """
+import contextlib
 from collections import OrderedDict
 
 import torch
@@ -209,9 +210,15 @@ class EncoderDecoder(nn.Module):
             logit = self._resize_logits(logit, img_meta[0]["ori_shape"][:2])
         return logit
 
+    def _test_precision(self):
+        """``fp16_enabled`` (core.fp16_utils.wrap_fp16_model): the test-time convs contract fp16
+        operands (ops.forward_precision); activations, BN, pooling, resize and the epilogue stay fp32."""
+        return ops.forward_precision("fp16") if self.fp16_enabled else contextlib.nullcontext()
+
     def simple_test_device(self, img, img_meta, rescale=True):
         """simple_test that keeps the label map on the device: int64 [N, H, W]."""
-        return self._view(img, img_meta, rescale)[0]
+        with self._test_precision():
+            return self._view(img, img_meta, rescale)[0]
 
     def simple_test(self, img, img_meta, rescale=True):
         return list(self.simple_test_device(img, img_meta, rescale).cpu().numpy())
@@ -223,10 +230,11 @@ class EncoderDecoder(nn.Module):
         if not rescale:
             raise ValueError("aug_test needs rescale=True (views of different sizes)")
         acc = None
-        for k, (img, meta) in enumerate(zip(imgs, img_metas)):
-            last = k == len(imgs) - 1
-            labels, acc = self._view(img, meta, rescale, probs_in=acc, want_probs=not last,
-                                     want_labels=last)
+        with self._test_precision():
+            for k, (img, meta) in enumerate(zip(imgs, img_metas)):
+                last = k == len(imgs) - 1
+                labels, acc = self._view(img, meta, rescale, probs_in=acc, want_probs=not last,
+                                         want_labels=last)
         return list(labels.cpu().numpy())
 
     def forward_test(self, imgs, img_metas, **kwargs):

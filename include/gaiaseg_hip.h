@@ -567,6 +567,23 @@ int gs_seg_augment(const gs_augment_desc* d, const uint8_t* img, const uint8_t* 
                    float* out_img, int64_t* out_label, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Forward precision of the convolutions (inference; tools/test_supernet.py with cfg.fp16).       */
+/*   0 = fp32 (default): every launch as documented above.                                     */
+/*   1 = fp16 operands: a forward launch of gs_conv2d_forward / gs_conv_bn_forward that takes   */
+/*       the fast row kernel with a 64-row tile (columns narrowed to 64 / 48 where the planner  */
+/*       chose 80 / 32) contracts on GS_KLOOP_F16: both operands -- the input AFTER its fp32     */
+/*       in_affine BatchNorm + ReLU -- are rounded once to fp16 (round to nearest even) and     */
+/*       multiplied on v_mfma_f32_16x16x32_f16 with fp32 accumulation.  The error of an output   */
+/*       is that of an fp64 contraction of the rounded operands plus fp32 accumulation noise    */
+/*       (~1e-6 of sum |a||b|).  Outputs, BatchNorm, residual, ReLU and split-K stay fp32.       */
+/*       The stem, the 1x1 streaming kernel, the generic kernel and all data- and weight-       */
+/*       gradient launches keep their fp32 paths.  Not for training: the gradients assume fp32. */
+/* Process-global.  gs_set_forward_precision returns GS_E_BADARG for any other mode.            */
+/* ------------------------------------------------------------------------------------------ */
+int gs_set_forward_precision(int32_t mode);
+int32_t gs_get_forward_precision(void);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Tuning hook (tools/sweep_conv_plans.py): force tile rows (64|128), tile columns            */
 /* (32|48|64|80|96|128) and split-K factor of the following gs_conv2d_* calls; bm = 0 restores */
 /* the planner.  Process-global, not thread-safe, results stay exact (only the fixed summation */
@@ -590,7 +607,10 @@ int gs_debug_query_plan(int32_t M, int32_t N, int32_t K, int32_t max_splits, int
 #define GS_KLOOP_FP32_PAIRS 2   /* the same, two K steps per barrier                                  */
 #define GS_KLOOP_BF16X3 3       /* six v_mfma_f32_16x16x32_bf16 over an exact 3-way bf16 split        */
 #define GS_KLOOP_STREAM 4       /* 1x1 streaming kernel: weights resident in LDS, persistent over rows  */
-#define GS_KLOOP_COUNT 5
+#define GS_KLOOP_COUNT 5         /* entries per op of the count / FLOP tables below (GS_KLOOP_F16 has none) */
+#define GS_KLOOP_F16 5           /* forward, fp16 mode only: one v_mfma_f32_16x16x32_f16 on operands
+                                  * rounded to fp16; reported by gs_debug_last_conv_launch and
+                                  * gs_debug_query_conv_launch, counted by gs_debug_f16_launches  */
 typedef struct gs_debug_launch {
   int32_t op;                   /* GS_OP_*                                                            */
   int32_t kloop;                /* GS_KLOOP_*                                                         */
@@ -646,8 +666,12 @@ int gs_debug_set_stream_mode(int32_t mode);
 /* The same for the forward launches with role GS_CONV_ROLE_BOTTLENECK3X3 only: flops[kloop], 5 entries
  * (which bound bench.py's headline `roofline` is priced against). */
 int gs_debug_k3_flops(double* flops, int32_t reset);
+/* Launches on GS_KLOOP_F16 since the last reset (*n) and their algorithmic FLOPs (*flops, 2 * M * N * K);
+ * either pointer may be NULL, reset != 0 clears both after reading. */
+int gs_debug_f16_launches(int64_t* n, double* flops, int32_t reset);
 /* What gs_conv2d_forward / _dgrad / _wgrad (op = GS_OP_*) WOULD launch for this descriptor: host
- * arithmetic only, no GPU needed (honours gs_debug_force_plan and the GS_X3 switches).  For a strided
+ * arithmetic only, no GPU needed (honours gs_debug_force_plan, the GS_X3 switches and
+ * gs_set_forward_precision).  For a strided
  * dgrad it describes the parity class (0, 0). */
 int gs_debug_query_conv_launch(const gs_conv_desc* d, int32_t op, gs_debug_launch* out);
 
