@@ -21,8 +21,8 @@ import torch
 from ..core import dist as gdist
 from ..core.param_arena import ParamArena
 from ..core.runner import (ArenaOptimizerHook, CheckpointHook, FixedLrUpdaterHook,
-                           IterBasedRunner, ManipulateArchHook, PolyLrUpdaterHook, SandwichHook,
-                           TextLoggerHook, check_sandwich_model)
+                           Fp16ArenaOptimizerHook, IterBasedRunner, ManipulateArchHook,
+                           PolyLrUpdaterHook, SandwichHook, TextLoggerHook, check_sandwich_model)
 from ..core.synthetic import SyntheticLoader
 
 
@@ -87,8 +87,25 @@ def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_cl
     return dataset_cfg  # already an iterable of batches
 
 
+def optimizer_hook(optimizer_config):
+    """``cfg.optimizer_config`` -> the arena optimizer hook (mmcv's register_training_hooks builds
+    the hook it names).  ``type='Fp16OptimizerHook'`` turns on fp16 training with its ``loss_scale``
+    (core/runner.py Fp16ArenaOptimizerHook); any other (or no) type is the fp32 OptimizerHook.  A
+    top-level ``fp16`` key alone means fp16 evaluation (tools/test_supernet.py), not training."""
+    oc = dict(optimizer_config or {})
+    if oc.get("grad_clip"):
+        raise NotImplementedError("grad_clip")
+    if oc.pop("type", None) == "Fp16OptimizerHook":
+        return Fp16ArenaOptimizerHook(**oc)
+    return ArenaOptimizerHook()
+
+
 def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed=False,
                     validate=False, timestamp=None, meta=None, logger=None):
+    opt_hook = optimizer_hook(cfg.get("optimizer_config"))
+    if cfg.get("use_distillation", False) and isinstance(opt_hook, Fp16ArenaOptimizerHook):
+        raise ValueError("use_distillation with fp16 training (optimizer_config type "
+                         "'Fp16OptimizerHook') is not supported")
     device = torch.device("cuda", torch.cuda.current_device())
     model = model.to(device)
     arena = ParamArena(model)
@@ -120,9 +137,7 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
     lrc = dict(cfg.get("lr_config") or dict(policy="fixed"))
     policy = lrc.pop("policy", "fixed")
     runner.register_hook(PolyLrUpdaterHook(**lrc) if policy == "poly" else FixedLrUpdaterHook())
-    if cfg.get("optimizer_config", {}) and dict(cfg.optimizer_config).get("grad_clip"):
-        raise NotImplementedError("grad_clip")
-    runner.register_hook(ArenaOptimizerHook())
+    runner.register_hook(opt_hook)
     ck = cfg.get("checkpoint_config")
     if ck:
         runner.register_hook(CheckpointHook(**dict(ck)))

@@ -219,7 +219,11 @@ class ArenaOptimizerHook(Hook):
         ops.DEFER_JOIN = True          # the tapes hand their weight gradients over but do not join
         runner.mark("fwd_end")
         try:
-            runner.outputs["loss"].backward()
+            loss = runner.outputs["loss"]
+            if runner.loss_scale != 1.0:
+                loss.backward(gradient=runner.loss_seed(loss))   # (static loss scale S)
+            else:
+                loss.backward()
         finally:
             ops.DEFER_JOIN = False
         t1 = time.perf_counter() if prof is not None else 0.0
@@ -229,7 +233,7 @@ class ArenaOptimizerHook(Hook):
             runner.mark("bwd_end_side0", side)
         ops.join_branch_streams()      # (auxiliary head / shortcut work on the branch stream)
         runner.reducer.finish()
-        scale = 1.0 / gdist.world_size()
+        scale = runner.grad_scale()
         early, late = runner.split_ranges()
         ck = ops.SIDE_CHECKPOINT
         if ck is not None and early:
@@ -254,6 +258,50 @@ class ArenaOptimizerHook(Hook):
             prof["finish+sgd"] = prof.get("finish+sgd", 0.0) + (time.perf_counter() - t1)
 
 
+class Fp16ArenaOptimizerHook(ArenaOptimizerHook):
+    """``optimizer_config = dict(type='Fp16OptimizerHook', loss_scale=...)`` (mmcv's hook, which
+    mmseg's fp16 configs name) on the arena SGD: fp16 conv operands in the training step
+    (ops.train_precision: forward and data gradient) and a static loss scale S --
+    backward is seeded with S and SGD's gradient scale becomes 1 / (world_size * S).  As mmcv's hook
+    does in before_run, the model is wrapped for fp16 (its evaluation then runs in fp16 as well) and
+    a scaler state found in ``runner.meta['fp16']['loss_scaler']`` (a resumed checkpoint) is restored.
+    Only the static form: ``loss_scale='dynamic'`` or a dict are refused (not implemented)."""
+
+    def __init__(self, grad_clip=None, loss_scale=512., coalesce=True, bucket_size_mb=-1,
+                 distributed=True):
+        super().__init__(grad_clip)
+        from .fp16_utils import LossScaler
+        self.loss_scaler = LossScaler(**parse_loss_scale(loss_scale))
+
+    def before_run(self, runner):
+        from .fp16_utils import wrap_fp16_model
+        if any(isinstance(h, SandwichHook) for h in runner.hooks):
+            raise ValueError("fp16 training with use_distillation (sandwich) is not supported")
+        wrap_fp16_model(runner.model)
+        saved = ((runner.meta or {}).get("fp16") or {}).get("loss_scaler")
+        if saved is not None:
+            self.loss_scaler.load_state_dict(saved)
+        runner.train_precision = "fp16"
+        runner.loss_scale = self.loss_scaler.loss_scale
+        runner.meta = dict(runner.meta or {})
+        runner.meta["fp16"] = dict(runner.meta.get("fp16") or {}, loss_scaler=self.loss_scaler.state_dict())
+
+
+def parse_loss_scale(loss_scale):
+    """mmcv's Fp16OptimizerHook ``loss_scale`` -> LossScaler arguments.  A number is a static scale;
+    'dynamic' and dicts (dynamic scaling) are recognised and refused: not implemented."""
+    if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, str, dict)):
+        raise ValueError("loss_scale must be a number, 'dynamic' or a dict, got %r" % (loss_scale,))
+    if isinstance(loss_scale, (int, float)):
+        if not loss_scale > 0 or loss_scale != loss_scale or loss_scale == float("inf"):
+            raise ValueError("loss_scale must be a finite positive number, got %r" % (loss_scale,))
+        return dict(init_scale=float(loss_scale), mode="static")
+    if loss_scale == "dynamic" or isinstance(loss_scale, dict):
+        raise NotImplementedError("dynamic loss scaling (loss_scale=%r): only a static loss_scale "
+                                  "(a number) is implemented" % (loss_scale,))
+    raise ValueError("loss_scale must be a number, 'dynamic' or a dict, got %r" % (loss_scale,))
+
+
 class TextLoggerHook(Hook):
     def __init__(self, interval=50, by_epoch=False, logger=None, **unused):
         self.interval = interval
@@ -270,6 +318,8 @@ class TextLoggerHook(Hook):
         items = ", ".join("%s: %.4f" % (k, float(v)) for k, v in lv.items())
         dt = (time.time() - self._t0) / self.interval
         self._t0 = time.time()
+        if runner.train_precision != "fp32" or runner.loss_scale != 1.0:
+            items += ", loss_scale: %g" % runner.loss_scale
         msg = "Iter [%d/%d]\tlr: %.3e, arch: %s, time: %.3f, %s" % (
             runner.iter + 1, runner.max_iters, runner.lr, runner.arch_name, dt, items)
         if gdist.rank() == 0:
@@ -333,6 +383,12 @@ class IterBasedRunner:
         self.hyper = None              # device {lr, momentum, weight_decay, grad_scale} (graphs on)
         self.graph_stats = {"captured": 0, "replayed": 0, "eager": 0}
         self.sandwich = None           # (members, kd_cfg) of THIS iteration, set by SandwichHook
+        # fp16 training (Fp16ArenaOptimizerHook sets both; settable independently): the conv operand
+        # precision of every train_iter ('fp32' / 'fp16', ops.train_precision) and the static loss
+        # scale S that seeds backward (SGD divides it out: grad_scale)
+        self.train_precision = "fp32"
+        self.loss_scale = 1.0
+        self._loss_seeds = {}
         self.set_arch(None)
 
     def register_hook(self, hook):
@@ -447,7 +503,20 @@ class IterBasedRunner:
                 if not v.is_cuda:
                     return None
                 sig.append((k, tuple(v.shape), v.dtype))
-        return (self.arch_key, tuple(sig), self.model.training)
+        # (a step captured in fp32 must never be replayed in fp16, nor one scaled by another S)
+        return (self.arch_key, tuple(sig), self.model.training, self.train_precision, self.loss_scale)
+
+    def grad_scale(self):
+        """SGD's gradient scale: the all-reduce sums world_size ranks' gradients of the loss times S."""
+        return 1.0 / (gdist.world_size() * self.loss_scale)
+
+    def loss_seed(self, loss):
+        """The device scalar S that seeds backward (one per device: graph captures reuse it)."""
+        key = (loss.device, loss.dtype, self.loss_scale)
+        t = self._loss_seeds.get(key)
+        if t is None:
+            t = self._loss_seeds[key] = torch.full((), self.loss_scale, dtype=loss.dtype, device=loss.device)
+        return t
 
     def _write_hyper(self):
         """lr / momentum / weight decay / gradient scale of THIS step -> the device buffer."""
@@ -456,7 +525,7 @@ class IterBasedRunner:
         if self.hyper is None:
             self.hyper = torch.zeros(4, dtype=torch.float32, device=self.arena.flat_param.device)
         _lib.check(_lib.load().gs_sgd_set_hyper(self.hyper.data_ptr(), self.lr, self.momentum,
-                                                self.weight_decay, 1.0 / gdist.world_size(),
+                                                self.weight_decay, self.grad_scale(),
                                                 current_stream_ptr()), "gs_sgd_set_hyper")
 
     def _after_hooks(self, in_graph):
@@ -554,7 +623,11 @@ class IterBasedRunner:
 
     def train_iter(self, data_batch):
         self._enter_priority_stream()
-        return self._train_iter(data_batch)
+        if self.train_precision == "fp32":
+            return self._train_iter(data_batch)
+        from ..hip import ops
+        with ops.train_precision(self.train_precision):   # (fp32 again on return or raise)
+            return self._train_iter(data_batch)
 
     def _train_iter(self, data_batch):
         prof = self.host_prof
@@ -678,6 +751,8 @@ class IterBasedRunner:
         if "optimizer" in ck:
             self.arena.load_state_dict(ck["optimizer"], logger=self.logger)
         self.iter = ck.get("meta", {}).get("iter", 0)
+        if "fp16" in ck.get("meta", {}):   # the loss scaler's state (Fp16ArenaOptimizerHook.before_run)
+            self.meta = dict(self.meta or {}, fp16=ck["meta"]["fp16"])
 
     def load_checkpoint(self, checkpoint):
         from .checkpoint import load_checkpoint

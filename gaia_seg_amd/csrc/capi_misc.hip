@@ -43,8 +43,11 @@ long long g_splitk_combined = 0;
 int g_col_finalize = -1;
 long long g_col_finalized = 0;
 int g_fwd_precision = 0;
+int g_train_precision = 0;
 long long g_f16_launches = 0;
 double g_f16_flops = 0.0;
+long long g_f16_op_launches[2] = {};
+double g_f16_op_flops[2] = {};
 }
 
 extern "C" int gs_set_forward_precision(int32_t mode) {
@@ -54,12 +57,30 @@ extern "C" int gs_set_forward_precision(int32_t mode) {
 }
 extern "C" int32_t gs_get_forward_precision(void) { return gs::g_fwd_precision; }
 
+extern "C" int gs_set_train_precision(int32_t mode) {
+  if (mode != 0 && mode != 1) return GS_E_BADARG;
+  gs::g_train_precision = mode;
+  return GS_OK;
+}
+extern "C" int32_t gs_get_train_precision(void) { return gs::g_train_precision; }
+
 extern "C" int gs_debug_f16_launches(int64_t* n, double* flops, int32_t reset) {
   if (n) *n = __atomic_load_n(&gs::g_f16_launches, __ATOMIC_RELAXED);
   if (flops) *flops = gs::flops_load(&gs::g_f16_flops);
   if (reset) {
     __atomic_store_n(&gs::g_f16_launches, 0LL, __ATOMIC_RELAXED);
     gs::flops_store(&gs::g_f16_flops, 0.0);
+  }
+  return GS_OK;
+}
+extern "C" int gs_debug_f16_launches_by_op(int64_t* n, double* flops, int32_t reset) {
+  for (int o = 0; o < 2; ++o) {
+    if (n) n[o] = __atomic_load_n(&gs::g_f16_op_launches[o], __ATOMIC_RELAXED);
+    if (flops) flops[o] = gs::flops_load(&gs::g_f16_op_flops[o]);
+    if (reset) {
+      __atomic_store_n(&gs::g_f16_op_launches[o], 0LL, __ATOMIC_RELAXED);
+      gs::flops_store(&gs::g_f16_op_flops[o], 0.0);
+    }
   }
   return GS_OK;
 }

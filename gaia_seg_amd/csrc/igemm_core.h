@@ -1355,7 +1355,8 @@ __device__ __forceinline__ void x3_k_loop(int nk16, float* ldsf,
 }
 
 // ------------------------------------------------------------------------------------------
-// f16 forward K loop (gs_set_forward_precision(1): inference only).  x3_k_loop<BFWD> with ONE piece:
+// f16 K loop (forward: gs_set_forward_precision(1) or gs_set_train_precision(1); data gradient:
+// gs_set_train_precision(1)).  x3_k_loop with ONE piece (BFWD: x3_k_loop<true>, else <false>):
 // both operands are rounded once to fp16 at the stage store (round to nearest even: a plain
 // _Float16 conversion, v_cvt_f16_f32 -- not the round-toward-zero v_cvt_pkrtz) and contracted with
 // one v_mfma_f32_16x16x32_f16 per 16x16x32 of work, accumulating in fp32.  Same step (two 16-channel
@@ -1369,6 +1370,10 @@ __device__ __forceinline__ void x3_k_loop(int nk16, float* ldsf,
 // A stage is a third of the bf16x3 one (64 x 80 + BN x 80 bytes): kF16Stages = 2 stages (one
 // barrier per step) fit in 20 KB, so registers, not LDS, bound the workgroups per CU; kF16Sets = 2
 // register sets keep the global loads two steps ahead of the MFMAs.
+// !BFWD (data gradient): both operands are k-contiguous per row, so each thread
+// stores its eight values of (row t >> 2, chunk t & 3) -- both operands -- as ONE 16-byte chunk in
+// the plain x3_pack order [lo0..lo3, hi0..hi3]; any k order contracts correctly as long as A and B
+// share it.
 // ------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -1380,6 +1385,11 @@ __device__ __forceinline__ unsigned f16_pair(float lo, float hi) {
 __device__ __forceinline__ u32x4 f16_pack_il(const f32x4 lo4, const f32x4 hi4) {
   return u32x4{f16_pair(lo4[0], hi4[0]), f16_pair(lo4[1], hi4[1]), f16_pair(lo4[2], hi4[2]),
                f16_pair(lo4[3], hi4[3])};
+}
+// plain chunk [lo0, lo1, lo2, lo3, hi0, hi1, hi2, hi3] (the x3_pack order)
+__device__ __forceinline__ u32x4 f16_pack(const f32x4 lo4, const f32x4 hi4) {
+  return u32x4{f16_pair(lo4[0], lo4[1]), f16_pair(lo4[2], lo4[3]), f16_pair(hi4[0], hi4[1]),
+               f16_pair(hi4[2], hi4[3])};
 }
 
 #ifndef GS_F16_STAGES
@@ -1397,7 +1407,7 @@ struct F16Tile {
 };
 
 // AS: the register-set size of the loader (1, or 1 + 4 coefficient quads with AFF)
-template <int BM, int BN, int AS, bool AFF, class LA, class LB>
+template <int BM, int BN, int AS, bool AFF, bool BFWD = true, class LA, class LB>
 __device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
                                            f32x4 (&acc)[Tile<BM, BN>::TM][Tile<BM, BN>::TN],
                                            int wave, int lane, int t, int b_row, int b_kq,
@@ -1406,6 +1416,7 @@ __device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
   using X = F16Tile<BN>;
   using G = ColGroups<T::TN>;
   static_assert(BM == 64 && T::BV == 1 && AS == (AFF ? 5 : 1), "f16 loop: 64-row tiles, BN <= 64");
+  static_assert(BFWD || !AFF, "f16 loop: in_affine is a forward operand");
   unsigned char* lds = reinterpret_cast<unsigned char*>(ldsf);
   const int li = lane & 15, fk = lane >> 4;
   const int row = t >> 2, kq = t & 3;
@@ -1427,6 +1438,14 @@ __device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
     }
   };
   auto sstore = [&](int set, unsigned char* st) __attribute__((always_inline)) {
+    if constexpr (!BFWD) {
+      // data gradient: B's row b_row (= t >> 2), chunk b_kq (= t & 3), like A (see x3_k_loop<false>)
+      *reinterpret_cast<u32x4*>(st + row * X::ROWB + kq * 16) = f16_pack(act(a0[set]), act(a1[set]));
+      if (b_on)
+        *reinterpret_cast<u32x4*>(st + X::PA + b_row * X::ROWB + b_kq * 16) =
+            f16_pack(b0[set][0], b1[set][0]);
+      return;
+    }
     *reinterpret_cast<u32x4*>(st + row * X::ROWB + kq * 16) = f16_pack_il(act(a0[set]), act(a1[set]));
     if (b_on) {
       // column b_row + e, (step 1, step 2) of k row b_kq: one dword per column (see x3_k_loop<BFWD>)
@@ -1523,14 +1542,15 @@ __device__ __forceinline__ unsigned long long gs_stamp() {
 // split-K slabs (IgemmArgs::tickets) and / or merge their tile partials (col_tickets) themselves.
 // A variant of its own because that code's loads in flight cost registers the many-round launches
 // would pay for in occupancy.
-// F16: the forward on f16_k_loop (gs_set_forward_precision(1)); AFF allowed.
+// F16: f16_k_loop -- the forward (gs_set_forward_precision(1) or gs_set_train_precision(1); AFF
+// allowed) or the data gradient (gs_set_train_precision(1)).
 template <int BM, int BN, bool BTRANS, int KS, int ABL = 0, int ROLE = 0, bool PIPE = true,
           bool PAIR = false, bool AFF = false, bool X3 = false, bool SK = false, bool F16 = false>
 __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) {
   using T = Tile<BM, BN>;
   static_assert(!X3 || (PIPE && !PAIR && !AFF && ABL == 0 && BN <= 64), "bf16x3 loop: no loader fusion");
-  static_assert(!F16 || (PIPE && !PAIR && !X3 && !BTRANS && ABL == 0 && BM == 64 && BN <= 64),
-                "f16 loop: forward, 64-row tiles");
+  static_assert(!F16 || (PIPE && !PAIR && !X3 && ABL == 0 && BM == 64 && BN <= 64),
+                "f16 loop: 64-row tiles");
   constexpr int LDS_X3 = X3Tile<BN>::LDS_FLOATS > T::C_SZ + 512 ? X3Tile<BN>::LDS_FLOATS : T::C_SZ + 512;
   constexpr int LDS_F16 = F16Tile<BN>::LDS_FLOATS > T::C_SZ + 512 ? F16Tile<BN>::LDS_FLOATS : T::C_SZ + 512;
   constexpr int LDS_TILES = F16 ? LDS_F16 : (X3 ? LDS_X3 : (PAIR ? T::LDSF2 : T::LDSF));
@@ -1804,7 +1824,8 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
     };
     GS_STAMP(st_l0)
     if constexpr (F16)
-      f16_k_loop<BM, BN, AX, AFF>(nk, lds, acc, wave, lane, t, 4 * x3_nq, x3_kr, load_a, load_b);
+      f16_k_loop<BM, BN, AX, AFF, !BTRANS>(nk, lds, acc, wave, lane, t, BTRANS ? (t >> 2) : 4 * x3_nq,
+                                           BTRANS ? (t & 3) : x3_kr, load_a, load_b);
     else if constexpr (X3)
       x3_k_loop<BM, BN, AX, !BTRANS>(nk, lds, acc, wave, lane, t, BTRANS ? (t >> 2) : 4 * x3_nq,
                                      BTRANS ? (t & 3) : x3_kr, load_a, load_b);
@@ -2314,6 +2335,9 @@ extern double g_k3_flops[GS_KLOOP_COUNT];          // the same for the role-1 (b
 // FLOPs have counters of their own (gs_debug_f16_launches)
 extern long long g_f16_launches;
 extern double g_f16_flops;
+// the same split by op (gs_debug_f16_launches_by_op): [GS_OP_FORWARD], [GS_OP_DGRAD]
+extern long long g_f16_op_launches[2];
+extern double g_f16_op_flops[2];
 static inline void note_launch(int op, int kloop, const Plan& pl, bool aff, int bw_mode,
                                double flops = 0.0) {
   g_last_launch = gs_debug_launch{op, kloop, pl.bm, pl.bn, pl.splits, pl.nk_per_split, aff ? 1 : 0,
@@ -2321,6 +2345,10 @@ static inline void note_launch(int op, int kloop, const Plan& pl, bool aff, int 
   if (kloop == GS_KLOOP_F16) {
     flops_add(&g_f16_flops, flops);
     __atomic_fetch_add(&g_f16_launches, 1LL, __ATOMIC_RELAXED);
+    if (op == GS_OP_FORWARD || op == GS_OP_DGRAD) {
+      flops_add(&g_f16_op_flops[op], flops);
+      __atomic_fetch_add(&g_f16_op_launches[op], 1LL, __ATOMIC_RELAXED);
+    }
     return;
   }
   flops_add(&g_launch_flops[op][kloop], flops);
@@ -2512,16 +2540,36 @@ static inline bool x3_grid_ok(const Plan& pl, int min_ksteps_) {
          (pl.splits == 1 || pl.nk_per_split >= split_min) &&
          (long)pl.tiles_m * pl.tiles_n * pl.splits >= 2L * num_cu();
 }
-// Forward precision (gs_set_forward_precision): 0 = fp32 (default), 1 = fp16 operands.
-extern int g_fwd_precision;   // capi_misc.hip
-static inline bool f16_fwd_on() { return g_fwd_precision == 1; }
-// The f16 loop's tiles: 64 rows, BN 64 or 48 (plan_fwd narrows the planner's 80 / 32 to them).
+// Forward precision (gs_set_forward_precision, inference): 0 = fp32 (default), 1 = fp16 operands.
+// Training precision (gs_set_train_precision): 1 = the forward launches of the fp16 inference mode
+// AND the fast data-gradient launches contract fp16 operands; weight gradients stay fp32.
+extern int g_fwd_precision;     // capi_misc.hip
+extern int g_train_precision;   // capi_misc.hip
+static inline bool f16_train_on() { return g_train_precision == 1; }
+static inline bool f16_fwd_on() { return g_fwd_precision == 1 || f16_train_on(); }
+// The f16 loop's tiles: 64 rows, BN 64 or 48 (plan_fwd / f16_dgrad_plan narrow the planner's 80 / 32
+// to them).
 static inline bool f16_plan_ok(const Plan& pl) { return pl.bm == 64 && (pl.bn == 64 || pl.bn == 48); }
+// A fast data-gradient launch of this plan runs on the f16 loop in training fp16 mode: the tiles the
+// bf16x3 data-gradient gate admits, without its grid-size condition (as the f16 forward).
+// (profiles/r05_fp16_training.md: per shape class against the fp32 loops, kernels alone)
+static inline bool f16_dgrad_ok(const Plan& pl) { return f16_train_on() && f16_plan_ok(pl); }
+// training fp16 mode: a fast data-gradient plan of 64 x 80 / 64 x 32 tiles gets 64 / 48 columns, the
+// split-K factor (hence the workspace) unchanged -- what plan_fwd does for the forward
+static inline Plan f16_dgrad_plan(Plan pl, int Nn) {
+  if (f16_train_on() && pl.bm == 64 && (pl.bn == 80 || pl.bn == 32) && g_force_plan[0] == 0) {
+    pl.bn = pl.bn == 80 ? 64 : 48;
+    pl.tiles_n = (int)ceil_div(Nn, pl.bn);
+  }
+  return pl;
+}
 
 template <bool BTRANS>
 static inline int rows_fast_kloop(const Plan& pl, bool in_affine, int ks = 3) {
-  // fp16 mode: every fast forward launch on a 64-row tile, in_affine included
+  // fp16 mode: every fast forward launch on a 64-row tile, in_affine included;
+  // training fp16 mode: the fast data gradients as well (section 17)
   if (!BTRANS && f16_fwd_on() && f16_plan_ok(pl)) return GS_KLOOP_F16;
+  if (BTRANS && f16_dgrad_ok(pl)) return GS_KLOOP_F16;
   if constexpr (BTRANS) {
     static const int x3_min = env_int("GS_X3", 4);
     if (x3_grid_ok(pl, x3_min) && (pl.bn == 64 || pl.bn == 48)) return GS_KLOOP_BF16X3;
@@ -2592,28 +2640,27 @@ static void launch_rows_fast(const Plan& pl, const IgemmArgs& a_in, hipStream_t 
 #define GS_PLAIN(...) \
   launch_rows_kernel((igemm_rows_fast_kernel<__VA_ARGS__, false>), grid, block, lds_dyn, st, a, ev0, ev1)
   int lds_dyn = 0;
-  if constexpr (!BTRANS) {
-    if (kloop == GS_KLOOP_F16) {
-#define GS_F16L(BN_, AFF_)                                                                       \
-  do {                                                                                           \
-    if (a.tickets || a.col_tickets)                                                              \
-      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, false, KS, 0, ROLE, true, false, AFF_, \
+  if (kloop == GS_KLOOP_F16) {
+#define GS_F16L(BN_, AFF_)                                                                        \
+  do {                                                                                            \
+    if (a.tickets || a.col_tickets)                                                               \
+      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, BTRANS, KS, 0, ROLE, true, false, AFF_, \
                                                  false, true, true>), grid, block, 0, st, a, ev0, ev1);  \
-    else                                                                                         \
-      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, false, KS, 0, ROLE, true, false, AFF_, \
+    else                                                                                          \
+      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, BTRANS, KS, 0, ROLE, true, false, AFF_, \
                                                  false, false, true>), grid, block, 0, st, a, ev0, ev1); \
   } while (0)
+    if constexpr (!BTRANS) {
       if (a.a_coeffs) {
         if (pl.bn == 64) GS_F16L(64, true);
         else GS_F16L(48, true);
-      } else if (pl.bn == 64) {
-        GS_F16L(64, false);
-      } else {
-        GS_F16L(48, false);
+        return;
       }
-#undef GS_F16L
-      return;
     }
+    if (pl.bn == 64) GS_F16L(64, false);
+    else GS_F16L(48, false);
+#undef GS_F16L
+    return;
   }
   if (kloop == GS_KLOOP_BF16X3) {
     if constexpr (BTRANS) {
@@ -2762,8 +2809,15 @@ static Plan plan_fwd(const gs_conv_desc* d) {
   }
   return pl;
 }
+// (training fp16 mode: a stride-1 data gradient on the fast kernel gets f16_dgrad_plan's tiles; the
+// strided one narrows each parity class's plan the same way)
 static Plan plan_dgrad(const gs_conv_desc* d) {
-  return make_plan(d->N * d->H * d->W, d->Ci, d->KH * d->KW * d->Co, true);
+  const Plan pl = make_plan(d->N * d->H * d->W, d->Ci, d->KH * d->KW * d->Co, true);
+  if (!f16_train_on() || d->stride != 1 || getenv("GS_NO_FAST") != nullptr) return pl;
+  const int ks = (d->KH == 1 && d->KW == 1) ? 1 : ((d->KH == 3 && d->KW == 3) ? 3 : 0);
+  const size_t dy_b = (size_t)d->N * d->Ho * d->Wo * d->ldy * sizeof(float);
+  const size_t dense_b = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
+  return fast_rows_ok(d->Co, ks, dy_b, dense_b) ? f16_dgrad_plan(pl, d->Ci) : pl;
 }
 static Plan plan_wgrad(const gs_conv_desc* d) {
   // wgrad: K runs over pixels (up to 131072 at stage 1) while M x N is tiny: allow deep split-K

@@ -64,7 +64,7 @@ static int dgrad_strided_fast(const gs_conv_desc* d, const float* dy, const floa
       if (!th.n || !tw.n || !Hq || !Wq) continue;
       const long Mc = (long)d->N * Hq * Wq;
       const int ktot = th.n * tw.n * d->Co;
-      const Plan pl = make_plan((int)Mc, d->Ci, ktot, true);
+      const Plan pl = f16_dgrad_plan(make_plan((int)Mc, d->Ci, ktot, true), d->Ci);
       const size_t need = slab_bytes(pl, Mc, d->Ci);
       if (need > workspace_bytes || (need && !workspace)) return GS_E_WORKSPACE;
       IgemmArgs a{};

@@ -324,7 +324,7 @@ extern "C" int gs_debug_query_conv_launch(const gs_conv_desc* d, int32_t op, gs_
       const int s = d->stride;
       const TapAxis th = tap_axis(0, d->pad, d->dil, s, d->KH), tw = tap_axis(0, d->pad, d->dil, s, d->KW);
       const long Mc = (long)d->N * class_len(d->H, s, 0) * class_len(d->W, s, 0);
-      pl = make_plan((int)Mc, d->Ci, std::max(1, th.n * tw.n) * d->Co, true);
+      pl = f16_dgrad_plan(make_plan((int)Mc, d->Ci, std::max(1, th.n * tw.n) * d->Co, true), d->Ci);
       kloop = rows_fast_kloop<true>(pl, false);
     } else {
       pl = plan_dgrad(d);

@@ -57,11 +57,12 @@ class DebugLaunch(Structure):
 OP_FORWARD, OP_DGRAD, OP_WGRAD = 0, 1, 2
 KLOOP_GENERIC, KLOOP_FP32, KLOOP_FP32_PAIRS, KLOOP_BF16X3, KLOOP_STREAM = 0, 1, 2, 3, 4
 KLOOP_COUNT = 5
-# fp16 mode only (set_forward_precision(1)): not a slot of the count / FLOP tables, which keep
-# KLOOP_COUNT entries per op; gs_debug_f16_launches counts it
+# fp16 modes only (set_forward_precision(1), set_train_precision(1)): not a slot of the count / FLOP
+# tables, which keep KLOOP_COUNT entries per op; gs_debug_f16_launches(_by_op) counts it
 KLOOP_F16 = 5
-# gs_set_forward_precision modes.  FP16: the fast forward launches round both operands once to fp16
-# (round to nearest even, the input after its fp32 in_affine BN + ReLU) and accumulate in fp32 on
+# gs_set_forward_precision / gs_set_train_precision modes.  FP16: the fast forward launches (and, in
+# training mode, the fast data-gradient launches) round both operands once to fp16 (round to nearest
+# even, the input after its fp32 in_affine BN + ReLU) and accumulate in fp32 on
 # v_mfma_f32_16x16x32_f16; outputs, BN, residual and split-K stay fp32 (include/gaiaseg_hip.h).
 PRECISION_FP32, PRECISION_FP16 = 0, 1
 
@@ -188,6 +189,9 @@ PROTOTYPES = {
     "gs_debug_f16_launches": (_i32, [POINTER(_i64), POINTER(_f64), _i32]),
     "gs_set_forward_precision": (_i32, [_i32]),
     "gs_get_forward_precision": (_i32, []),
+    "gs_set_train_precision": (_i32, [_i32]),
+    "gs_get_train_precision": (_i32, []),
+    "gs_debug_f16_launches_by_op": (_i32, [POINTER(_i64), POINTER(_f64), _i32]),
     "gs_stream_fork": (_i32, [_P, _P]),
     "gs_conv_bn_workspace_bytes": (_sz, [_CD]),
     "gs_conv_bn_forward": (_i32, [_CD, _P, _P, _BN, _P, _i32, _P, _P, _P, _i32, _P, _sz, _P]),

@@ -596,6 +596,41 @@ class forward_precision:
         return False
 
 
+# ---- training precision ----------------------------------------------------------------------
+# gs_set_train_precision: 1 = the forward launches of the fp16 inference mode AND the fast
+# data-gradient launches contract fp16-rounded operands (weight gradients, BN, loss and SGD stay
+# fp32).  Separate from the inference switch: FORWARD_PRECISION and
+# gs_get_forward_precision() keep reading fp32 while training runs in fp16.  As for the forward
+# switch, neither workspace sizes nor the conv_bn plan cache depend on it.
+def set_train_precision(mode):
+    """Set the library's training precision ('fp32' / 'fp16'); returns the previous name."""
+    if mode not in _PRECISIONS:
+        raise ValueError("train precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
+    L = _L()
+    prev = "fp16" if L.gs_get_train_precision() == _lib.PRECISION_FP16 else "fp32"
+    _lib.check(L.gs_set_train_precision(_PRECISIONS[mode]), "gs_set_train_precision")
+    return prev
+
+
+class train_precision:
+    """``with train_precision("fp16"): ...`` -- training steps with fp16 conv operands (forward and
+    data gradient); the previous precision is restored on exit, exceptions included."""
+
+    def __init__(self, mode):
+        if mode not in _PRECISIONS:
+            raise ValueError("train precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
+        self.mode = mode
+        self._prev = None
+
+    def __enter__(self):
+        self._prev = set_train_precision(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        set_train_precision(self._prev)
+        return False
+
+
 def _check_precision(tape):
     if FORWARD_PRECISION != _lib.PRECISION_FP32 and tape.enabled:
         raise RuntimeError("fp16 forward precision is inference only: a conv was called with a "

@@ -582,6 +582,23 @@ int gs_seg_augment(const gs_augment_desc* d, const uint8_t* img, const uint8_t* 
 /* ------------------------------------------------------------------------------------------ */
 int gs_set_forward_precision(int32_t mode);
 int32_t gs_get_forward_precision(void);
+/* ------------------------------------------------------------------------------------------ */
+/* Training precision of the convolutions (fp16 mixed-precision training, separate from the    */
+/* inference switch above, which it neither reads nor changes).                                */
+/*   0 = fp32 (default): every launch as documented above.                                     */
+/*   1 = fp16 operands: every forward launch that forward precision 1 puts on GS_KLOOP_F16      */
+/*       (in_affine included) AND every data-gradient launch of gs_conv2d_dgrad /               */
+/*       gs_conv_bn_backward that takes the fast row kernel with a 64-row tile -- stride 1 and    */
+/*       the parity classes of a strided one; columns narrowed to 64 / 48 where the planner chose */
+/*       80 / 32, split-K factor and workspace unchanged -- contract on GS_KLOOP_F16: dy and W    */
+/*       rounded once to fp16 (round to nearest even), fp32 accumulation; the fused              */
+/*       BatchNorm-backward epilogue and the split-K combine stay fp32.  The stem, the 1x1        */
+/*       streaming kernel (forward and data gradient), the generic kernels and every weight-     */
+/*       gradient launch keep their fp32 paths.                                                  */
+/* Process-global.  gs_set_train_precision returns GS_E_BADARG for any other mode.              */
+/* ------------------------------------------------------------------------------------------ */
+int gs_set_train_precision(int32_t mode);
+int32_t gs_get_train_precision(void);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Tuning hook (tools/sweep_conv_plans.py): force tile rows (64|128), tile columns            */
@@ -669,9 +686,12 @@ int gs_debug_k3_flops(double* flops, int32_t reset);
 /* Launches on GS_KLOOP_F16 since the last reset (*n) and their algorithmic FLOPs (*flops, 2 * M * N * K);
  * either pointer may be NULL, reset != 0 clears both after reading. */
 int gs_debug_f16_launches(int64_t* n, double* flops, int32_t reset);
+/* The same split by op: n[GS_OP_FORWARD], n[GS_OP_DGRAD] and flops[...] (2 entries each; either
+ * pointer may be NULL), reset != 0 clears these two pairs after reading (not gs_debug_f16_launches'). */
+int gs_debug_f16_launches_by_op(int64_t* n, double* flops, int32_t reset);
 /* What gs_conv2d_forward / _dgrad / _wgrad (op = GS_OP_*) WOULD launch for this descriptor: host
- * arithmetic only, no GPU needed (honours gs_debug_force_plan, the GS_X3 switches and
- * gs_set_forward_precision).  For a strided
+ * arithmetic only, no GPU needed (honours gs_debug_force_plan, the GS_X3 switches,
+ * gs_set_forward_precision and gs_set_train_precision).  For a strided
  * dgrad it describes the parity class (0, 0). */
 int gs_debug_query_conv_launch(const gs_conv_desc* d, int32_t op, gs_debug_launch* out);
 
