@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ..core import dist as gdist
+from ..core.optimizer import build_param_groups
 from ..core.param_arena import ParamArena
 from ..core.runner import (ArenaOptimizerHook, CheckpointHook, FixedLrUpdaterHook,
                            Fp16ArenaOptimizerHook, IterBasedRunner, ManipulateArchHook,
@@ -112,9 +113,10 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
     gdist.sync_module_states(model, arena)   # the DDP wrap-time broadcast (:88-96)
     reducer = gdist.GradReducer(arena.flat_grad, arena.segments,
                                 bucket_bytes=cfg.get("bucket_bytes", 64 << 20))
+    # optimizer keys the arena SGD does not implement are errors, and paramwise_cfg becomes parameter
+    # groups (core/optimizer.py; None = the one-group path)
+    param_groups = build_param_groups(model, cfg.optimizer)
     opt = dict(cfg.optimizer)
-    if opt.pop("type", "SGD") != "SGD":
-        raise NotImplementedError("only SGD (the in-tree config) has a fused arena kernel")
     lr = opt["lr"]
     lr_scaler = cfg.get("lr_scaler")      # gaiaseg/apis/train.py:103-113
     if lr_scaler is not None:
@@ -126,7 +128,7 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
     runner = IterBasedRunner(model, arena, reducer, base_lr=lr, momentum=opt.get("momentum", 0.0),
                              weight_decay=opt.get("weight_decay", 0.0),
                              max_iters=cfg.runner["max_iters"], work_dir=cfg.get("work_dir"),
-                             logger=logger, meta=meta)
+                             logger=logger, meta=meta, param_groups=param_groups)
     if cfg.get("use_distillation", False):
         # the sandwich iteration takes the place of the one-subnet draw (core/runner.py SandwichHook);
         # train_sampler is the concat of sandwich_train_sampler(cfg)
@@ -136,7 +138,9 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
         runner.register_hook(ManipulateArchHook(train_sampler))
     lrc = dict(cfg.get("lr_config") or dict(policy="fixed"))
     policy = lrc.pop("policy", "fixed")
-    runner.register_hook(PolyLrUpdaterHook(**lrc) if policy == "poly" else FixedLrUpdaterHook())
+    if policy not in ("poly", "fixed"):
+        raise NotImplementedError("lr_config.policy=%r: only 'poly' and 'fixed'" % (policy,))
+    runner.register_hook(PolyLrUpdaterHook(**lrc) if policy == "poly" else FixedLrUpdaterHook(**lrc))
     runner.register_hook(opt_hook)
     ck = cfg.get("checkpoint_config")
     if ck:

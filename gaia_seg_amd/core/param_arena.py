@@ -73,6 +73,71 @@ class ParamArena:
         # gradient accumulation buffer of the sandwich iterations (core/runner.py), allocated at
         # first use; zero outside a running iteration
         self.flat_acc = None
+        # parameter groups (set_param_groups): None = the ungrouped gs_sgd_step path
+        self.groups = None
+        self.group_epoch = 0          # counts set_param_groups calls (part of the step-graph key)
+        self.group_hyper = None       # device {momentum, grad_scale, n_groups, 0, lr_0, wd_0, ...}
+        self._group_hyper_vals = None
+        self._tables = None           # optimizer.ChunkTableCache of the current grouping
+        # while a list: every device tensor a gs_sgd_step_groups launch names is appended (the runner
+        # sets it around a graph capture and keeps the list with the graph)
+        self.capture_refs = None
+
+    # ---- parameter groups (paramwise_cfg, core/optimizer.py) ----
+    def set_param_groups(self, group_of_param, n_groups=1, chunk_floats=None):
+        """``group_of_param``: {parameter name: group index} over the trainable parameters (None
+        switches grouping off).  From here on sgd_step takes one lr / weight decay PER GROUP and makes
+        ONE gs_sgd_step_groups launch over a chunk table, whatever the number of fragments.
+        Calling it again starts a new grouping: ``group_epoch`` moves on, so step graphs captured
+        under the earlier one are never replayed (runner._graph_key); they keep their own tables."""
+        from . import optimizer as _opt
+        self.group_epoch += 1
+        self._group_hyper_vals = None
+        self._tables = None
+        if group_of_param is None:
+            self.groups = None
+            return
+        if not 1 <= n_groups <= _lib.SGD_MAX_GROUPS:
+            raise ValueError("n_groups must be in [1, %d], got %d" % (_lib.SGD_MAX_GROUPS, n_groups))
+        unknown = set(group_of_param) - {name for name, *_ in self._layout}
+        if unknown:
+            raise KeyError("set_param_groups: no such parameters %s" % sorted(unknown)[:3])
+        if any(not 0 <= g < n_groups for g in group_of_param.values()):
+            raise ValueError("set_param_groups: group index outside [0, %d)" % n_groups)
+        self.groups = n_groups
+        self._tables = _opt.ChunkTableCache(
+            _opt.segment_groups(self._layout, group_of_param, _ALIGN), chunk_floats or _opt.CHUNK_FLOATS,
+            upload=lambda tab: torch.from_numpy(tab).to(self.device), numel=self.numel)
+        # a fresh table per grouping: a graph of an earlier grouping keeps (and reads) its own
+        self.group_hyper = torch.zeros(4 + 2 * _lib.SGD_MAX_GROUPS, dtype=torch.float32, device=self.device)
+
+    def chunk_table(self, ranges):
+        """(device table, chunks, fragments) of ``ranges`` under the current grouping, built once per
+        set of ranges (a host walk and one upload: never inside a graph capture -- the runner
+        prepares the tables of a subnet in refresh_active)."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        try:
+            return self._tables.get(ranges, build=not capturing)
+        except KeyError:
+            raise RuntimeError("the chunk table of these ranges was not prepared before the capture") from None
+
+    def write_group_hyper(self, lrs, weight_decays, momentum, grad_scale):
+        """{momentum, grad_scale, n_groups, 0, lr_0, wd_0, ...} -> the device table in stream order
+        (one tiny launch; skipped while the table already holds exactly these values)."""
+        vals = (tuple(float(x) for x in lrs), tuple(float(x) for x in weight_decays),
+                float(momentum), float(grad_scale))
+        if len(vals[0]) != self.groups or len(vals[1]) != self.groups:
+            raise ValueError("%d parameter groups need %d learning rates and weight decays, got %d / %d"
+                             % (self.groups, self.groups, len(vals[0]), len(vals[1])))
+        if vals == self._group_hyper_vals:
+            return
+        g = _lib.SgdGroups()
+        for i, (lr, wd) in enumerate(zip(vals[0], vals[1])):
+            g.lr_wd[2 * i], g.lr_wd[2 * i + 1] = lr, wd
+        _lib.check(_lib.load().gs_sgd_set_group_hyper(self.group_hyper.data_ptr(), vals[2], vals[3],
+                                                      self.groups, g, current_stream_ptr()),
+                   "gs_sgd_set_group_hyper")
+        self._group_hyper_vals = vals
 
     @staticmethod
     def _view(flat, p, phys, off, n):
@@ -121,10 +186,28 @@ class ParamArena:
                  hyper=None):
         """torch.optim.SGD(momentum, weight_decay, dampening=0, nesterov=False) on the ranges.
         ``hyper``: device tensor {lr, momentum, weight_decay, grad_scale} read by the kernel at run
-        time instead of the by-value arguments (step graphs, core/runner.py)."""
+        time instead of the by-value arguments (step graphs, core/runner.py).
+        With parameter groups set, ``lr`` and ``weight_decay`` are sequences (one value per group) and
+        the whole step is ONE gs_sgd_step_groups launch over the chunk table of ``ranges``; a non-None
+        ``hyper`` then means the caller has written the group table itself (write_group_hyper, outside
+        the captured graph)."""
         L = _lib.load()
         st = current_stream_ptr()
         pb, gb, mb = self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.flat_mom.data_ptr()
+        if self.groups is not None:
+            table, n_chunks, _ = self.chunk_table(ranges)
+            if n_chunks == 0:
+                return
+            if hyper is None:
+                self.write_group_hyper(lr, weight_decay, momentum, grad_scale)
+            elif self._group_hyper_vals is None:
+                raise RuntimeError("sgd_step(hyper=...) with parameter groups before write_group_hyper")
+            if self.capture_refs is not None:
+                self.capture_refs += [table, self.group_hyper]
+            _lib.check(L.gs_sgd_step_groups(pb, gb, mb, table.data_ptr(), n_chunks,
+                                            self.group_hyper.data_ptr(), 1 if zero_grad else 0, st),
+                       "gs_sgd_step_groups")
+            return
         if hyper is not None:
             hp = hyper.data_ptr()
             for a, b in ranges:

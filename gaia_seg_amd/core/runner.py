@@ -129,25 +129,75 @@ class SandwichHook(Hook):
         self.history.append([m.get("name", "random") for m in members])
 
 
-class PolyLrUpdaterHook(Hook):
-    def __init__(self, power=1.0, min_lr=0.0, by_epoch=False, **unused):
-        self.power, self.min_lr = power, min_lr
+class LrUpdaterHook(Hook):
+    """mmcv's LrUpdaterHook for iteration-based runs: before every iteration ``runner.lr`` becomes the
+    policy's regular lr, warmed up while ``iter < warmup_iters`` (``warmup`` = 'constant': lr * ratio;
+    'linear': lr * (1 - (1 - iter / warmup_iters) * (1 - ratio)); 'exp': lr * ratio ** (1 - iter /
+    warmup_iters); mmcv's defaults None / 0 / 0.1).  On a runner with parameter groups every group is
+    scheduled from ITS OWN initial lr (``runner.group_base_lr`` -> ``runner.group_lr``), as mmcv
+    does, and ``runner.lr`` is group 0's.  Epoch-based warm-up and unknown keys are refused."""
+
+    def __init__(self, by_epoch=False, warmup=None, warmup_iters=0, warmup_ratio=0.1,
+                 warmup_by_epoch=False, **unknown):
+        if unknown:
+            raise KeyError("lr_config: unknown keys %s" % sorted(unknown))
+        if warmup_by_epoch:
+            raise NotImplementedError("lr_config.warmup_by_epoch=True: only warm-up by iteration")
+        if warmup is not None:
+            if warmup not in ("constant", "linear", "exp"):
+                raise ValueError("lr_config.warmup=%r: must be 'constant', 'linear' or 'exp'" % (warmup,))
+            if not warmup_iters > 0:
+                raise ValueError("lr_config.warmup_iters must be positive with a warm-up, got %r"
+                                 % (warmup_iters,))
+            if not 0 < warmup_ratio <= 1.0:
+                raise ValueError("lr_config.warmup_ratio must be in (0, 1], got %r" % (warmup_ratio,))
+        self.warmup, self.warmup_iters, self.warmup_ratio = warmup, warmup_iters, warmup_ratio
         self.base_lr = None
 
     def before_run(self, runner):
         self.base_lr = runner.base_lr
 
+    def regular_lr(self, runner, base_lr):
+        return base_lr
+
+    def warmup_lr(self, cur_iter, lr):
+        if self.warmup is None or cur_iter >= self.warmup_iters:
+            return lr
+        if self.warmup == "constant":
+            return lr * self.warmup_ratio
+        if self.warmup == "linear":
+            return lr * (1 - (1 - cur_iter / self.warmup_iters) * (1 - self.warmup_ratio))
+        return lr * self.warmup_ratio ** (1 - cur_iter / self.warmup_iters)
+
     def get_lr(self, runner):
+        return self.regular_lr(runner, self.base_lr)
+
+    def before_train_iter(self, runner):
+        runner.lr = self.warmup_lr(runner.iter, self.get_lr(runner))
+        bases = getattr(runner, "group_base_lr", None)
+        if bases is not None:
+            runner.group_lr = [self.warmup_lr(runner.iter, self.regular_lr(runner, b)) for b in bases]
+            runner.lr = runner.group_lr[0]
+
+
+class PolyLrUpdaterHook(LrUpdaterHook):
+    def __init__(self, power=1.0, min_lr=0.0, **kwargs):
+        super().__init__(**kwargs)
+        self.power, self.min_lr = power, min_lr
+
+    def regular_lr(self, runner, base_lr):
         coeff = (1 - runner.iter / runner.max_iters) ** self.power
-        return (self.base_lr - self.min_lr) * coeff + self.min_lr
-
-    def before_train_iter(self, runner):
-        runner.lr = self.get_lr(runner)
+        return (base_lr - self.min_lr) * coeff + self.min_lr
 
 
-class FixedLrUpdaterHook(Hook):
-    def before_train_iter(self, runner):
-        runner.lr = runner.base_lr
+class FixedLrUpdaterHook(LrUpdaterHook):
+    # (reads runner.base_lr at every iteration and needs no before_run: tools and tests register this
+    # hook and call train_iter without call_hook("before_run"), which has always worked)
+    def before_run(self, runner):
+        pass
+
+    def get_lr(self, runner):
+        return runner.base_lr
 
 
 def _ranges_subtract(a, b):
@@ -241,15 +291,15 @@ class ArenaOptimizerHook(Hook):
             # it: update those parameters while the stem / stage-1 weight gradients still run
             for ev in ck:
                 torch.cuda.current_stream().wait_event(ev)
-            runner.arena.sgd_step(early, runner.lr, runner.momentum, runner.weight_decay, scale, True,
+            runner.arena.sgd_step(early, runner.opt_lr, runner.momentum, runner.opt_wd, scale, True,
                                   hyper=runner.hyper)
             ops.join_side_streams()
-            runner.arena.sgd_step(late, runner.lr, runner.momentum, runner.weight_decay, scale, True,
+            runner.arena.sgd_step(late, runner.opt_lr, runner.momentum, runner.opt_wd, scale, True,
                                   hyper=runner.hyper)
         else:
             ops.join_side_streams()
-            runner.arena.sgd_step(runner.active_ranges, runner.lr, runner.momentum,
-                                  runner.weight_decay, scale, True, hyper=runner.hyper)
+            runner.arena.sgd_step(runner.active_ranges, runner.opt_lr, runner.momentum,
+                                  runner.opt_wd, scale, True, hyper=runner.hyper)
         # the step cleared exactly the ranges backward wrote: the next zero_grad has nothing to do
         runner.arena.grads_clean = True
         runner.mark("step_end")
@@ -340,20 +390,33 @@ class CheckpointHook(Hook):
 
 
 class _StepGraph:
-    __slots__ = ("graph", "static", "outputs", "counters")
+    """``keep``: device tensors whose addresses the captured launches carry and that nothing else is
+    sure to keep alive for as long as the graph (the chunk tables and the hyper table of a grouped SGD
+    step: the arena's table cache may evict them)."""
+    __slots__ = ("graph", "static", "outputs", "counters", "keep")
 
-    def __init__(self, graph, static, outputs, counters):
+    def __init__(self, graph, static, outputs, counters, keep=()):
         self.graph, self.static, self.outputs, self.counters = graph, static, outputs, counters
+        self.keep = list(keep)
 
 
 class IterBasedRunner:
     """``run(data_loaders, workflow)`` drives ``model.train_step`` for ``max_iters`` iterations."""
 
     def __init__(self, model, arena, reducer, base_lr=0.01, momentum=0.9, weight_decay=5e-4,
-                 max_iters=80000, work_dir=None, logger=None, meta=None):
+                 max_iters=80000, work_dir=None, logger=None, meta=None, param_groups=None):
         self.model, self.arena, self.reducer = model, arena, reducer
         self.base_lr = self.lr = base_lr
         self.momentum, self.weight_decay = momentum, weight_decay
+        # parameter groups (core/optimizer.py build_param_groups; None = one lr / weight decay):
+        # group_lr follows the schedule (LrUpdaterHook), group_wd is fixed here
+        self.param_groups = param_groups
+        self.group_base_lr = self.group_lr = self.group_wd = None
+        if param_groups is not None:
+            arena.set_param_groups(param_groups.index, len(param_groups))
+            self.group_base_lr = param_groups.lrs(base_lr)
+            self.group_lr = list(self.group_base_lr)
+            self.group_wd = param_groups.weight_decays(weight_decay)
         self.max_iters = max_iters
         self.work_dir, self.logger, self.meta = work_dir, logger, meta
         self.iter = 0
@@ -457,6 +520,19 @@ class IterBasedRunner:
                 self._active_cache[key] = hit
         self.active_params, self.trainable_params = hit
         self.active_ranges = self.arena.ranges_for(self.trainable_params, key)
+        if self.arena.groups is not None:
+            # chunk tables are built and uploaded here, never inside a graph capture
+            for r in (self.active_ranges,) + tuple(self.split_ranges()):
+                self.arena.chunk_table(r)
+
+    # what the optimizer hooks hand to arena.sgd_step: one value, or one per parameter group
+    @property
+    def opt_lr(self):
+        return self.lr if self.group_lr is None else self.group_lr
+
+    @property
+    def opt_wd(self):
+        return self.weight_decay if self.group_wd is None else self.group_wd
 
     def split_ranges(self):
         """(early, late) parts of active_ranges: `late` covers the parameters whose weight gradients
@@ -504,7 +580,10 @@ class IterBasedRunner:
                     return None
                 sig.append((k, tuple(v.shape), v.dtype))
         # (a step captured in fp32 must never be replayed in fp16, nor one scaled by another S)
-        return (self.arch_key, tuple(sig), self.model.training, self.train_precision, self.loss_scale)
+        # (nor a step captured under another grouping: the arena counts its set_param_groups calls)
+        grouping = None if self.arena.groups is None else (self.arena.group_epoch, self.arena.groups)
+        return (self.arch_key, tuple(sig), self.model.training, grouping, self.train_precision,
+                self.loss_scale)
 
     def grad_scale(self):
         """SGD's gradient scale: the all-reduce sums world_size ranks' gradients of the loss times S."""
@@ -527,6 +606,8 @@ class IterBasedRunner:
         _lib.check(_lib.load().gs_sgd_set_hyper(self.hyper.data_ptr(), self.lr, self.momentum,
                                                 self.weight_decay, self.grad_scale(),
                                                 current_stream_ptr()), "gs_sgd_set_hyper")
+        if self.group_lr is not None:
+            self.arena.write_group_hyper(self.group_lr, self.group_wd, self.momentum, self.grad_scale())
 
     def _after_hooks(self, in_graph):
         for h in self.hooks:
@@ -541,14 +622,16 @@ class IterBasedRunner:
         ops.reserve_workspaces(dev)   # no workspace may be (re)allocated inside the capture
         graph = torch.cuda.CUDAGraph()
         runtime.CAPTURE_LOG = []
+        self.arena.capture_refs = []   # (the graph entry owns the tables its SGD launches name)
         try:
             with torch.cuda.graph(graph):
                 self.outputs = self.model.train_step(static, None)
                 self._after_hooks(True)
-            counters = runtime.CAPTURE_LOG
+            counters, keep = runtime.CAPTURE_LOG, self.arena.capture_refs
         finally:
             runtime.CAPTURE_LOG = None
-        entry = _StepGraph(graph, static, self.outputs, counters)
+            self.arena.capture_refs = None
+        entry = _StepGraph(graph, static, self.outputs, counters, keep)
         self._graphs[key] = entry
         while len(self._graphs) > self.max_graphs:
             self._graphs.popitem(last=False)
@@ -722,7 +805,7 @@ class IterBasedRunner:
                 log_vars["%s.%s" % (name, k)] = v
         self.arena.accumulate(union, into="grad")
         self.arena.grads_clean = False
-        self.arena.sgd_step(union, self.lr, self.momentum, self.weight_decay,
+        self.arena.sgd_step(union, self.opt_lr, self.momentum, self.opt_wd,
                             1.0 / gdist.world_size(), True)
         self.arena.grads_clean = True
         self.arch_name = "sandwich"

@@ -349,6 +349,20 @@ __global__ __launch_bounds__(256) void scale_nc_kernel(const float* x, int ldx,
 // HYPER: lr / momentum / weight decay / gradient scale are read from device memory at run time
 // (`hyper` = {lr, momentum, wd, gscale}), so that a captured hipGraph of the whole training step can
 // be replayed under a learning-rate schedule without re-capturing.
+// The update of four elements: the ONE expression both SGD kernels evaluate, so that a parameter
+// group with multipliers (1, 1) gets bit for bit what sgd_kernel gives it.
+template <bool ZERO>
+__device__ __forceinline__ void sgd_update4(float* __restrict__ p, float* __restrict__ g,
+                                            float* __restrict__ m, long i, float lr, float momentum,
+                                            float wd, float gscale) {
+  f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+  f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale + pv * wd;
+  f32x4 mv = reinterpret_cast<f32x4*>(m)[i] * momentum + gv;
+  reinterpret_cast<f32x4*>(m)[i] = mv;
+  reinterpret_cast<f32x4*>(p)[i] = pv - mv * lr;
+  if (ZERO) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 template <bool ZERO, bool HYPER>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* __restrict__ g,
                                                   float* __restrict__ m, long n4, float lr,
@@ -356,13 +370,34 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
                                                   const float* __restrict__ hyper) {
   if (HYPER) { lr = hyper[0]; momentum = hyper[1]; wd = hyper[2]; gscale = hyper[3]; }
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (long)gridDim.x * blockDim.x) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale + pv * wd;
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i] * momentum + gv;
-    reinterpret_cast<f32x4*>(m)[i] = mv;
-    reinterpret_cast<f32x4*>(p)[i] = pv - mv * lr;
-    if (ZERO) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+       i += (long)gridDim.x * blockDim.x)
+    sgd_update4<ZERO>(p, g, m, i, lr, momentum, wd, gscale);
+}
+
+// The same step over a TABLE of chunks with per-group lr / weight decay (paramwise_cfg: BatchNorm
+// parameters as a group of their own cut the forward-order arena into 84-294 fragments per anchor
+// of the in-tree supernets; one launch covers them all).
+// chunk = {begin, length, group} in float4 units relative to the arena bases; every chunk lies
+// inside one fragment of one group.  One workgroup per chunk (grid-stride over the table): the entry
+// is uniform over the workgroup.  hyper = {momentum, gscale, n_groups, 0, lr_0, wd_0, lr_1, wd_1, ..}
+// in device memory, so the launch carries no step-dependent argument (step graphs).  Elements
+// outside the table are never read or written; an entry naming a group the hyper table does not
+// have is skipped.
+template <bool ZERO>
+__global__ __launch_bounds__(256) void sgd_groups_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                         float* __restrict__ m,
+                                                         const GsSgdChunk* __restrict__ chunks,
+                                                         int n_chunks,
+                                                         const float* __restrict__ hyper) {
+  const float momentum = hyper[0], gscale = hyper[1];
+  const int n_groups = (int)hyper[2];
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const GsSgdChunk ch = chunks[c];
+    if ((unsigned)ch.group >= (unsigned)n_groups || ch.begin < 0) continue;
+    const float lr = hyper[4 + 2 * ch.group], wd = hyper[5 + 2 * ch.group];
+    const long end = (long)ch.begin + ch.length;
+    for (long i = (long)ch.begin + threadIdx.x; i < end; i += blockDim.x)
+      sgd_update4<ZERO>(p, g, m, i, lr, momentum, wd, gscale);
   }
 }
 
@@ -709,5 +744,41 @@ extern "C" int gs_sgd_step_hyper(float* param, float* grad, float* momentum_buf,
     hipLaunchKernelGGL((sgd_kernel<false, true>), dim3(stream_grid(n >> 2, 256)), dim3(256), 0,
                        as_stream(stream), param, grad, momentum_buf, (long)(n >> 2), 0.f, 0.f, 0.f,
                        0.f, hyper);
+  return launch_status();
+}
+
+__global__ void set_group_hyper_kernel(float* hyper, float momentum, float gscale, int n_groups,
+                                       GsSgdGroups v) {
+  const int t = threadIdx.x;
+  if (t == 0) { hyper[0] = momentum; hyper[1] = gscale; hyper[2] = (float)n_groups; hyper[3] = 0.f; }
+  if (t < 2 * GS_SGD_MAX_GROUPS) hyper[4 + t] = t < 2 * n_groups ? v.lr_wd[t] : 0.f;
+}
+
+extern "C" int gs_sgd_set_group_hyper(float* hyper, float momentum, float grad_scale,
+                                      int32_t n_groups, GsSgdGroups lr_wd, void* stream) {
+  if (!hyper) return GS_E_NULL;
+  if (n_groups < 1 || n_groups > GS_SGD_MAX_GROUPS) return GS_E_BADARG;
+  if (!aligned16(hyper)) return GS_E_ALIGN;
+  hipLaunchKernelGGL(set_group_hyper_kernel, dim3(1), dim3(64), 0, as_stream(stream), hyper,
+                     momentum, grad_scale, (int)n_groups, lr_wd);
+  return launch_status();
+}
+
+extern "C" int gs_sgd_step_groups(float* param, float* grad, float* momentum_buf,
+                                  const GsSgdChunk* chunks, int32_t n_chunks, const float* hyper,
+                                  int32_t zero_grad, void* stream) {
+  if (!param || !grad || !momentum_buf || !chunks || !hyper) return GS_E_NULL;
+  if (n_chunks <= 0) return GS_E_BADARG;
+  if (!aligned16(param) || !aligned16(grad) || !aligned16(momentum_buf) || !aligned16(chunks) ||
+      !aligned16(hyper))
+    return GS_E_ALIGN;
+  // a fixed number of workgroups (8 per CU), fewer only when the table is shorter
+  const int grid = (int)std::min<int64_t>(n_chunks, (int64_t)num_cu() * 8);
+  if (zero_grad)
+    hipLaunchKernelGGL((sgd_groups_kernel<true>), dim3(grid), dim3(256), 0, as_stream(stream), param,
+                       grad, momentum_buf, chunks, (int)n_chunks, hyper);
+  else
+    hipLaunchKernelGGL((sgd_groups_kernel<false>), dim3(grid), dim3(256), 0, as_stream(stream), param,
+                       grad, momentum_buf, chunks, (int)n_chunks, hyper);
   return launch_status();
 }

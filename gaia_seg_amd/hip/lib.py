@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class HipLibraryError(RuntimeError):
@@ -100,6 +100,19 @@ class AugmentDesc(Structure):
                  ("std", c_float * 3), ("pad_val", c_float), ("seg_pad_val", c_int32)])
 
 
+SGD_MAX_GROUPS = 16   # GS_SGD_MAX_GROUPS
+
+
+class SgdGroups(Structure):
+    """Mirror of ``GsSgdGroups`` (passed by value)."""
+    _fields_ = [("lr_wd", c_float * (2 * SGD_MAX_GROUPS))]
+
+
+class SgdChunk(Structure):
+    """Mirror of ``GsSgdChunk``: {begin, length, group, reserved} in units of 4 floats."""
+    _fields_ = [(k, c_int32) for k in ("begin", "length", "group", "reserved")]
+
+
 _P = c_void_p  # device pointers and the stream travel as plain addresses
 _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
 _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
@@ -170,6 +183,8 @@ PROTOTYPES = {
     "gs_sgd_step": (_i32, [_P, _P, _P, _i64, _f32, _f32, _f32, _f32, _i32, _P]),
     "gs_sgd_step_hyper": (_i32, [_P, _P, _P, _i64, _P, _i32, _P]),
     "gs_sgd_set_hyper": (_i32, [_P, _f32, _f32, _f32, _f32, _P]),
+    "gs_sgd_set_group_hyper": (_i32, [_P, _f32, _f32, _i32, SgdGroups, _P]),
+    "gs_sgd_step_groups": (_i32, [_P, _P, _P, _P, _i32, _P, _i32, _P]),
     "gs_grad_accumulate": (_i32, [_P, _P, _i64, _P]),
     "gs_debug_force_plan": (_i32, [_i32, _i32, _i32]),
     "gs_debug_query_plan": (_i32, [_i32, _i32, _i32, _i32, POINTER(_i32), POINTER(_i32), POINTER(_i32),

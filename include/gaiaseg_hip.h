@@ -527,6 +527,38 @@ int gs_sgd_set_hyper(float* hyper, float lr, float momentum, float weight_decay,
                      void* stream);
 int gs_sgd_step_hyper(float* param, float* grad, float* momentum_buf, int64_t n, const float* hyper,
                       int32_t zero_grad, void* stream);
+/* Parameter groups (paramwise_cfg: per-group lr / weight decay, core/optimizer.py).  BatchNorm
+ * parameters sit between the conv weights of the forward-order arena, so a grouping cuts a subnet's
+ * few merged ranges into many fragments (84-294 for the anchors of the in-tree supernets when norm
+ * parameters are a group of their own); ONE launch walks a table of chunks instead.
+ *   chunk = {begin, length, group} in units of 4 floats, relative to the three arena bases; every
+ *           chunk lies inside one fragment of one group (the host cuts fragments into chunks of at
+ *           most a few thousand floats and uploads the table once per set of ranges).  16 bytes per
+ *           entry, table 16-byte aligned; begin >= 0, length >= 0, 0 <= group < n_groups (an entry
+ *           that breaks this is skipped, not followed).
+ *   hyper = {momentum, grad_scale, n_groups, 0, lr_0, wd_0, lr_1, wd_1, ...}: 4 + 2 *
+ *           GS_SGD_MAX_GROUPS floats of device memory, 16-byte aligned, written by
+ *           gs_sgd_set_group_hyper in stream order (values travel as kernel arguments, as in
+ *           gs_sgd_set_hyper).  gs_sgd_step_groups carries no step-dependent argument, so a captured
+ *           step graph replays under a changing per-group schedule.
+ * The per-element update is gs_sgd_step's own expression: a group whose lr / wd equal the by-value
+ * arguments of gs_sgd_step gets bit-identical results.  Elements outside the table are never
+ * touched in param, grad or momentum_buf.  GS_E_NULL / GS_E_BADARG (n_chunks <= 0, n_groups outside
+ * [1, GS_SGD_MAX_GROUPS]) / GS_E_ALIGN before any launch. */
+#define GS_SGD_MAX_GROUPS 16
+typedef struct GsSgdGroups {
+  float lr_wd[2 * GS_SGD_MAX_GROUPS]; /* {lr_0, wd_0, lr_1, wd_1, ...}; entries >= n_groups ignored */
+} GsSgdGroups;
+typedef struct GsSgdChunk {
+  int32_t begin;    /* first float4 of the chunk */
+  int32_t length;   /* float4s in the chunk */
+  int32_t group;    /* index into the hyper table */
+  int32_t reserved; /* 0 */
+} GsSgdChunk;
+int gs_sgd_set_group_hyper(float* hyper, float momentum, float grad_scale, int32_t n_groups,
+                           GsSgdGroups lr_wd, void* stream);
+int gs_sgd_step_groups(float* param, float* grad, float* momentum_buf, const GsSgdChunk* chunks,
+                       int32_t n_chunks, const float* hyper, int32_t zero_grad, void* stream);
 /* Gradient accumulation of a sandwich iteration (one SGD step over several subnets, US-Nets): the
  * weight-gradient kernels overwrite their gradient, so each member's gradients are moved into an
  * accumulation arena:  dst[i] += src[i]; src[i] = 0  for i in [0, n).  One launch per range; float4
