@@ -20,6 +20,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdio>
+#include <type_traits>
 #include <unordered_map>
 #include <hip/hip_ext.h>
 #include "common.h"
@@ -915,42 +916,6 @@ __device__ __forceinline__ void rows_epilogue(
   }
 }
 
-
-// Progress priority (experiment, GS_PRIO > 0): a wave lowers its issue priority as it advances through
-// its K range, so that the co-resident workgroups of a CU -- which the arbiter otherwise serves
-// oldest-first, finishing them one after the other and leaving the CU under-occupied for the last
-// third of a single-round launch -- advance together.  `done` of `total` loop units.
-#ifndef GS_PRIO
-#define GS_PRIO 0
-#endif
-__device__ __forceinline__ void progress_prio(int done, int total) {
-#if GS_PRIO == 1
-  const int q = total >> 2;
-  if (done >= 3 * q) __builtin_amdgcn_s_setprio(0);
-  else if (done >= 2 * q) __builtin_amdgcn_s_setprio(1);
-  else if (done >= q) __builtin_amdgcn_s_setprio(2);
-  else __builtin_amdgcn_s_setprio(3);
-#elif GS_PRIO == 2   // finer towards the end: 50 %, 75 %, 90 %
-  if (10 * done >= 9 * total) __builtin_amdgcn_s_setprio(0);
-  else if (4 * done >= 3 * total) __builtin_amdgcn_s_setprio(1);
-  else if (2 * done >= total) __builtin_amdgcn_s_setprio(2);
-  else __builtin_amdgcn_s_setprio(3);
-#elif GS_PRIO == 3   // inverted (control): priority rises with progress
-  const int q = total >> 2;
-  if (done >= 3 * q) __builtin_amdgcn_s_setprio(3);
-  else if (done >= 2 * q) __builtin_amdgcn_s_setprio(2);
-  else if (done >= q) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);
-#else
-  (void)done; (void)total;
-#endif
-}
-__device__ __forceinline__ void progress_prio_end() {
-#if GS_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
-}
-
 // ------------------------------------------------------------------------------------------
 // Software-pipelined K loop shared by the fast row and wgrad kernels.
 // One wave can run only ONE MFMA ahead of its instruction stream, so everything else a K step
@@ -1027,7 +992,6 @@ __device__ __forceinline__ void pipelined_k_loop(int nk, float* lds,
   read_b(buf0, 0, fb[0]);
   int ib = 0;
   for (; ib + 6 <= nk; ib += 6) {   // unconditional body (see pipelined_k_loop_pairs)
-    progress_prio(ib, nk);
     phase(ra0, rb0, ra1, rb1, buf0, buf1);
     phase(ra1, rb1, ra2, rb2, buf1, buf0);
     phase(ra2, rb2, ra0, rb0, buf0, buf1);
@@ -1040,7 +1004,6 @@ __device__ __forceinline__ void pipelined_k_loop(int nk, float* lds,
   if (ib + 2 < nk) phase(ra2, rb2, ra0, rb0, buf0, buf1);
   if (ib + 3 < nk) phase(ra0, rb0, ra1, rb1, buf1, buf0);
   if (ib + 4 < nk) phase(ra1, rb1, ra2, rb2, buf0, buf1);
-  progress_prio_end();
 }
 
 
@@ -1126,18 +1089,17 @@ __device__ __forceinline__ void pipelined_k_loop_pairs(
   // drain, r01 ISA; the odd pair is peeled off instead)
   int pp = 0;
   for (; pp + 1 < npairs; pp += 2) {
-    progress_prio(pp, npairs);
     // pair in A, next pair (held in sets 2,3) -> B, refill sets 0,1
     phase(ra0, rb0, ra1, rb1, ra2, rb2, ra3, rb3, A0, A1, B0, B1);
     // pair in B, next pair (sets 0,1) -> A, refill sets 2,3
     phase(ra2, rb2, ra3, rb3, ra0, rb0, ra1, rb1, B0, B1, A0, A1);
   }
   if (pp < npairs) phase(ra0, rb0, ra1, rb1, ra2, rb2, ra3, rb3, A0, A1, B0, B1);
-  progress_prio_end();
 }
 
 // ------------------------------------------------------------------------------------------
-// bf16x3 K loop (stride-1 data gradient by default, GS_X3=<min K steps>, 0 = off): the fp32 contraction as SIX bf16 MFMAs over an
+// bf16x3 contraction (packed_k_loop<PackBf16x3>; stride-1 data gradient by default,
+// GS_X3=<min K steps>, 0 = off): the fp32 contraction as SIX bf16 MFMAs over an
 // exact three-way bf16 split of both operands (x = x0 + x1 + x2 with 8 mantissa bits each; products
 // a_i * b_j for i + j <= 2, smallest first, fp32 accumulation in v_mfma_f32_16x16x32_bf16): as
 // accurate as the fp32 MFMA against fp64 (profiles/r02_bf16x3_probe.md) at 6 x 16 instead of
@@ -1145,9 +1107,9 @@ __device__ __forceinline__ void pipelined_k_loop_pairs(
 // thread that stages (row, kq) holds channels 4kq..4kq+3 of both: its 8 values are one 16-byte bf16
 // chunk per piece; any k order works as long as both operands use it).  Operands are split ONCE,
 // at the stage store; LDS holds [piece][row][32 bf16 + 16 B pad] (80-byte rows: conflict-free
-// 16-byte fragment reads).  Both operands must be k-contiguous per row: dgrad (BTRANS) only.
-// Global loads run kX3Sets = 2 steps ahead of the MFMAs (two register sets); the split + stage store
-// of step i+1 follows the MFMAs of step i into the SAME single LDS stage (kX3Stages = 1: one barrier
+// 16-byte fragment reads).
+// Global loads run two steps ahead of the MFMAs (two register sets); the split + stage store
+// of step i+1 follows the MFMAs of step i into the SAME single LDS stage (one barrier
 // before the store frees the stage, one after publishes it) -- 112 VGPRs and 31 KB of LDS, i.e. four
 // workgroups per CU, which is where the loop's speed comes from.
 // Non-finite operands: x3_split turns +-Inf into (Inf, NaN, NaN) pieces (Inf - Inf), so an output
@@ -1191,189 +1153,17 @@ __device__ __forceinline__ void x3_split_il(const f32x4 lo4, const f32x4 hi4, u3
   p2 = x3_pack_il(__builtin_bit_cast(u32x4, r2l), __builtin_bit_cast(u32x4, r2h));
 }
 
-// one LDS stage (two barriers per step, three workgroups per CU by registers) or two (one barrier,
-// two workgroups per CU by LDS)
-constexpr int kX3Stages = 1;
-// Product terms a_i * b_j kept per element pair: 6 = all with i + j <= 2 (drops a1 b2 + a2 b1, each
-// 2^-24 of |a||b| -- the size of one fp32 rounding -- and a2 b2); 8 = those two as well, leaving only
-// a2 b2 (2^-32).  Measured (r03): 8 terms cost 9 % (stage-1 3x3 dgrad 47.6 -> 52.4 us) and do NOT
-// lower the loop's noise -- with the forward on x3 the conditioned-gradient error ratios of the
-// full-size parity tests were 1.53 / 3 outliers with 6 terms and 1.59 / 1.61 with 8 -- so the extra
-// noise over the fp32 MFMA's exact fmaf chain is the bf16 MFMA's internal 32-term accumulation, not
-// the dropped cross terms.  6 it is.
-#ifndef GS_X3_TERMS
-#define GS_X3_TERMS 6
-#endif
-constexpr int kX3Terms = GS_X3_TERMS;
-constexpr int kX3Sets = 2;     // register sets = how many steps the global loads run ahead
-
-template <int BN>
-struct X3Tile {
-  static constexpr int ROWB = 80;
-  static constexpr int PA = 64 * ROWB, PB = BN * ROWB;
-  static constexpr int STAGE = 3 * PA + 3 * PB;            // bytes
-  static constexpr int LDS_FLOATS = kX3Stages * STAGE / 4;
-};
-
-// BFWD (forward): B arrives as one k ROW of the [k][n] weights per thread and step -- four columns
-// (b_row .. b_row + 3) of k row b_kq (0..15) -- and both operands use the interleaved chunk order;
-// the pair (step 1 value, step 2 value) of a column is one 32-bit LDS store per piece.
-template <int BM, int BN, int AS, bool BFWD = false, class LA, class LB>
-__device__ __forceinline__ void x3_k_loop(int nk16, float* ldsf,
-                                          f32x4 (&acc)[Tile<BM, BN>::TM][Tile<BM, BN>::TN],
-                                          int wave, int lane, int t, int b_row, int b_kq,
-                                          LA&& load_a, LB&& load_b) {
-  using T = Tile<BM, BN>;
-  using X = X3Tile<BN>;
-  using G = ColGroups<T::TN>;
-  static_assert(BM == 64 && AS == 1 && T::BV == 1, "bf16x3 loop: 64-row tiles, BN <= 64");
-  unsigned char* lds = reinterpret_cast<unsigned char*>(ldsf);
-  const int li = lane & 15, fk = lane >> 4;
-  const int row = t >> 2, kq = t & 3;
-  // the thread's B staging slot: column b_row of the tile, k chunk b_kq (dgrad: (t >> 2, t & 3)
-  // like A; forward: (t & 63, t >> 6), see the kernel's load_b)
-  const bool b_on = b_row < BN;
-  // register sets: step k lives in set k % kX3Sets
-  f32x4 a0[kX3Sets][AS], a1[kX3Sets][AS], b0[kX3Sets][T::BV], b1[kX3Sets][T::BV];
-  auto gload = [&](int set) __attribute__((always_inline)) {
-    load_a(a0[set]); load_b(b0[set]);     // (load_b advances the K state)
-    load_a(a1[set]); load_b(b1[set]);
-  };
-  auto sstore = [&](int set, unsigned char* st) __attribute__((always_inline)) {
-    u32x4 p0, p1, p2;
-    if constexpr (BFWD) x3_split_il(a0[set][0], a1[set][0], p0, p1, p2);
-    else x3_split(a0[set][0], a1[set][0], p0, p1, p2);
-    unsigned char* pa = st + row * X::ROWB + kq * 16;
-    *reinterpret_cast<u32x4*>(pa) = p0;
-    *reinterpret_cast<u32x4*>(pa + X::PA) = p1;
-    *reinterpret_cast<u32x4*>(pa + 2 * X::PA) = p2;
-    if constexpr (BFWD) {
-      if (b_on) {
-        // element e of the thread's row pair = column b_row + e: (step 1, step 2) as one dword at
-        // chunk b_kq >> 2, pair slot b_kq & 3 of that column's row
-        x3_split_il(b0[set][0], b1[set][0], p0, p1, p2);
-        unsigned char* pb = st + 3 * X::PA + b_row * X::ROWB + (b_kq >> 2) * 16 + (b_kq & 3) * 4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          *reinterpret_cast<unsigned*>(pb + e * X::ROWB) = p0[e];
-          *reinterpret_cast<unsigned*>(pb + e * X::ROWB + X::PB) = p1[e];
-          *reinterpret_cast<unsigned*>(pb + e * X::ROWB + 2 * X::PB) = p2[e];
-        }
-      }
-    } else if (b_on) {
-      x3_split(b0[set][0], b1[set][0], p0, p1, p2);
-      unsigned char* pb = st + 3 * X::PA + b_row * X::ROWB + b_kq * 16;
-      *reinterpret_cast<u32x4*>(pb) = p0;
-      *reinterpret_cast<u32x4*>(pb + X::PB) = p1;
-      *reinterpret_cast<u32x4*>(pb + 2 * X::PB) = p2;
-    }
-  };
-  constexpr bool QUAD = BN == 64;   // 2 x 2 waves of 32 x 32: each wave re-reads half of B, not all
-  // B fragment row of MFMA block j for this lane: the column the epilogue expects there
-  int brow[T::TN];
-#pragma unroll
-  for (int j = 0; j < T::TN; ++j) brow[j] = G::base(j) + G::width(j) * li + (j - G::first(j));
-  auto compute = [&](const unsigned char* cb) __attribute__((always_inline)) {
-    if constexpr (QUAD) {
-      bf16x8 qa[2][3], qb[2][3];
-      const int ar = (wave >> 1) * 32 + li, bc = (wave & 1) * 32 + li;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-          qa[h][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
-              cb + p * X::PA + (ar + h * 16) * X::ROWB + fk * 16));
-          qb[h][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
-              cb + 3 * X::PA + p * X::PB + (bc + h * 16) * X::ROWB + fk * 16));
-        }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i2 = q >> 1, j2 = q & 1;
-        if constexpr (kX3Terms == 8) {   // the 2^-24-level cross terms (see kX3Terms)
-          acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][2], qb[j2][1], acc[0][q], 0, 0, 0);
-          acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][1], qb[j2][2], acc[0][q], 0, 0, 0);
-        }
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][2], qb[j2][0], acc[0][q], 0, 0, 0);
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][1], qb[j2][1], acc[0][q], 0, 0, 0);
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][0], qb[j2][2], acc[0][q], 0, 0, 0);
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][1], qb[j2][0], acc[0][q], 0, 0, 0);
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][0], qb[j2][1], acc[0][q], 0, 0, 0);
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[i2][0], qb[j2][0], acc[0][q], 0, 0, 0);
-      }
-      return;
-    }
-    bf16x8 fa[3], fb[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-      fa[p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
-          cb + p * X::PA + (wave * 16 + li) * X::ROWB + fk * 16));
-#pragma unroll
-    for (int j = 0; j < T::TN; ++j) {
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-        fb[p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
-            cb + 3 * X::PA + p * X::PB + brow[j] * X::ROWB + fk * 16));
-      if constexpr (kX3Terms == 8) {
-        acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[1], acc[0][j], 0, 0, 0);
-        acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[2], acc[0][j], 0, 0, 0);
-      }
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2], fb[0], acc[0][j], 0, 0, 0);
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[1], acc[0][j], 0, 0, 0);
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[2], acc[0][j], 0, 0, 0);
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[1], fb[0], acc[0][j], 0, 0, 0);
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[1], acc[0][j], 0, 0, 0);
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0], fb[0], acc[0][j], 0, 0, 0);
-    }
-  };
-  const int nst = (nk16 + 1) >> 1;
-  if (nst <= 0) return;
-  unsigned char* buf0 = lds;
-  unsigned char* buf1 = kX3Stages == 2 ? lds + X::STAGE : lds;
-  // (loads past the K range return zeros: the loaders' kvalid test, so the prologue needs no guard)
-#pragma unroll
-  for (int u = 0; u < kX3Sets; ++u) gload(u);
-  sstore(0, buf0);
-  __syncthreads();
-  // phase i (set = i % kX3Sets): compute step i from cur, refill its set with step i + kX3Sets,
-  // store step i + 1 (the next set, loaded kX3Sets - 1 phases ago) into the (other) stage
-#define GS_X3_PHASE(I, CUR, NXT)                                  \
-  if (s + (I) < nst) {                                             \
-    gload((I) % kX3Sets);                                          \
-    compute(CUR);                                                  \
-    if (kX3Stages == 1) __syncthreads();                           \
-    sstore(((I) + 1) % kX3Sets, NXT);                              \
-    __syncthreads();                                               \
-  }
-  static_assert(12 % kX3Sets == 0 && kX3Sets >= 2, "the phase loop is unrolled by 12");
-  for (int s = 0; s < nst; s += 12) {
-    GS_X3_PHASE(0, buf0, buf1) GS_X3_PHASE(1, buf1, buf0) GS_X3_PHASE(2, buf0, buf1)
-    GS_X3_PHASE(3, buf1, buf0) GS_X3_PHASE(4, buf0, buf1) GS_X3_PHASE(5, buf1, buf0)
-    GS_X3_PHASE(6, buf0, buf1) GS_X3_PHASE(7, buf1, buf0) GS_X3_PHASE(8, buf0, buf1)
-    GS_X3_PHASE(9, buf1, buf0) GS_X3_PHASE(10, buf0, buf1) GS_X3_PHASE(11, buf1, buf0)
-  }
-#undef GS_X3_PHASE
-}
-
 // ------------------------------------------------------------------------------------------
-// f16 K loop (forward: gs_set_forward_precision(1) or gs_set_train_precision(1); data gradient:
-// gs_set_train_precision(1)).  x3_k_loop with ONE piece (BFWD: x3_k_loop<true>, else <false>):
-// both operands are rounded once to fp16 at the stage store (round to nearest even: a plain
-// _Float16 conversion, v_cvt_f16_f32 -- not the round-toward-zero v_cvt_pkrtz) and contracted with
-// one v_mfma_f32_16x16x32_f16 per 16x16x32 of work, accumulating in fp32.  Same step (two 16-channel
-// K steps), same interleaved chunk order and the same 80-byte LDS rows as the bf16x3 forward: the
-// f16 MFMA's A / B lane maps are the bf16 ones (lane l holds A[l & 15][8 (l >> 4) + j] and
-// B[8 (l >> 4) + j][l & 15]; tests/test_fwd_f16_gpu.py checks them with exact integer data).
-// AFF (in_affine): the loader's register set carries the BatchNorm coefficients of its K step (see
-// igemm_rows_fast_kernel) and relu((x - mean) * scale + beta) is evaluated in fp32 here, before the
-// rounding, with the padding select applied to the activation -- the bottleneck convs that consume
-// a deferred BN + ReLU (ops.DEFER_EDGES) reach the loop without an activation pass through HBM.
-// A stage is a third of the bf16x3 one (64 x 80 + BN x 80 bytes): kF16Stages = 2 stages (one
-// barrier per step) fit in 20 KB, so registers, not LDS, bound the workgroups per CU; kF16Sets = 2
-// register sets keep the global loads two steps ahead of the MFMAs.
-// !BFWD (data gradient): both operands are k-contiguous per row, so each thread
-// stores its eight values of (row t >> 2, chunk t & 3) -- both operands -- as ONE 16-byte chunk in
-// the plain x3_pack order [lo0..lo3, hi0..hi3]; any k order contracts correctly as long as A and B
-// share it.
+// f16 contraction (forward: gs_set_forward_precision(1) or gs_set_train_precision(1); data gradient:
+// gs_set_train_precision(1)): the bf16x3 scheme with ONE piece.  Both operands are rounded once to
+// fp16 at the stage store (round to nearest even: a plain _Float16 conversion, v_cvt_f16_f32 -- not the
+// round-toward-zero v_cvt_pkrtz) and contracted with one v_mfma_f32_16x16x32_f16 per 16x16x32 of work,
+// accumulating in fp32.  Same step (two 16-channel K steps), same chunk orders and the same 80-byte
+// LDS rows as bf16x3: the f16 MFMA's A / B lane maps are the bf16 ones (lane l holds
+// A[l & 15][8 (l >> 4) + j] and B[8 (l >> 4) + j][l & 15]; tests/test_fwd_f16_gpu.py checks them with
+// exact integer data).  A stage is a third of the bf16x3 one (64 x 80 + BN x 80 bytes): two stages (one
+// barrier per step) fit in 20 KB, so registers, not LDS, bound the workgroups per CU (DESIGN.md
+// sections 16 and 17).
 // ------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -1392,36 +1182,93 @@ __device__ __forceinline__ u32x4 f16_pack(const f32x4 lo4, const f32x4 hi4) {
                f16_pair(hi4[2], hi4[3])};
 }
 
-#ifndef GS_F16_STAGES
-#define GS_F16_STAGES 2
-#endif
-constexpr int kF16Stages = GS_F16_STAGES;
-constexpr int kF16Sets = 2;
+// ------------------------------------------------------------------------------------------
+// Precision policies of packed_k_loop: how many 16-bit pieces an fp32 operand becomes (PIECES), how
+// many LDS stages the loop keeps (STAGES: one = two barriers per step, two = one barrier), the split of
+// two K steps' quads into one 16-byte chunk per piece (IL: the interleaved order of the forward), and
+// the MFMA sequence of one fragment pair.
+// bf16x3: products a_i * b_j for i + j <= 2, smallest first -- SIX terms.  Keeping a1 b2 + a2 b1 as
+// well (8 terms; each is 2^-24 of |a||b|, the size of one fp32 rounding) was measured in r03: 9 % slower
+// (stage-1 3x3 dgrad 47.6 -> 52.4 us) and NOT less noisy -- the conditioned-gradient error ratios of the
+// full-size parity tests were 1.53 / 3 outliers with 6 terms and 1.59 / 1.61 with 8 -- so the extra noise
+// over the fp32 MFMA's exact fmaf chain is the bf16 MFMA's internal 32-term accumulation, not the
+// dropped cross terms.  One LDS stage: 31 KB and 112 VGPRs, four workgroups per CU (two stages: two).
+// ------------------------------------------------------------------------------------------
+struct PackBf16x3 {
+  static constexpr int PIECES = 3, STAGES = 1;
+  using frag = bf16x8;
+  template <bool IL>
+  static __device__ __forceinline__ void split(const f32x4 lo4, const f32x4 hi4, u32x4 (&p)[3]) {
+    if constexpr (IL) x3_split_il(lo4, hi4, p[0], p[1], p[2]);
+    else x3_split(lo4, hi4, p[0], p[1], p[2]);
+  }
+  static __device__ __forceinline__ f32x4 mfma(const frag (&a)[3], const frag (&b)[3], f32x4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
+    return c;
+  }
+};
+struct PackF16 {
+  static constexpr int PIECES = 1, STAGES = 2;
+  using frag = f16x8;
+  template <bool IL>
+  static __device__ __forceinline__ void split(const f32x4 lo4, const f32x4 hi4, u32x4 (&p)[1]) {
+    p[0] = IL ? f16_pack_il(lo4, hi4) : f16_pack(lo4, hi4);
+  }
+  static __device__ __forceinline__ f32x4 mfma(const frag (&a)[1], const frag (&b)[1], f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], c, 0, 0, 0);
+  }
+};
+// the policy of a packed K loop (GS_KLOOP_BF16X3 / GS_KLOOP_F16)
+template <int KLOOP>
+using PackPolicy = std::conditional_t<KLOOP == GS_KLOOP_F16, PackF16, PackBf16x3>;
 
-template <int BN>
-struct F16Tile {
+// LDS image of one stage: [piece][A rows | B rows][32 x 16 bit + 16 B pad]
+template <int BN, int PIECES, int STAGES>
+struct PackedTile {
   static constexpr int ROWB = 80;
   static constexpr int PA = 64 * ROWB, PB = BN * ROWB;
-  static constexpr int STAGE = PA + PB;                    // bytes
-  static constexpr int LDS_FLOATS = kF16Stages * STAGE / 4;
+  static constexpr int STAGE = PIECES * (PA + PB);          // bytes
+  static constexpr int LDS_FLOATS = STAGES * STAGE / 4;
 };
 
-// AS: the register-set size of the loader (1, or 1 + 4 coefficient quads with AFF)
-template <int BM, int BN, int AS, bool AFF, bool BFWD = true, class LA, class LB>
-__device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
-                                           f32x4 (&acc)[Tile<BM, BN>::TM][Tile<BM, BN>::TN],
-                                           int wave, int lane, int t, int b_row, int b_kq,
-                                           LA&& load_a, LB&& load_b) {
+// The packed 16-bit K loop of the fast row kernel (policy P: PackBf16x3 or PackF16).
+// BFWD (forward): B arrives as one k ROW of the [k][n] weights per thread and step -- four columns
+// (b_row .. b_row + 3) of k row b_kq (0..15) -- and both operands use the interleaved chunk order;
+// the pair (step 1 value, step 2 value) of a column is one 32-bit LDS store per piece.
+// !BFWD (data gradient): both operands are k-contiguous per row, so each thread stores its eight
+// values of (row t >> 2, chunk t & 3) -- both operands -- as ONE 16-byte chunk per piece in the plain
+// order [lo0..lo3, hi0..hi3]; any k order contracts correctly as long as A and B share it.
+// AFF (in_affine, forward): the loader's register set carries the BatchNorm coefficients of its K step
+// (see igemm_rows_fast_kernel; AS = 1 + 4 coefficient quads) and relu((x - mean) * scale + beta) is
+// evaluated in fp32 here, before the rounding, with the padding select applied to the activation -- the
+// bottleneck convs that consume a deferred BN + ReLU (ops.DEFER_EDGES) reach the loop without an
+// activation pass through HBM.
+template <class P, int BM, int BN, int AS, bool AFF, bool BFWD, class LA, class LB>
+__device__ __forceinline__ void packed_k_loop(int nk16, float* ldsf,
+                                              f32x4 (&acc)[Tile<BM, BN>::TM][Tile<BM, BN>::TN],
+                                              int wave, int lane, int t, int b_row, int b_kq,
+                                              LA&& load_a, LB&& load_b) {
   using T = Tile<BM, BN>;
-  using X = F16Tile<BN>;
+  using X = PackedTile<BN, P::PIECES, P::STAGES>;
   using G = ColGroups<T::TN>;
-  static_assert(BM == 64 && T::BV == 1 && AS == (AFF ? 5 : 1), "f16 loop: 64-row tiles, BN <= 64");
-  static_assert(BFWD || !AFF, "f16 loop: in_affine is a forward operand");
+  using F = typename P::frag;
+  constexpr int NP = P::PIECES;
+  constexpr int kSets = 2;     // register sets = how many steps the global loads run ahead
+  static_assert(BM == 64 && T::BV == 1 && AS == (AFF ? 5 : 1), "packed loop: 64-row tiles, BN <= 64");
+  static_assert(BFWD || !AFF, "packed loop: in_affine is a forward operand");
   unsigned char* lds = reinterpret_cast<unsigned char*>(ldsf);
   const int li = lane & 15, fk = lane >> 4;
   const int row = t >> 2, kq = t & 3;
+  // the thread's B staging slot: column b_row of the tile, k chunk b_kq (dgrad: (t >> 2, t & 3)
+  // like A; forward: (t & 63, t >> 6), see the kernel's load_b)
   const bool b_on = b_row < BN;
-  f32x4 a0[kF16Sets][AS], a1[kF16Sets][AS], b0[kF16Sets][1], b1[kF16Sets][1];
+  // register sets: step k lives in set k % kSets
+  f32x4 a0[kSets][AS], a1[kSets][AS], b0[kSets][T::BV], b1[kSets][T::BV];
   auto gload = [&](int set) __attribute__((always_inline)) {
     load_a(a0[set]); load_b(b0[set]);     // (load_b advances the K state)
     load_a(a1[set]); load_b(b1[set]);
@@ -1437,78 +1284,99 @@ __device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
       return ra[0];
     }
   };
+  // operands are split ONCE, here, at the stage store
   auto sstore = [&](int set, unsigned char* st) __attribute__((always_inline)) {
-    if constexpr (!BFWD) {
-      // data gradient: B's row b_row (= t >> 2), chunk b_kq (= t & 3), like A (see x3_k_loop<false>)
-      *reinterpret_cast<u32x4*>(st + row * X::ROWB + kq * 16) = f16_pack(act(a0[set]), act(a1[set]));
-      if (b_on)
-        *reinterpret_cast<u32x4*>(st + X::PA + b_row * X::ROWB + b_kq * 16) =
-            f16_pack(b0[set][0], b1[set][0]);
-      return;
-    }
-    *reinterpret_cast<u32x4*>(st + row * X::ROWB + kq * 16) = f16_pack_il(act(a0[set]), act(a1[set]));
-    if (b_on) {
-      // column b_row + e, (step 1, step 2) of k row b_kq: one dword per column (see x3_k_loop<BFWD>)
-      const u32x4 pk = f16_pack_il(b0[set][0], b1[set][0]);
-      unsigned char* pb = st + X::PA + b_row * X::ROWB + (b_kq >> 2) * 16 + (b_kq & 3) * 4;
+    u32x4 p[NP];
+    P::template split<BFWD>(act(a0[set]), act(a1[set]), p);
+    unsigned char* pa = st + row * X::ROWB + kq * 16;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) *reinterpret_cast<unsigned*>(pb + e * X::ROWB) = pk[e];
+    for (int i = 0; i < NP; ++i) *reinterpret_cast<u32x4*>(pa + i * X::PA) = p[i];
+    if (b_on) {
+      P::template split<BFWD>(b0[set][0], b1[set][0], p);
+      if constexpr (BFWD) {
+        // element e of the thread's row pair = column b_row + e: (step 1, step 2) as one dword at
+        // chunk b_kq >> 2, pair slot b_kq & 3 of that column's row
+        unsigned char* pb = st + NP * X::PA + b_row * X::ROWB + (b_kq >> 2) * 16 + (b_kq & 3) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int i = 0; i < NP; ++i)
+            *reinterpret_cast<unsigned*>(pb + e * X::ROWB + i * X::PB) = p[i][e];
+      } else {
+        unsigned char* pb = st + NP * X::PA + b_row * X::ROWB + b_kq * 16;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) *reinterpret_cast<u32x4*>(pb + i * X::PB) = p[i];
+      }
     }
   };
-  constexpr bool QUAD = BN == 64;   // 2 x 2 waves of 32 x 32 (the bf16x3 loop's layout)
+  constexpr bool QUAD = BN == 64;   // 2 x 2 waves of 32 x 32: each wave re-reads half of B, not all
+  // B fragment row of MFMA block j for this lane: the column the epilogue expects there
   int brow[T::TN];
 #pragma unroll
   for (int j = 0; j < T::TN; ++j) brow[j] = G::base(j) + G::width(j) * li + (j - G::first(j));
   auto compute = [&](const unsigned char* cb) __attribute__((always_inline)) {
     if constexpr (QUAD) {
-      f16x8 qa[2], qb[2];
+      F qa[2][NP], qb[2][NP];
       const int ar = (wave >> 1) * 32 + li, bc = (wave & 1) * 32 + li;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        qa[h] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
-            cb + (ar + h * 16) * X::ROWB + fk * 16));
-        qb[h] = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
-            cb + X::PA + (bc + h * 16) * X::ROWB + fk * 16));
-      }
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        acc[0][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qa[q >> 1], qb[q & 1], acc[0][q], 0, 0, 0);
+        for (int p = 0; p < NP; ++p) {
+          qa[h][p] = __builtin_bit_cast(F, *reinterpret_cast<const u32x4*>(
+              cb + p * X::PA + (ar + h * 16) * X::ROWB + fk * 16));
+          qb[h][p] = __builtin_bit_cast(F, *reinterpret_cast<const u32x4*>(
+              cb + NP * X::PA + p * X::PB + (bc + h * 16) * X::ROWB + fk * 16));
+        }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[0][q] = P::mfma(qa[q >> 1], qb[q & 1], acc[0][q]);
       return;
     }
-    const f16x8 fa = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
-        cb + (wave * 16 + li) * X::ROWB + fk * 16));
+    F fa[NP], fb[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+      fa[p] = __builtin_bit_cast(F, *reinterpret_cast<const u32x4*>(
+          cb + p * X::PA + (wave * 16 + li) * X::ROWB + fk * 16));
 #pragma unroll
     for (int j = 0; j < T::TN; ++j) {
-      const f16x8 fb = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(
-          cb + X::PA + brow[j] * X::ROWB + fk * 16));
-      acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, fb, acc[0][j], 0, 0, 0);
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+        fb[p] = __builtin_bit_cast(F, *reinterpret_cast<const u32x4*>(
+            cb + NP * X::PA + p * X::PB + brow[j] * X::ROWB + fk * 16));
+      acc[0][j] = P::mfma(fa, fb, acc[0][j]);
     }
   };
   const int nst = (nk16 + 1) >> 1;
   if (nst <= 0) return;
   unsigned char* buf0 = lds;
-  unsigned char* buf1 = kF16Stages == 2 ? lds + X::STAGE : lds;
-  // (loads past the K range return zeros -- and AFF zeroes their activation: no prologue guard)
+  unsigned char* buf1 = P::STAGES == 2 ? lds + X::STAGE : lds;
+  // (loads past the K range return zeros -- the loaders' kvalid test, and AFF zeroes their
+  // activation -- so the prologue needs no guard)
 #pragma unroll
-  for (int u = 0; u < kF16Sets; ++u) gload(u);
+  for (int u = 0; u < kSets; ++u) gload(u);
   sstore(0, buf0);
   __syncthreads();
-#define GS_F16_PHASE(I, CUR, NXT)                                 \
+  // phase i (set = i % kSets): compute step i from cur, refill its set with step i + kSets, store step
+  // i + 1 (the next set, loaded kSets - 1 phases ago) into the other stage -- or, with ONE stage, into
+  // the same one: a barrier before the store frees it, the one after publishes it
+  // (A macro, not an always_inline lambda as in pipelined_k_loop: with the lambda the kernels with
+  // 48-column tiles came out with the operands of one fragment-address add swapped -- harmless, but
+  // tools/compare_isa.py then no longer shows the code unchanged; profiles/r07_igemm_refactor_isa.md.)
+#define GS_PACKED_PHASE(I, CUR, NXT)                              \
   if (s + (I) < nst) {                                             \
-    gload((I) % kF16Sets);                                         \
+    gload((I) % kSets);                                            \
     compute(CUR);                                                  \
-    if (kF16Stages == 1) __syncthreads();                          \
-    sstore(((I) + 1) % kF16Sets, NXT);                             \
+    if (P::STAGES == 1) __syncthreads();                           \
+    sstore(((I) + 1) % kSets, NXT);                                \
     __syncthreads();                                               \
   }
-  static_assert(12 % kF16Sets == 0 && kF16Sets >= 2, "the phase loop is unrolled by 12");
+  static_assert(12 % kSets == 0 && kSets >= 2, "the phase loop is unrolled by 12");
   for (int s = 0; s < nst; s += 12) {
-    GS_F16_PHASE(0, buf0, buf1) GS_F16_PHASE(1, buf1, buf0) GS_F16_PHASE(2, buf0, buf1)
-    GS_F16_PHASE(3, buf1, buf0) GS_F16_PHASE(4, buf0, buf1) GS_F16_PHASE(5, buf1, buf0)
-    GS_F16_PHASE(6, buf0, buf1) GS_F16_PHASE(7, buf1, buf0) GS_F16_PHASE(8, buf0, buf1)
-    GS_F16_PHASE(9, buf1, buf0) GS_F16_PHASE(10, buf0, buf1) GS_F16_PHASE(11, buf1, buf0)
+    GS_PACKED_PHASE(0, buf0, buf1) GS_PACKED_PHASE(1, buf1, buf0) GS_PACKED_PHASE(2, buf0, buf1)
+    GS_PACKED_PHASE(3, buf1, buf0) GS_PACKED_PHASE(4, buf0, buf1) GS_PACKED_PHASE(5, buf1, buf0)
+    GS_PACKED_PHASE(6, buf0, buf1) GS_PACKED_PHASE(7, buf1, buf0) GS_PACKED_PHASE(8, buf0, buf1)
+    GS_PACKED_PHASE(9, buf1, buf0) GS_PACKED_PHASE(10, buf0, buf1) GS_PACKED_PHASE(11, buf1, buf0)
   }
-#undef GS_F16_PHASE
+#undef GS_PACKED_PHASE
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1522,17 +1390,32 @@ __device__ __forceinline__ void f16_k_loop(int nk16, float* ldsf,
 //  * global loads run THREE K steps ahead of the MFMAs (three register sets), because one K step of
 //    fp32 MFMA work (~1k cycles per wave) is shorter than the gather's memory latency.
 // ------------------------------------------------------------------------------------------
-// ABL > 0 are timing-only ablation builds used by scratch/kbench.hip (1: no global loads,
-// 2: + no LDS stores, 3: + no LDS reads); the library only instantiates ABL = 0.
-// ABL == 9 is a diagnostic build (scratch/kbench.hip): s_memtime stamps around the sections of
-// every phase, written per wave to p.slab as 8 x uint64.
+// TIMELINE is a diagnostic build (tools/probes/wg_timeline.hip): every wave writes 8 x uint64 to
+// p.slab -- [0] s_memrealtime at the start of the K loop, [1] s_memtime ticks inside it, [2] / [3]
+// s_memrealtime at entry / behind the epilogue, [7] HW_ID | XCC_ID -- and the result goes to p.out
+// unsplit.  The library only instantiates TIMELINE = false.
 __device__ __forceinline__ unsigned long long gs_stamp() {
   unsigned long long t;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
   return t;
 }
+// fast_tile_ok(KLOOP, AFF, BTRANS, BM, BN): the instantiations the fast row kernel admits -- the
+// launcher's dispatch_tile instantiates exactly these.
+//  * packed loops (bf16x3, f16): 64-row tiles of 64 or 48 columns;
+//  * AFF: forward only, 64-row tiles (the planner's), never on the bf16x3 loop.
+constexpr bool packed_kloop(int kloop) { return kloop == GS_KLOOP_BF16X3 || kloop == GS_KLOOP_F16; }
+constexpr bool packed_tile(int bm, int bn) { return bm == 64 && (bn == 64 || bn == 48); }
+constexpr bool in_affine_tile(int bm, int /*bn*/) { return bm == 64; }
+constexpr bool fast_tile_ok(int kloop, bool aff, bool btrans, int bm, int bn) {
+  return (kloop == GS_KLOOP_FP32 || kloop == GS_KLOOP_FP32_PAIRS || packed_kloop(kloop)) &&
+         (!packed_kloop(kloop) || packed_tile(bm, bn)) &&
+         (!aff || (!btrans && in_affine_tile(bm, bn) && kloop != GS_KLOOP_BF16X3));
+}
+// KS: compile-time kernel size (1 or 3); it only bounds the tap loop and tags the kernel name.
 // ROLE only names the instantiation (gs_conv_desc::role): role 1 = the bottleneck conv2 (K3), so
 // that rocprofv3 attributes the headline kernel separately from the other 3x3 convolutions.
+// KLOOP: the K loop (GS_KLOOP_FP32: pipelined_k_loop, GS_KLOOP_FP32_PAIRS: pipelined_k_loop_pairs,
+// GS_KLOOP_BF16X3 / GS_KLOOP_F16: packed_k_loop) -- the value gs_debug_launch reports.
 // AFF: the gathered operand is relu(bn(src)) (IgemmArgs::a_coeffs): the producer BatchNorm's
 // coefficients sit in LDS behind the tile stages; each register set of the pipelined loop carries,
 // besides its AS data quads, the three coefficient quads of its K step (fetched from LDS when the
@@ -1542,26 +1425,23 @@ __device__ __forceinline__ unsigned long long gs_stamp() {
 // split-K slabs (IgemmArgs::tickets) and / or merge their tile partials (col_tickets) themselves.
 // A variant of its own because that code's loads in flight cost registers the many-round launches
 // would pay for in occupancy.
-// F16: f16_k_loop -- the forward (gs_set_forward_precision(1) or gs_set_train_precision(1); AFF
-// allowed) or the data gradient (gs_set_train_precision(1)).
-template <int BM, int BN, bool BTRANS, int KS, int ABL = 0, int ROLE = 0, bool PIPE = true,
-          bool PAIR = false, bool AFF = false, bool X3 = false, bool SK = false, bool F16 = false>
+template <int BM, int BN, bool BTRANS, int KS, int ROLE, int KLOOP, bool AFF, bool SK,
+          bool TIMELINE = false>
 __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) {
   using T = Tile<BM, BN>;
-  static_assert(!X3 || (PIPE && !PAIR && !AFF && ABL == 0 && BN <= 64), "bf16x3 loop: no loader fusion");
-  static_assert(!F16 || (PIPE && !PAIR && !X3 && ABL == 0 && BM == 64 && BN <= 64),
-                "f16 loop: 64-row tiles");
-  constexpr int LDS_X3 = X3Tile<BN>::LDS_FLOATS > T::C_SZ + 512 ? X3Tile<BN>::LDS_FLOATS : T::C_SZ + 512;
-  constexpr int LDS_F16 = F16Tile<BN>::LDS_FLOATS > T::C_SZ + 512 ? F16Tile<BN>::LDS_FLOATS : T::C_SZ + 512;
-  constexpr int LDS_TILES = F16 ? LDS_F16 : (X3 ? LDS_X3 : (PAIR ? T::LDSF2 : T::LDSF));
+  static_assert(fast_tile_ok(KLOOP, AFF, BTRANS, BM, BN), "no such fast row kernel");
+  constexpr bool PACKED = packed_kloop(KLOOP);
+  using PK = PackPolicy<KLOOP>;
+  constexpr int LDS_PACKED = PackedTile<BN, PK::PIECES, PK::STAGES>::LDS_FLOATS > T::C_SZ + 512
+                                 ? PackedTile<BN, PK::PIECES, PK::STAGES>::LDS_FLOATS : T::C_SZ + 512;
+  constexpr int LDS_TILES = PACKED ? LDS_PACKED : (KLOOP == GS_KLOOP_FP32_PAIRS ? T::LDSF2 : T::LDSF);
   __shared__ __attribute__((aligned(16))) float lds[LDS_TILES + (AFF ? 3 * kAffMaxC : 0)];
   constexpr int AS = BM / 64;
-  constexpr int AX = AFF ? AS + 4 : AS;   // register-set size handed to the pipelined loop
-  static_assert(!AFF || (PIPE && !BTRANS && ABL == 0), "AFF: forward, pipelined loop only");
-  constexpr int MAXTAPS = KS * KS;  // KS only bounds the tap loop and tags the kernel name
+  constexpr int AX = AFF ? AS + 4 : AS;   // register-set size handed to the K loop
+  constexpr int MAXTAPS = KS * KS;
   const int ntaps = p.kh_n * p.kw_n;
   unsigned long long st_entry = 0;
-  if constexpr (ABL == 9) st_entry = __builtin_amdgcn_s_memrealtime();
+  if constexpr (TIMELINE) st_entry = __builtin_amdgcn_s_memrealtime();
   (void)st_entry;
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -1657,47 +1537,93 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
 #pragma unroll
     for (int j = 0; j < T::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto load = [&](f32x4 (&ra)[AS], f32x4 (&rb)[T::BV]) {
-    const bool kvalid = tap < ntaps;
-    const int kh = tap / p.kw_n, kw = tap - kh * p.kw_n;
-    const int aoff = 4 * (kh * p.step_h * (int)p.s_h + kw * p.step_w * (int)p.s_w + c0);
+  unsigned long long st_k0 = 0, st_l0 = 0, st_l1 = 0;
+  if constexpr (TIMELINE) st_k0 = __builtin_amdgcn_s_memrealtime();
+  // scalar K-step state of the NEXT stage to load (no divisions, no branches in the loop).
+  // (An incremental form with precomputed deltas saves ~10 SALU per K step but pushed the kernel
+  // past its SGPR budget: the buffer descriptors were spilled to VGPRs and every load became a
+  // waterfall loop.  The kernel sits at 103 SGPRs; keep the live scalar set small.)
+  const int a_step_h = 4 * p.step_h * (int)p.s_h, a_step_w = 4 * p.step_w * (int)p.s_w;
+  const int b_step_h = 4 * (int)p.d_tap_h, b_step_w = 4 * (int)p.d_tap_w;
+  const int b_cmul = BTRANS ? 4 : 4 * p.d_row;
+  int kh = tap / p.kw_n, kw = tap - kh * p.kw_n;
+  int aoff = kh * a_step_h + kw * a_step_w + 4 * c0;
+  int bbase = kh * b_step_h + kw * b_step_w + c0 * b_cmul;
+  unsigned tapbit = tap < 32 ? (1u << tap) : 0u;
+  int k_left = nk;
+  auto load_a = [&](f32x4 (&ra)[AX]) __attribute__((always_inline)) {
+    const bool kvalid = k_left > 0;
+    unsigned okbits = 0;
 #pragma unroll
     for (int s = 0; s < AS; ++s) {
-      const bool ok = kvalid && ((vmask[s] >> tap) & 1u);
+      const bool ok = kvalid && (vmask[s] & tapbit) != 0;
       const unsigned off = ok ? (unsigned)(rowoff[s] + aoff) : kOOB;
-      if constexpr (ABL >= 1 && ABL != 9) ra[s] = f32x4{(float)off, 1.f, 2.f, 3.f};
-      else
-        ra[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_src, off, 0, 0));
+      okbits |= (ok ? 1u : 0u) << s;
+      ra[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_src, off, 0, 0));
     }
-    const int bbase = 4 * (kh * (int)p.d_tap_h + kw * (int)p.d_tap_w + (BTRANS ? c0 : c0 * p.d_row));
+    if constexpr (AFF) {
+      const float* cp = coefL + c0 + kq * 4;   // channels of this K step handled by this thread
+      ra[AS] = *reinterpret_cast<const f32x4*>(cp);
+      ra[AS + 1] = *reinterpret_cast<const f32x4*>(cp + p.Cs);
+      ra[AS + 2] = *reinterpret_cast<const f32x4*>(cp + 2 * p.Cs);
+      ra[AS + 3][0] = __builtin_bit_cast(float, okbits);
+    }
+  };
+  // packed forward loops: thread (k row kr = lane & 15 of the 16-channel step, column quad
+  // nq = (lane >> 4) + 4 * wave) fetches ONE 16-byte quad of the [k][n] weights per step, like the
+  // fp32 loop (a wave reads 16 rows x 64 contiguous bytes).  The k rows run fastest over the lanes so
+  // that the 32-bit pair stores of packed_k_loop<BFWD> walk consecutive LDS banks.  (r02 fetched four
+  // consecutive k of one column as four dword loads per step: 4x the vector-memory instructions,
+  // level with the fp32 loop.)
+  const int x3_kr = lane & 15, x3_nq = (lane >> 4) + 4 * wave;
+  const int x3_col = n0 + 4 * x3_nq;
+  const bool x3_bok = 4 * x3_nq < BN && x3_col < p.n_lim;
+  const int x3_boff = 4 * (x3_kr * p.d_row + x3_col);
+  auto load_b = [&](f32x4 (&rb)[T::BV]) __attribute__((always_inline)) {
+    const bool kvalid = k_left > 0;
+    if constexpr (PACKED && !BTRANS) {
+      const unsigned off = (x3_bok && kvalid) ? (unsigned)(x3_boff + bbase) : kOOB;
+      rb[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dense, off, 0, 0));
+    } else
 #pragma unroll
     for (int r = 0; r < T::BV; ++r) {
       const unsigned off = (bok[r] && kvalid) ? (unsigned)(boff[r] + bbase) : kOOB;
-      if constexpr (ABL >= 1 && ABL != 9) rb[r] = f32x4{(float)off, 1.f, 2.f, 3.f};
-      else
-        rb[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dense, off, 0, 0));
+      rb[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dense, off, 0, 0));
     }
-    c0 += BK;
-    if (c0 >= p.Cs) { c0 = 0; ++tap; }
+    // advance to the following K step: pure integer arithmetic, the offsets are recomputed from
+    // (kh, kw, c0) every time -- written as selects this became four scalar branches per K step
+    // inside the MFMA stream (r01 ISA)
+    --k_left;
+    const int nc0 = c0 + BK;
+    const int wrap = nc0 >= p.Cs ? 1 : 0;          // next K step starts a new tap
+    const int nkw = kw + wrap;
+    const int wrapw = nkw >= p.kw_n ? 1 : 0;
+    kh += wrapw;
+    kw = nkw * (1 - wrapw);
+    c0 = nc0 * (1 - wrap);
+    tapbit <<= wrap;
+    aoff = kh * a_step_h + kw * a_step_w + 4 * c0;
+    bbase = kh * b_step_h + kw * b_step_w + c0 * b_cmul;
   };
-
-  auto store = [&](const f32x4 (&ra)[AS], const f32x4 (&rb)[T::BV], int buf) {
-    if constexpr (ABL >= 2 && ABL != 9) {
-      asm volatile("" ::"v"(ra[0][0]), "v"(rb[0][0]));
-      return;
-    }
-    float* As = lds + buf * T::STAGE;
-    float* Bs = As + T::A_SZ;
+  auto store_a = [&](const f32x4 (&ra)[AX], float* As) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < AS; ++s) {
       const int row = (t >> 2) + 64 * s;
+      f32x4 v = ra[s];
+      if constexpr (AFF) {
+        const unsigned okbits = __builtin_bit_cast(unsigned, ra[AS + 3][0]);
+        v = bn_relu_affine(v, ra[AS], ra[AS + 1], ra[AS + 2]);
+        if (!((okbits >> s) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};   // zero padding of the ACTIVATION
+      }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) As[(kq * 4 + j) * T::PA + 8 * kq + row] = ra[s][j];
+      for (int j = 0; j < 4; ++j) As[(kq * 4 + j) * T::PA + 8 * kq + row] = v[j];
     }
+  };
+  auto store_b = [&](const f32x4 (&rb)[T::BV], float* Bs) __attribute__((always_inline)) {
 #pragma unroll
     for (int r = 0; r < T::BV; ++r) {
       const int idx = t + NT * r;
-      if (idx < BK * BN / 4) {
+      if ((r + 1) * NT <= BK * BN / 4 || idx < BK * BN / 4) {
         if constexpr (!BTRANS) {
           const int kr = idx / (BN / 4), nq = idx - kr * (BN / 4);
           *reinterpret_cast<f32x4*>(&Bs[kr * T::PB + 8 * (kr >> 2) + nq * 4]) = rb[r];
@@ -1709,168 +1635,17 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
       }
     }
   };
-
-  f32x4 ra0[AS], ra1[AS], ra2[AS];
-  f32x4 rb0[T::BV], rb1[T::BV], rb2[T::BV];
-  float* buf0 = lds;
-  float* buf1 = lds + T::STAGE;
-  unsigned long long st_k0 = 0, st_l0 = 0, st_l1 = 0, d_load = 0, d_mfma = 0, d_store = 0, d_bar = 0;
-  unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-  (void)s0; (void)s1; (void)s2; (void)s3; (void)s4; (void)d_load; (void)d_mfma; (void)d_store; (void)d_bar;
-#define GS_STAMP(x) if constexpr (ABL == 9) { x = gs_stamp(); }
-  if constexpr (ABL == 9) st_k0 = __builtin_amdgcn_s_memrealtime();
-  if constexpr (PIPE) {
-    // scalar K-step state of the NEXT stage to load (no divisions, no branches in the loop).
-    // (An incremental form with precomputed deltas saves ~10 SALU per K step but pushed the kernel
-    // past its SGPR budget: the buffer descriptors were spilled to VGPRs and every load became a
-    // waterfall loop.  The kernel sits at 103 SGPRs; keep the live scalar set small.)
-    const int a_step_h = 4 * p.step_h * (int)p.s_h, a_step_w = 4 * p.step_w * (int)p.s_w;
-    const int b_step_h = 4 * (int)p.d_tap_h, b_step_w = 4 * (int)p.d_tap_w;
-    const int b_cmul = BTRANS ? 4 : 4 * p.d_row;
-    int kh = tap / p.kw_n, kw = tap - kh * p.kw_n;
-    int aoff = kh * a_step_h + kw * a_step_w + 4 * c0;
-    int bbase = kh * b_step_h + kw * b_step_w + c0 * b_cmul;
-    unsigned tapbit = tap < 32 ? (1u << tap) : 0u;
-    int k_left = nk;
-    auto load_a = [&](f32x4 (&ra)[AX]) __attribute__((always_inline)) {
-      const bool kvalid = k_left > 0;
-      unsigned okbits = 0;
-#pragma unroll
-      for (int s = 0; s < AS; ++s) {
-        const bool ok = kvalid && (vmask[s] & tapbit) != 0;
-        const unsigned off = ok ? (unsigned)(rowoff[s] + aoff) : kOOB;
-        okbits |= (ok ? 1u : 0u) << s;
-        if constexpr (ABL >= 1 && ABL != 9) ra[s] = f32x4{(float)off, 1.f, 2.f, 3.f};
-        else
-          ra[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_src, off, 0, 0));
-      }
-      if constexpr (AFF) {
-        const float* cp = coefL + c0 + kq * 4;   // channels of this K step handled by this thread
-        ra[AS] = *reinterpret_cast<const f32x4*>(cp);
-        ra[AS + 1] = *reinterpret_cast<const f32x4*>(cp + p.Cs);
-        ra[AS + 2] = *reinterpret_cast<const f32x4*>(cp + 2 * p.Cs);
-        ra[AS + 3][0] = __builtin_bit_cast(float, okbits);
-      }
-    };
-    // bf16x3 forward: thread (k row kr = lane & 15 of the 16-channel step, column quad
-    // nq = (lane >> 4) + 4 * wave) fetches ONE 16-byte quad of the [k][n] weights per step, like the
-    // fp32 loop (a wave reads 16 rows x 64 contiguous bytes).  The k rows run fastest over the lanes so
-    // that the 32-bit pair stores of x3_k_loop<BFWD> walk consecutive LDS banks.  (r02 fetched four
-    // consecutive k of one column as four dword loads per step: 4x the vector-memory instructions,
-    // level with the fp32 loop.)
-    const int x3_kr = lane & 15, x3_nq = (lane >> 4) + 4 * wave;
-    const int x3_col = n0 + 4 * x3_nq;
-    const bool x3_bok = 4 * x3_nq < BN && x3_col < p.n_lim;
-    const int x3_boff = 4 * (x3_kr * p.d_row + x3_col);
-    auto load_b = [&](f32x4 (&rb)[T::BV]) __attribute__((always_inline)) {
-      const bool kvalid = k_left > 0;
-      if constexpr ((X3 || F16) && !BTRANS) {
-        const unsigned off = (x3_bok && kvalid) ? (unsigned)(x3_boff + bbase) : kOOB;
-        rb[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dense, off, 0, 0));
-      } else
-#pragma unroll
-      for (int r = 0; r < T::BV; ++r) {
-        const unsigned off = (bok[r] && kvalid) ? (unsigned)(boff[r] + bbase) : kOOB;
-        if constexpr (ABL >= 1 && ABL != 9) rb[r] = f32x4{(float)off, 1.f, 2.f, 3.f};
-        else
-          rb[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dense, off, 0, 0));
-      }
-      // advance to the following K step: pure integer arithmetic, the offsets are recomputed from
-      // (kh, kw, c0) every time -- written as selects this became four scalar branches per K step
-      // inside the MFMA stream (r01 ISA)
-      --k_left;
-      const int nc0 = c0 + BK;
-      const int wrap = nc0 >= p.Cs ? 1 : 0;          // next K step starts a new tap
-      const int nkw = kw + wrap;
-      const int wrapw = nkw >= p.kw_n ? 1 : 0;
-      kh += wrapw;
-      kw = nkw * (1 - wrapw);
-      c0 = nc0 * (1 - wrap);
-      tapbit <<= wrap;
-      aoff = kh * a_step_h + kw * a_step_w + 4 * c0;
-      bbase = kh * b_step_h + kw * b_step_w + c0 * b_cmul;
-    };
-    auto store_a = [&](const f32x4 (&ra)[AX], float* As) __attribute__((always_inline)) {
-      if constexpr (ABL >= 2 && ABL != 9) { asm volatile("" ::"v"(ra[0][0])); return; }
-#pragma unroll
-      for (int s = 0; s < AS; ++s) {
-        const int row = (t >> 2) + 64 * s;
-        f32x4 v = ra[s];
-        if constexpr (AFF) {
-          const unsigned okbits = __builtin_bit_cast(unsigned, ra[AS + 3][0]);
-          v = bn_relu_affine(v, ra[AS], ra[AS + 1], ra[AS + 2]);
-          if (!((okbits >> s) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};   // zero padding of the ACTIVATION
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) As[(kq * 4 + j) * T::PA + 8 * kq + row] = v[j];
-      }
-    };
-    auto store_b = [&](const f32x4 (&rb)[T::BV], float* Bs) __attribute__((always_inline)) {
-      if constexpr (ABL >= 2 && ABL != 9) { asm volatile("" ::"v"(rb[0][0])); return; }
-#pragma unroll
-      for (int r = 0; r < T::BV; ++r) {
-        const int idx = t + NT * r;
-        if ((r + 1) * NT <= BK * BN / 4 || idx < BK * BN / 4) {
-          if constexpr (!BTRANS) {
-            const int kr = idx / (BN / 4), nq = idx - kr * (BN / 4);
-            *reinterpret_cast<f32x4*>(&Bs[kr * T::PB + 8 * (kr >> 2) + nq * 4]) = rb[r];
-          } else {
-            const int nrow = idx >> 2, kq2 = idx & 3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) Bs[(kq2 * 4 + j) * T::PB + 8 * kq2 + nrow] = rb[r][j];
-          }
-        }
-      }
-    };
-    GS_STAMP(st_l0)
-    if constexpr (F16)
-      f16_k_loop<BM, BN, AX, AFF, !BTRANS>(nk, lds, acc, wave, lane, t, BTRANS ? (t >> 2) : 4 * x3_nq,
-                                           BTRANS ? (t & 3) : x3_kr, load_a, load_b);
-    else if constexpr (X3)
-      x3_k_loop<BM, BN, AX, !BTRANS>(nk, lds, acc, wave, lane, t, BTRANS ? (t >> 2) : 4 * x3_nq,
-                                     BTRANS ? (t & 3) : x3_kr, load_a, load_b);
-    else if constexpr (PAIR)
-      pipelined_k_loop_pairs<BM, BN, AX>(nk, lds, acc, wave, lane, load_a, load_b, store_a, store_b);
-    else
-      pipelined_k_loop<BM, BN, AX>(nk, lds, acc, wave, lane, load_a, load_b, store_a, store_b);
-  } else {
-  // step i computes from buf[i&1]; two register sets hold steps i+1 and i+2 (in flight); the set
-  // freed at step i is refilled with step i+3.  Unrolled by 6: buffer parity and set index static.
-#define GS_ROW_PHASE(I, RL_A, RL_B, RS_A, RS_B, BC, BI)                                   \
-  if ((I) < nk) {                                                                        \
-    GS_STAMP(s0)                                                                         \
-    if ((I) + 3 < nk) load(RL_A, RL_B);                                                  \
-    GS_STAMP(s1)                                                                         \
-    mfma_stage<BM, BN, (ABL >= 3 && ABL != 9)>(BC, BC + T::A_SZ, acc, wave, lane);       \
-    GS_STAMP(s2)                                                                         \
-    if ((I) + 1 < nk) store(RS_A, RS_B, BI);                                             \
-    GS_STAMP(s3)                                                                         \
-    __syncthreads();                                                                     \
-    GS_STAMP(s4)                                                                         \
-    if constexpr (ABL == 9) {                                                            \
-      d_load += s1 - s0; d_mfma += s2 - s1; d_store += s3 - s2; d_bar += s4 - s3;        \
-    }                                                                                    \
-  }
-  if (nk > 0) {
-    load(ra0, rb0);
-    if (nk > 1) load(ra1, rb1);
-    if (nk > 2) load(ra2, rb2);
-    store(ra0, rb0, 0);
-    __syncthreads();
-    GS_STAMP(st_l0)
-    for (int ib = 0; ib < nk; ib += 6) {
-      GS_ROW_PHASE(ib + 0, ra0, rb0, ra1, rb1, buf0, 1)
-      GS_ROW_PHASE(ib + 1, ra1, rb1, ra2, rb2, buf1, 0)
-      GS_ROW_PHASE(ib + 2, ra2, rb2, ra0, rb0, buf0, 1)
-      GS_ROW_PHASE(ib + 3, ra0, rb0, ra1, rb1, buf1, 0)
-      GS_ROW_PHASE(ib + 4, ra1, rb1, ra2, rb2, buf0, 1)
-      GS_ROW_PHASE(ib + 5, ra2, rb2, ra0, rb0, buf1, 0)
-    }
-  }
-  }
-#undef GS_ROW_PHASE
-  GS_STAMP(st_l1)
-  if constexpr (ABL == 9) {
+  if constexpr (TIMELINE) st_l0 = gs_stamp();
+  if constexpr (PACKED)
+    packed_k_loop<PK, BM, BN, AX, AFF, !BTRANS>(nk, lds, acc, wave, lane, t,
+                                                BTRANS ? (t >> 2) : 4 * x3_nq,
+                                                BTRANS ? (t & 3) : x3_kr, load_a, load_b);
+  else if constexpr (KLOOP == GS_KLOOP_FP32_PAIRS)
+    pipelined_k_loop_pairs<BM, BN, AX>(nk, lds, acc, wave, lane, load_a, load_b, store_a, store_b);
+  else
+    pipelined_k_loop<BM, BN, AX>(nk, lds, acc, wave, lane, load_a, load_b, store_a, store_b);
+  if constexpr (TIMELINE) {
+    st_l1 = gs_stamp();
     float* keep = p.slab;
     IgemmArgs q = p;
     q.slab = nullptr;
@@ -1881,16 +1656,13 @@ __global__ __launch_bounds__(NT) void igemm_rows_fast_kernel(const IgemmArgs p) 
     if (lane == 0) {
       unsigned long long* o = reinterpret_cast<unsigned long long*>(keep) + ((long)blockIdx.x * 4 + wave) * 8;
       o[0] = st_k0; o[1] = st_l1 - st_l0; o[2] = st_entry; o[3] = r_end;
-      o[4] = d_load; o[5] = d_mfma; o[6] = d_store;
       // HW_REG_HW_ID (4) and HW_REG_XCC_ID (20), all 32 bits: which CU / SIMD ran this wave
       o[7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
              ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-      (void)d_bar;
     }
   } else {
-    rows_epilogue<BM, BN, ((X3 || F16) && BN == 64), SK>(p, lds, acc, m0, n0, t, wave, lane, split, tile);
+    rows_epilogue<BM, BN, (PACKED && BN == 64), SK>(p, lds, acc, m0, n0, t, wave, lane, split, tile);
   }
-#undef GS_STAMP
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2386,7 +2158,8 @@ static Plan make_plan(int M, int Nn, int Ktot, bool allow_split, int max_splits 
     pl.splits = (int)ceil_div(pl.nk_total, pl.nk_per_split);
     return pl;
   }
-  if (pipelined && !wg_target_forced() && env_int("GS_FORCE_BM", 0) == 0) {
+  static const int force_bm = env_int("GS_FORCE_BM", 0);
+  if (pipelined && !wg_target_forced() && force_bm == 0) {
     // Pipelined kernels (rows and wgrad): 64-row tiles and a small cost model over the column
     // width {80,64,48,32} and the split factor, fitted to the r01 plan sweeps
     // (tools/sweep_conv_plans.py over the supernet's GEMM shapes at 1024x512 bs 2,
@@ -2463,7 +2236,6 @@ static Plan make_plan(int M, int Nn, int Ktot, bool allow_split, int max_splits 
     target = (pl.nk_total / s_hi >= 48) ? 2 * num_cu() : num_cu();
   }
   const long can_split = allow_split ? std::min<long>(max_splits, std::max(1, pl.nk_total / min_ksteps())) : 1;
-  static const int force_bm = env_int("GS_FORCE_BM", 0);
   const long pad128 = ceil_div(M, 128) * 128, pad64 = ceil_div(M, 64) * 64;
   const bool wasteful = pad128 * 100 > pad64 * 115;  // e.g. M = 64 rows of a stage-1 1x1 wgrad
   pl.bm = force_bm ? force_bm : ((t128 * can_split >= target && !wasteful) ? 128 : 64);
@@ -2483,113 +2255,36 @@ static Plan make_plan(int M, int Nn, int Ktot, bool allow_split, int max_splits 
   return pl;
 }
 
+// The twelve tiles the kernels are instantiated for, as compile-time constants: calls
+// f(integral_constant BM, integral_constant BN) for the plan's tile.  Which (kernel, tile) pairs exist
+// is said by the constexpr predicates next to the kernels (fast_tile_ok, in_affine_tile,
+// splitk_combine_tile); a launcher's lambda asks them with `if constexpr`.
+template <class F>
+static inline void dispatch_tile(const Plan& pl, F&& f) {
+  auto columns = [&](auto BM) {
+    switch (pl.bn) {
+      case 128: f(BM, std::integral_constant<int, 128>{}); break;
+      case 96: f(BM, std::integral_constant<int, 96>{}); break;
+      case 80: f(BM, std::integral_constant<int, 80>{}); break;
+      case 64: f(BM, std::integral_constant<int, 64>{}); break;
+      case 48: f(BM, std::integral_constant<int, 48>{}); break;
+      case 32: f(BM, std::integral_constant<int, 32>{}); break;
+      default: break;
+    }
+  };
+  if (pl.bm == 128) columns(std::integral_constant<int, 128>{});
+  else if (pl.bm == 64) columns(std::integral_constant<int, 64>{});
+}
+
 template <bool BTRANS, bool DIVS, bool SCALAR, int KS>
 static void launch_rows(const Plan& pl, const IgemmArgs& a, hipStream_t st) {
   const dim3 grid(pl.tiles_m * pl.tiles_n, pl.splits), block(NT);
   note_launch(BTRANS ? GS_OP_DGRAD : GS_OP_FORWARD, GS_KLOOP_GENERIC, pl, false, 0,
               2.0 * a.M * (double)a.Nn * a.Ktot);
-#define GS_ROWS(BM_, BN_)                                                                     \
-  if (pl.bm == BM_ && pl.bn == BN_) {                                                         \
-    hipLaunchKernelGGL((igemm_rows_kernel<BM_, BN_, BTRANS, DIVS, SCALAR, KS>), grid, block, 0, st, a); \
-    return;                                                                                   \
-  }
-  GS_ROWS(128, 128) GS_ROWS(128, 96) GS_ROWS(128, 80) GS_ROWS(128, 64) GS_ROWS(128, 48) GS_ROWS(128, 32)
-  GS_ROWS(64, 128) GS_ROWS(64, 96) GS_ROWS(64, 80) GS_ROWS(64, 64) GS_ROWS(64, 48) GS_ROWS(64, 32)
-#undef GS_ROWS
-}
-
-// K loop of a fast row launch (GS_KLOOP_*).  bf16x3 contraction (see x3_k_loop): stride-1 dgrad,
-// 64-row tiles, BN 64 / 48.  r02 sweep over the supernet's data-gradient shapes
-// (profiles/r02_bf16x3_probe.md): +7.5 % in sum against the fp32 loop, ahead everywhere except short
-// split-K ranges (a split's 16 K steps are 8 bf16 steps: the fill does not amortise) and
-// one-workgroup-per-CU launches (its single LDS stage wants co-resident workgroups to hide the two
-// barriers per step: s3 1x1 256->1024, 30.5 vs 25.6 us), which keep the fp32 loop.  GS_X3=0 switches
-// it off, GS_X3=n (n > 1) raises the minimum K steps per workgroup (3 K steps = 2 bf16 steps, a
-// quarter wasted: -10 %).  The forward runs on it only behind GS_X3_FWD=<min K steps> (the [k][n]
-// weights are staged with eight dword loads per thread and step: level with the fp32 loop).
-// Long K ranges otherwise run two K steps per barrier (pipelined_k_loop_pairs) when the launch has at
-// most three workgroups per CU anyway (its four LDS stages allow no more); big grids and short K
-// ranges keep the two-stage loop, whose smaller footprint lets five workgroups per CU overlap their
-// fill / drain (r01 A/B: s2..s4 3x3 and the head convs +3..7 %, s1 3x3 -3 % if paired).
-// forward on the bf16x3 loop: 0 = never, 1 = every 3x3 where it measured ahead of the fp32 loops, 2 =
-// wherever the loop's gate admits it (tests, sweeps), 3 = the split-K 3x3s only (DEFAULT); GS_X3_FWD
-// sets the initial value, gs_debug_set_x3_fwd changes it at run time.
-// Why not everywhere it is faster (K3 +9 % at stage 1): the bf16x3 contraction is ~1.3-1.5x noisier
-// than the exact fmaf chain of the fp32 MFMA (the bf16 MFMA's internal accumulation: see kX3Terms) and
-// forward noise is amplified by every layer behind it.  With mode 1 the median error ratio of the
-// ill-conditioned parameter gradients against the fp32 oracle rose from 1.15 to 1.53 on config 4
-// (bound 1.5, tests/parity.py) and three parameters of config 3 left the 3x bound.  Mode 3 keeps the
-// early layers on the fp32 MFMA and takes the loop only where a 3x3 is split along K -- stages 3-4 at
-// bs 2 and the heads' big-K convs, +3..5 % per launch: the margins of the full-size tests do not move
-// (config 4 median 1.13 vs 1.15, config 3 p90 1.72 vs 1.70, largest ratio 2.06 both), K3 on the
-// sampled mix 0.541 -> 0.551 of the fp32 peak, the step +0.65 % (A/B/A/B on one box).
-extern int g_x3_fwd;   // capi_misc.hip (-1 = not yet read from the environment)
-static inline int x3_fwd_mode() {
-  if (g_x3_fwd < 0) g_x3_fwd = env_int("GS_X3_FWD", 3);
-  return g_x3_fwd;
-}
-static inline bool pair_loop_ok(const Plan& pl) {
-  return pl.nk_per_split >= pair_min_ksteps() &&
-         (long)pl.tiles_m * pl.tiles_n * pl.splits <= 3L * num_cu();
-}
-static inline bool x3_grid_ok(const Plan& pl, int min_ksteps_) {
-  // (r03 A/B: 32 instead of 48 puts the MIN anchor's split-K launches on the loop as well -- MIN +1 %,
-  // sampled mix +-0; kept at 48)
-  static const int split_min = env_int("GS_X3_SPLIT_MIN", 48);
-  return min_ksteps_ > 0 && pl.bm == 64 && pl.nk_per_split >= min_ksteps_ &&
-         (pl.splits == 1 || pl.nk_per_split >= split_min) &&
-         (long)pl.tiles_m * pl.tiles_n * pl.splits >= 2L * num_cu();
-}
-// Forward precision (gs_set_forward_precision, inference): 0 = fp32 (default), 1 = fp16 operands.
-// Training precision (gs_set_train_precision): 1 = the forward launches of the fp16 inference mode
-// AND the fast data-gradient launches contract fp16 operands; weight gradients stay fp32.
-extern int g_fwd_precision;     // capi_misc.hip
-extern int g_train_precision;   // capi_misc.hip
-static inline bool f16_train_on() { return g_train_precision == 1; }
-static inline bool f16_fwd_on() { return g_fwd_precision == 1 || f16_train_on(); }
-// The f16 loop's tiles: 64 rows, BN 64 or 48 (plan_fwd / f16_dgrad_plan narrow the planner's 80 / 32
-// to them).
-static inline bool f16_plan_ok(const Plan& pl) { return pl.bm == 64 && (pl.bn == 64 || pl.bn == 48); }
-// A fast data-gradient launch of this plan runs on the f16 loop in training fp16 mode: the tiles the
-// bf16x3 data-gradient gate admits, without its grid-size condition (as the f16 forward).
-// (profiles/r05_fp16_training.md: per shape class against the fp32 loops, kernels alone)
-static inline bool f16_dgrad_ok(const Plan& pl) { return f16_train_on() && f16_plan_ok(pl); }
-// training fp16 mode: a fast data-gradient plan of 64 x 80 / 64 x 32 tiles gets 64 / 48 columns, the
-// split-K factor (hence the workspace) unchanged -- what plan_fwd does for the forward
-static inline Plan f16_dgrad_plan(Plan pl, int Nn) {
-  if (f16_train_on() && pl.bm == 64 && (pl.bn == 80 || pl.bn == 32) && g_force_plan[0] == 0) {
-    pl.bn = pl.bn == 80 ? 64 : 48;
-    pl.tiles_n = (int)ceil_div(Nn, pl.bn);
-  }
-  return pl;
-}
-
-template <bool BTRANS>
-static inline int rows_fast_kloop(const Plan& pl, bool in_affine, int ks = 3) {
-  // fp16 mode: every fast forward launch on a 64-row tile, in_affine included;
-  // training fp16 mode: the fast data gradients as well (section 17)
-  if (!BTRANS && f16_fwd_on() && f16_plan_ok(pl)) return GS_KLOOP_F16;
-  if (BTRANS && f16_dgrad_ok(pl)) return GS_KLOOP_F16;
-  if constexpr (BTRANS) {
-    static const int x3_min = env_int("GS_X3", 4);
-    if (x3_grid_ok(pl, x3_min) && (pl.bn == 64 || pl.bn == 48)) return GS_KLOOP_BF16X3;
-  } else {
-    // Forward (r03: the [k][n] weights staged one k row per thread and step, x3_k_loop<BFWD>).
-    // Per shape against the fp32 loops, kernels alone (profiles/r03_fwd_x3_per_shape.md): 3x3 at
-    // stage 1 +9 % (one K step per barrier there), the split-K 3x3s of stages 3-4 +3..5 %, the
-    // unsplit 3x3 of stage 2 -4 % (the two-steps-per-barrier fp32 loop wins), 1x1s -10..+8 %
-    // without a pattern.  Production: 3x3 only, and not where the paired fp32 loop runs unsplit.
-    const int mode = x3_fwd_mode();
-    if (mode > 0 && !in_affine && x3_grid_ok(pl, 4) && (pl.bn == 64 || pl.bn == 48)) {
-      if (mode == 2) return GS_KLOOP_BF16X3;
-      if (mode == 3) {   // only the split-K 3x3s (stages 3-4: late layers, the least amplification)
-        if (ks == 3 && pl.splits > 1) return GS_KLOOP_BF16X3;
-      } else if (ks == 3 && !(pair_loop_ok(pl) && pl.splits == 1)) {
-        return GS_KLOOP_BF16X3;
-      }
-    }
-  }
-  return pair_loop_ok(pl) ? GS_KLOOP_FP32_PAIRS : GS_KLOOP_FP32;
+  dispatch_tile(pl, [&](auto BM, auto BN) {
+    hipLaunchKernelGGL((igemm_rows_kernel<decltype(BM)::value, decltype(BN)::value, BTRANS, DIVS,
+                                          SCALAR, KS>), grid, block, 0, st, a);
+  });
 }
 
 // fused_layers.hip: the live timer of the role-1 (K3) launches.  If a timer interval is open for the
@@ -2607,8 +2302,10 @@ static inline void launch_rows_kernel(K kernel, const dim3& grid, const dim3& bl
   else hipLaunchKernelGGL(kernel, grid, block, lds_dyn, st, a);
 }
 
+// kloop: the K loop the route chose (GS_KLOOP_FP32 / _FP32_PAIRS / _BF16X3 / _F16); a (tile, K loop,
+// in_affine) combination without an instantiation launches nothing (the routes admit none).
 template <bool BTRANS, int KS, int ROLE = 0>
-static void launch_rows_fast(const Plan& pl, const IgemmArgs& a_in, hipStream_t st) {
+static void launch_rows_fast(const Plan& pl, int kloop, const IgemmArgs& a_in, hipStream_t st) {
   IgemmArgs a = a_in;
   a.nsplits = pl.splits;
   {  // the larger operand should cross the fabric once: see the kernel's tile decode
@@ -2617,161 +2314,87 @@ static void launch_rows_fast(const Plan& pl, const IgemmArgs& a_in, hipStream_t 
     a.tile_order = force >= 0 ? force : (b_bytes > a_bytes ? 1 : 0);
   }
   const dim3 grid(pl.tiles_m * pl.tiles_n * pl.splits), block(NT);
-  const int kloop = rows_fast_kloop<BTRANS>(pl, a.a_coeffs != nullptr, KS);
-  const bool pair = kloop == GS_KLOOP_FP32_PAIRS;
-  note_launch(BTRANS ? GS_OP_DGRAD : GS_OP_FORWARD, kloop, pl, a.a_coeffs != nullptr, a.bw_mode,
+  const bool aff = a.a_coeffs != nullptr;
+  note_launch(BTRANS ? GS_OP_DGRAD : GS_OP_FORWARD, kloop, pl, aff, a.bw_mode,
               2.0 * a.M * (double)a.Nn * a.Ktot);
   if (ROLE == 1 && !BTRANS && kloop < GS_KLOOP_COUNT)
     flops_add(&g_k3_flops[kloop], 2.0 * a.M * (double)a.Nn * a.Ktot);
   if (a.tickets && splitk_combine_ok(pl)) __atomic_fetch_add(&g_splitk_combined, 1LL, __ATOMIC_RELAXED);
   else a.tickets = nullptr;
-  // (GS_SKL: the extended-epilogue instantiation when the launch carries arrival counters)
   if (!splitk_combine_tile(pl.bm, pl.bn)) a.col_tickets = nullptr;   // (callers check; see column_tickets)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (ROLE == 1 && !BTRANS && !k3_launch_events(st, pl.splits == 1 || a.tickets != nullptr, &ev0, &ev1))
     ev0 = ev1 = nullptr;
-#define GS_SKL(...)                                                                            \
-  do {                                                                                         \
-    if (a.tickets || a.col_tickets)                                                            \
-      launch_rows_kernel((igemm_rows_fast_kernel<__VA_ARGS__, true>), grid, block, lds_dyn, st, a, ev0, ev1);   \
-    else                                                                                       \
-      launch_rows_kernel((igemm_rows_fast_kernel<__VA_ARGS__, false>), grid, block, lds_dyn, st, a, ev0, ev1);  \
-  } while (0)
-#define GS_PLAIN(...) \
-  launch_rows_kernel((igemm_rows_fast_kernel<__VA_ARGS__, false>), grid, block, lds_dyn, st, a, ev0, ev1)
-  int lds_dyn = 0;
-  if (kloop == GS_KLOOP_F16) {
-#define GS_F16L(BN_, AFF_)                                                                        \
-  do {                                                                                            \
-    if (a.tickets || a.col_tickets)                                                               \
-      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, BTRANS, KS, 0, ROLE, true, false, AFF_, \
-                                                 false, true, true>), grid, block, 0, st, a, ev0, ev1);  \
-    else                                                                                          \
-      launch_rows_kernel((igemm_rows_fast_kernel<64, BN_, BTRANS, KS, 0, ROLE, true, false, AFF_, \
-                                                 false, false, true>), grid, block, 0, st, a, ev0, ev1); \
-  } while (0)
-    if constexpr (!BTRANS) {
-      if (a.a_coeffs) {
-        if (pl.bn == 64) GS_F16L(64, true);
-        else GS_F16L(48, true);
-        return;
+  // the extended-epilogue instantiation when the launch carries arrival counters
+  const bool xe = a.tickets || a.col_tickets;
+  // (GS_DYN_LDS caps the workgroups per CU of the plain fp32 loops: tuning only)
+  const int lds_dyn = (aff || packed_kloop(kloop)) ? 0 : dyn_lds();
+  dispatch_tile(pl, [&](auto BM, auto BN) {
+    auto launch = [&](auto KL, auto AFF) {
+      constexpr int bm = decltype(BM)::value, bn = decltype(BN)::value, kl = decltype(KL)::value;
+      constexpr bool af = decltype(AFF)::value;
+      if constexpr (fast_tile_ok(kl, af, BTRANS, bm, bn)) {
+        if constexpr (splitk_combine_tile(bm, bn)) {
+          if (xe) {
+            launch_rows_kernel((igemm_rows_fast_kernel<bm, bn, BTRANS, KS, ROLE, kl, af, true>), grid,
+                               block, lds_dyn, st, a, ev0, ev1);
+            return;
+          }
+        }
+        launch_rows_kernel((igemm_rows_fast_kernel<bm, bn, BTRANS, KS, ROLE, kl, af, false>), grid,
+                           block, lds_dyn, st, a, ev0, ev1);
       }
+    };
+    auto with_aff = [&](auto KL) {
+      if (aff) launch(KL, std::true_type{});
+      else launch(KL, std::false_type{});
+    };
+    switch (kloop) {
+      case GS_KLOOP_FP32: with_aff(std::integral_constant<int, GS_KLOOP_FP32>{}); break;
+      case GS_KLOOP_FP32_PAIRS: with_aff(std::integral_constant<int, GS_KLOOP_FP32_PAIRS>{}); break;
+      case GS_KLOOP_BF16X3: with_aff(std::integral_constant<int, GS_KLOOP_BF16X3>{}); break;
+      case GS_KLOOP_F16: with_aff(std::integral_constant<int, GS_KLOOP_F16>{}); break;
+      default: break;
     }
-    if (pl.bn == 64) GS_F16L(64, false);
-    else GS_F16L(48, false);
-#undef GS_F16L
-    return;
-  }
-  if (kloop == GS_KLOOP_BF16X3) {
-    if constexpr (BTRANS) {
-      if (pl.bn == 64) GS_SKL(64, 64, true, KS, 0, ROLE, true, false, false, true);
-      else GS_SKL(64, 48, true, KS, 0, ROLE, true, false, false, true);
-    } else if (pl.bn == 64) {
-      GS_SKL(64, 64, false, KS, 0, ROLE, true, false, false, true);
-    } else {
-      GS_SKL(64, 48, false, KS, 0, ROLE, true, false, false, true);
-    }
-    return;
-  }
-  if constexpr (!BTRANS) {
-    if (a.a_coeffs) {   // relu(bn(x)) evaluated in the loader: 64-row tiles (the planner's choice)
-#define GS_FAST_AFF(BN_)                                                                   \
-  if (pl.bm == 64 && pl.bn == BN_) {                                                       \
-    if constexpr (splitk_combine_tile(64, BN_)) {                                          \
-      if (pair) GS_SKL(64, BN_, false, KS, 0, ROLE, true, true, true, false);              \
-      else GS_SKL(64, BN_, false, KS, 0, ROLE, true, false, true, false);                  \
-    } else {                                                                               \
-      if (pair) GS_PLAIN(64, BN_, false, KS, 0, ROLE, true, true, true, false);            \
-      else GS_PLAIN(64, BN_, false, KS, 0, ROLE, true, false, true, false);                \
-    }                                                                                      \
-    return;                                                                                \
-  }
-      GS_FAST_AFF(128) GS_FAST_AFF(96) GS_FAST_AFF(80) GS_FAST_AFF(64) GS_FAST_AFF(48) GS_FAST_AFF(32)
-#undef GS_FAST_AFF
-      return;   // (unreachable: conv_in_affine_ok() admits only plans with 64-row tiles)
-    }
-  }
-  lds_dyn = dyn_lds();
-#define GS_FAST(BM_, BN_)                                                                  \
-  if (pl.bm == BM_ && pl.bn == BN_) {                                                      \
-    if constexpr (splitk_combine_tile(BM_, BN_)) {                                         \
-      if (pair) GS_SKL(BM_, BN_, BTRANS, KS, 0, ROLE, true, true, false, false);           \
-      else GS_SKL(BM_, BN_, BTRANS, KS, 0, ROLE, true, false, false, false);               \
-    } else {                                                                               \
-      if (pair) GS_PLAIN(BM_, BN_, BTRANS, KS, 0, ROLE, true, true, false, false);         \
-      else GS_PLAIN(BM_, BN_, BTRANS, KS, 0, ROLE, true, false, false, false);             \
-    }                                                                                      \
-    return;                                                                                \
-  }
-  GS_FAST(128, 128) GS_FAST(128, 96) GS_FAST(128, 80) GS_FAST(128, 64) GS_FAST(128, 48) GS_FAST(128, 32)
-  GS_FAST(64, 128) GS_FAST(64, 96) GS_FAST(64, 80) GS_FAST(64, 64) GS_FAST(64, 48) GS_FAST(64, 32)
-#undef GS_FAST
-#undef GS_SKL
-#undef GS_PLAIN
+  });
 }
 
-// the fast row kernel needs: NHWC vector source, channels per tap % BK == 0, 1x1 or 3x3
-static inline bool fast_rows_ok(int cs, int ks, size_t src_bytes, size_t dense_bytes) {
-  return (ks == 1 || ks == 3) && (cs % BK) == 0 && src_bytes < (1ull << 31) &&
-         dense_bytes < (1ull << 31);
-}
-
+// kloop: GS_KLOOP_FP32 or GS_KLOOP_FP32_PAIRS (the route's choice)
 template <int KS>
-static void launch_wgrad_fast(const Plan& pl, const IgemmArgs& a_in, hipStream_t st) {
+static void launch_wgrad_fast(const Plan& pl, int kloop, const IgemmArgs& a_in, hipStream_t st) {
   IgemmArgs a = a_in;
   a.nsplits = pl.splits;
   const dim3 grid(pl.tiles_m * pl.tiles_n * pl.splits), block(NT);
-  const bool pair = pair_loop_ok(pl);
-  note_launch(GS_OP_WGRAD, pair ? GS_KLOOP_FP32_PAIRS : GS_KLOOP_FP32, pl, a.a_coeffs != nullptr, 0,
-              2.0 * a.M * (double)a.Nn * a.Ktot);
+  const bool pair = kloop == GS_KLOOP_FP32_PAIRS;
+  note_launch(GS_OP_WGRAD, kloop, pl, a.a_coeffs != nullptr, 0, 2.0 * a.M * (double)a.Nn * a.Ktot);
   static const int no_walign = env_int("GS_NO_WALIGN", 0);
   const bool walign = !no_walign && a.Wp % BK == 0;
-  if (a.a_coeffs) {
-#define GS_WGF_AFF(BN_)                                                                   \
-  if (pl.bm == 64 && pl.bn == BN_) {                                                      \
-    if (pair && walign)                                                                   \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<64, BN_, KS, true, true, true>), grid, block, 0, st, a); \
-    else if (pair)                                                                        \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<64, BN_, KS, true, false, true>), grid, block, 0, st, a); \
-    else if (walign)                                                                      \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<64, BN_, KS, false, true, true>), grid, block, 0, st, a); \
-    else                                                                                  \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<64, BN_, KS, false, false, true>), grid, block, 0, st, a); \
-    return;                                                                               \
-  }
-    GS_WGF_AFF(128) GS_WGF_AFF(96) GS_WGF_AFF(80) GS_WGF_AFF(64) GS_WGF_AFF(48) GS_WGF_AFF(32)
-#undef GS_WGF_AFF
-    return;
-  }
-#define GS_WGF(BM_, BN_)                                                                  \
-  if (pl.bm == BM_ && pl.bn == BN_) {                                                     \
-    if (pair && walign)                                                                   \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<BM_, BN_, KS, true, true>), grid, block, dyn_lds(), st, a); \
-    else if (pair)                                                                        \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<BM_, BN_, KS, true, false>), grid, block, dyn_lds(), st, a); \
-    else if (walign)                                                                      \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<BM_, BN_, KS, false, true>), grid, block, dyn_lds(), st, a); \
-    else                                                                                  \
-      hipLaunchKernelGGL((igemm_wgrad_fast_kernel<BM_, BN_, KS, false, false>), grid, block, dyn_lds(), st, a); \
-    return;                                                                               \
-  }
-  GS_WGF(128, 128) GS_WGF(128, 96) GS_WGF(128, 80) GS_WGF(128, 64) GS_WGF(128, 48) GS_WGF(128, 32)
-  GS_WGF(64, 128) GS_WGF(64, 96) GS_WGF(64, 80) GS_WGF(64, 64) GS_WGF(64, 48) GS_WGF(64, 32)
-#undef GS_WGF
+  dispatch_tile(pl, [&](auto BM, auto BN) {
+    constexpr int bm = decltype(BM)::value, bn = decltype(BN)::value;
+    auto launch = [&](auto PAIR, auto WALIGN) {
+      constexpr bool pr = decltype(PAIR)::value, wa = decltype(WALIGN)::value;
+      if (a.a_coeffs) {   // relu(bn(x)) evaluated in the loader: 64-row tiles (the planner's choice)
+        if constexpr (in_affine_tile(bm, bn))
+          hipLaunchKernelGGL((igemm_wgrad_fast_kernel<bm, bn, KS, pr, wa, true>), grid, block, 0, st, a);
+      } else {
+        hipLaunchKernelGGL((igemm_wgrad_fast_kernel<bm, bn, KS, pr, wa>), grid, block, dyn_lds(), st, a);
+      }
+    };
+    if (pair && walign) launch(std::true_type{}, std::true_type{});
+    else if (pair) launch(std::true_type{}, std::false_type{});
+    else if (walign) launch(std::false_type{}, std::true_type{});
+    else launch(std::false_type{}, std::false_type{});
+  });
 }
 
 template <bool SCALAR, int KS>
 static void launch_wgrad(const Plan& pl, const IgemmArgs& a, hipStream_t st) {
   const dim3 grid(pl.tiles_m * pl.tiles_n, pl.splits), block(NT);
   note_launch(GS_OP_WGRAD, GS_KLOOP_GENERIC, pl, false, 0, 2.0 * a.M * (double)a.Nn * a.Ktot);
-#define GS_WG(BM_, BN_)                                                                \
-  if (pl.bm == BM_ && pl.bn == BN_) {                                                  \
-    hipLaunchKernelGGL((igemm_wgrad_kernel<BM_, BN_, SCALAR, KS>), grid, block, 0, st, a); \
-    return;                                                                            \
-  }
-  GS_WG(128, 128) GS_WG(128, 96) GS_WG(128, 80) GS_WG(128, 64) GS_WG(128, 48) GS_WG(128, 32)
-  GS_WG(64, 128) GS_WG(64, 96) GS_WG(64, 80) GS_WG(64, 64) GS_WG(64, 48) GS_WG(64, 32)
-#undef GS_WG
+  dispatch_tile(pl, [&](auto BM, auto BN) {
+    hipLaunchKernelGGL((igemm_wgrad_kernel<decltype(BM)::value, decltype(BN)::value, SCALAR, KS>), grid,
+                       block, 0, st, a);
+  });
 }
 
 static int check_desc(const gs_conv_desc* d) {
@@ -2788,43 +2411,6 @@ static int check_desc(const gs_conv_desc* d) {
   return GS_OK;
 }
 
-static bool x_is_vector(const gs_conv_desc* d) {
-  return d->x_sc == 1 && (d->Ci & 3) == 0 && (d->x_sw & 3) == 0 && (d->x_sh & 3) == 0 &&
-         (d->x_sn & 3) == 0;
-}
-
-// fp16 mode: a fast-kernel forward whose plan has 64-row tiles of 80 or 32 columns gets 64 or 48
-// columns instead (the f16 loop's tiles; the split-K factor, hence the workspace, is unchanged)
-static Plan plan_fwd(const gs_conv_desc* d) {
-  Plan pl = make_plan(d->N * d->Ho * d->Wo, d->Co, d->KH * d->KW * d->Ci, true);
-  if (f16_fwd_on() && pl.bm == 64 && (pl.bn == 80 || pl.bn == 32) && g_force_plan[0] == 0 &&
-      x_is_vector(d) && getenv("GS_NO_FAST") == nullptr) {
-    const int ks = (d->KH == 1 && d->KW == 1) ? 1 : ((d->KH == 3 && d->KW == 3) ? 3 : 0);
-    const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
-    const size_t dense_b = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
-    if (fast_rows_ok(d->Ci, ks, src_b, dense_b)) {
-      pl.bn = pl.bn == 80 ? 64 : 48;
-      pl.tiles_n = (int)ceil_div(d->Co, pl.bn);
-    }
-  }
-  return pl;
-}
-// (training fp16 mode: a stride-1 data gradient on the fast kernel gets f16_dgrad_plan's tiles; the
-// strided one narrows each parity class's plan the same way)
-static Plan plan_dgrad(const gs_conv_desc* d) {
-  const Plan pl = make_plan(d->N * d->H * d->W, d->Ci, d->KH * d->KW * d->Co, true);
-  if (!f16_train_on() || d->stride != 1 || getenv("GS_NO_FAST") != nullptr) return pl;
-  const int ks = (d->KH == 1 && d->KW == 1) ? 1 : ((d->KH == 3 && d->KW == 3) ? 3 : 0);
-  const size_t dy_b = (size_t)d->N * d->Ho * d->Wo * d->ldy * sizeof(float);
-  const size_t dense_b = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
-  return fast_rows_ok(d->Co, ks, dy_b, dense_b) ? f16_dgrad_plan(pl, d->Ci) : pl;
-}
-static Plan plan_wgrad(const gs_conv_desc* d) {
-  // wgrad: K runs over pixels (up to 131072 at stage 1) while M x N is tiny: allow deep split-K
-  static const int old_plan = env_int("GS_WGRAD_OLD_PLAN", 0);
-  if (old_plan) return make_plan(d->KH * d->KW * d->Ci, d->Co, d->N * d->Ho * d->Wo, true, 512, false);
-  return make_plan(d->KH * d->KW * d->Ci, d->Co, d->N * d->Ho * d->Wo, true, 512, true, 4.0);
-}
 static size_t slab_bytes(const Plan& pl, long M, int Nn) {
   return pl.splits > 1 ? (size_t)pl.splits * M * Nn * sizeof(float) : 0;
 }
@@ -2845,57 +2431,6 @@ static inline void launch_reduce(const IgemmArgs& a, int splits, int rows_are_ta
     hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(stream_grid(total, 256)), dim3(256), 0, st,
                        a, splits, rows_are_taps);
   }
-}
-
-// ---- strided dgrad as s*s stride-1 sub-problems (one per input-pixel parity class) ----
-// For input row h = hq*s + ph the taps kh with (ph + pad - kh*dil) % s == 0 contribute, reading
-// dy row hq + (ph + pad - kh*dil)/s.  Those taps form an arithmetic progression, so each class is
-// an ordinary gather-GEMM over a sub-sampled tap grid: no MFMA work is spent on structural zeros
-// (the single-launch form wastes 1 - 1/s^2 of it).
-struct TapAxis {
-  int n;      // number of valid taps
-  int k0;     // first valid tap
-  int dk;     // tap step
-  int off0;   // source offset of the first valid tap
-  int step;   // source offset step per valid tap
-};
-static inline TapAxis tap_axis(int ph, int pad, int dil, int s, int K) {
-  TapAxis a{0, 0, 1, 0, 0};
-  int first = -1, second = -1;
-  for (int k = 0; k < K; ++k) {
-    const int num = ph + pad - k * dil;
-    if (((num % s) + s) % s == 0) {
-      if (first < 0) first = k;
-      else if (second < 0) second = k;
-      ++a.n;
-    }
-  }
-  if (a.n == 0) return a;
-  a.k0 = first;
-  a.dk = second > 0 ? second - first : 1;
-  a.off0 = (ph + pad - first * dil) / s;          // exact division
-  a.step = -(a.dk * dil) / s;
-  return a;
-}
-static inline int class_len(int L, int s, int ph) { return L > ph ? (L - ph + s - 1) / s : 0; }
-
-// gs_conv_desc::in_affine (relu(bn(x)) in the operand loaders) needs the fast forward and wgrad
-// kernels with 64-row tiles and the coefficient image in LDS
-static inline bool conv_in_affine_ok(const gs_conv_desc* d) {
-  if (!x_is_vector(d) || d->Ci > kAffMaxC || (d->Ci % BK) != 0) return false;
-  const int ks = (d->KH == 1 && d->KW == 1) ? 1 : ((d->KH == 3 && d->KW == 3) ? 3 : 0);
-  if (!ks) return false;
-  const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
-  const size_t dense_b = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
-  if (!fast_rows_ok(d->Ci, ks, src_b, dense_b) || getenv("GS_NO_FAST")) return false;
-  if ((d->Ci & 3) || (d->Co & 3)) return false;
-  return plan_fwd(d).bm == 64 && plan_wgrad(d).bm == 64;
-}
-
-static inline int ksize_tag(const gs_conv_desc* d) {
-  if (d->KH == 1 && d->KW == 1) return 1;
-  if (d->KH == 3 && d->KW == 3) return 3;
-  return 0;
 }
 
 }  // namespace gs

@@ -1,25 +1,7 @@
 // DynConv2d data gradient (implicit GEMM, fp32 MFMA) — see igemm_core.h
-#include "igemm_core.h"
-#include "igemm_stream.h"
-#include "fused_internal.h"
+#include "igemm_route.h"
 
 using namespace gs;
-
-// workspace needed by the strided (parity-class) path: max over the classes
-size_t gs_dgrad_strided_slab_bytes(const gs_conv_desc* d) {
-  size_t need = 0;
-  const int s = d->stride;
-  for (int ph = 0; ph < s; ++ph)
-    for (int pw = 0; pw < s; ++pw) {
-      const TapAxis th = tap_axis(ph, d->pad, d->dil, s, d->KH), tw = tap_axis(pw, d->pad, d->dil, s, d->KW);
-      const int Hq = class_len(d->H, s, ph), Wq = class_len(d->W, s, pw);
-      if (!th.n || !tw.n || !Hq || !Wq) continue;
-      const long Mc = (long)d->N * Hq * Wq;
-      const Plan pl = make_plan((int)Mc, d->Ci, th.n * tw.n * d->Co, true);
-      need = std::max(need, slab_bytes(pl, Mc, d->Ci));
-    }
-  return need;
-}
 
 // dx[r][0..C) = 0 for a channel slice of a wider buffer (pixel stride ld > C)
 static __global__ __launch_bounds__(256) void zero_rows_kernel(float* __restrict__ dx, long rows,
@@ -38,12 +20,7 @@ static int dgrad_strided_fast(const gs_conv_desc* d, const float* dy, const floa
                               hipStream_t st) {
   const int s = d->stride, ks = ksize_tag(d);
   const long d_tap = (long)d->Ci_max * d->Co_ld;
-  bool any_empty = false;
-  for (int ph = 0; ph < s && !any_empty; ++ph)
-    for (int pw = 0; pw < s; ++pw)
-      if (!tap_axis(ph, d->pad, d->dil, s, d->KH).n || !tap_axis(pw, d->pad, d->dil, s, d->KW).n)
-        any_empty = true;
-  if (!accumulate && any_empty) {
+  if (!accumulate && dgrad_has_tapless_class(d)) {
     // classes without taps (e.g. 3 of the 4 classes of a 1x1 stride-2 conv) stay zero.  A dense dx is
     // cleared with the 1-D memset (a fill kernel); hipMemset2DAsync is staged through ~30 buffer
     // copies per call on ROCm 7.2 (seen in the r01 trace), so a sliced dx gets its own fill kernel.
@@ -57,16 +34,15 @@ static int dgrad_strided_fast(const gs_conv_desc* d, const float* dy, const floa
                          (long)rows, d->Ci / 4, (long)d->x_sw);
     }
   }
-  for (int ph = 0; ph < s; ++ph)
-    for (int pw = 0; pw < s; ++pw) {
-      const TapAxis th = tap_axis(ph, d->pad, d->dil, s, d->KH), tw = tap_axis(pw, d->pad, d->dil, s, d->KW);
-      const int Hq = class_len(d->H, s, ph), Wq = class_len(d->W, s, pw);
-      if (!th.n || !tw.n || !Hq || !Wq) continue;
-      const long Mc = (long)d->N * Hq * Wq;
-      const int ktot = th.n * tw.n * d->Co;
-      const Plan pl = f16_dgrad_plan(make_plan((int)Mc, d->Ci, ktot, true), d->Ci);
-      const size_t need = slab_bytes(pl, Mc, d->Ci);
-      if (need > workspace_bytes || (need && !workspace)) return GS_E_WORKSPACE;
+  int rc = GS_OK;
+  for_each_dgrad_class(d, [&](const DgradClass& c) {
+      if (rc != GS_OK) return;
+      const TapAxis &th = c.th, &tw = c.tw;
+      const int ph = c.ph, pw = c.pw, Hq = c.Hq, Wq = c.Wq, ktot = c.ktot;
+      const long Mc = c.M;
+      const Plan& pl = c.plan;
+      const size_t need = c.need;
+      if (need > workspace_bytes || (need && !workspace)) { rc = GS_E_WORKSPACE; return; }
       IgemmArgs a{};
       a.src = dy; a.out = dx; a.slab = need ? static_cast<float*>(workspace) : nullptr;
       const long tap0 = (long)th.k0 * d->KW + tw.k0;
@@ -87,21 +63,19 @@ static int dgrad_strided_fast(const gs_conv_desc* d, const float* dy, const floa
       a.src_bytes = (unsigned)((size_t)d->N * a.s_n * sizeof(float));
       a.dense_bytes = (unsigned)(((size_t)d->KH * d->KW - tap0) * d_tap * sizeof(float));
       a.o_s = s; a.o_ph = ph; a.o_pw = pw; a.o_Hq = Hq; a.o_Wq = Wq; a.o_H = d->H; a.o_W = d->W;
-      if (splitk_combine_ok(pl)) {   // slabs combined inside the launch (igemm_core.h splitk_publish)
+      if (c.combine) {   // slabs combined inside the launch (splitk_publish)
         a.tickets = splitk_tickets(st, (long)pl.tiles_m * pl.tiles_n);
         a.slab_bytes = (unsigned)need;
       }
-      if (ks == 1) launch_rows_fast<true, 1>(pl, a, st);
-      else launch_rows_fast<true, 3>(pl, a, st);
-      int rc = launch_status();
-      if (rc != GS_OK) return rc;
-      if (pl.splits > 1 && !a.tickets) {
+      if (ks == 1) launch_rows_fast<true, 1>(pl, c.kloop, a, st);
+      else launch_rows_fast<true, 3>(pl, c.kloop, a, st);
+      rc = launch_status();
+      if (rc == GS_OK && pl.splits > 1 && !a.tickets) {
         launch_reduce(a, pl.splits, 0, st);
         rc = launch_status();
-        if (rc != GS_OK) return rc;
       }
-    }
-  return GS_OK;
+  });
+  return rc;
 }
 
 extern "C" int gs_conv2d_dgrad(const gs_conv_desc* d, const float* dy, const float* w, float* dx,
@@ -118,10 +92,11 @@ static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // partials of the fused slab reduce
 size_t dgrad_bnbwd_part_bytes(const gs_conv_desc* d) {
   if (check_desc(d) != GS_OK || d->stride != 1 || (d->Ci & 3)) return 0;
-  const Plan pl = plan_dgrad(d);
+  const ConvRoute r = route_dgrad(d);
+  const Plan& pl = r.plan;
   const long M = (long)d->N * d->H * d->W;
   if (pl.splits != 1)   // slabs, then the partials of the slab reduce or (in-launch combine) of the tiles
-    return align256(slab_bytes(pl, M, d->Ci)) +
+    return align256(r.need) +
            std::max(bn_reduce_bnbwd_bytes(M, d->Ci), (size_t)2 * d->Ci * pl.tiles_m * sizeof(float));
   return (size_t)2 * d->Ci * pl.tiles_m * sizeof(float);
 }
@@ -149,17 +124,12 @@ int conv2d_dgrad_impl(const gs_conv_desc* d, const float* dy, const float* w, fl
   if (d->x_sh != (int64_t)d->W * d->x_sw || d->x_sn != (int64_t)d->H * d->x_sh) return GS_E_BADARG;
   if (!aligned16(dy) || !aligned16(w) || !aligned16(dx)) return GS_E_ALIGN;
   hipStream_t st = as_stream(stream);
-  {
-    const int ks0 = ksize_tag(d);
-    const size_t sb = (size_t)d->N * d->Ho * d->Wo * d->ldy * sizeof(float);
-    const size_t db = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
-    if (d->stride > 1 && fast_rows_ok(d->Co, ks0, sb, db) && getenv("GS_NO_FAST") == nullptr &&
-        (long)d->N * d->H * d->W * d->x_sw < (1L << 31))
-      return dgrad_strided_fast(d, dy, w, dx, accumulate, workspace, workspace_bytes, st);
-  }
-  const Plan pl = plan_dgrad(d);
+  const ConvRoute r = route_dgrad(d, RouteHints{false, bw ? std::max(bw->ldy, bw->ldact) : 0});
+  if (r.path == PATH_STRIDED_CLASSES)
+    return dgrad_strided_fast(d, dy, w, dx, accumulate, workspace, workspace_bytes, st);
+  const Plan& pl = r.plan;
   const long M = (long)d->N * d->H * d->W;
-  const size_t need = slab_bytes(pl, M, d->Ci);
+  const size_t need = r.need;
   if (need > workspace_bytes || (need && !workspace)) return GS_E_WORKSPACE;
 
   IgemmArgs a{};
@@ -177,23 +147,16 @@ int conv2d_dgrad_impl(const gs_conv_desc* d, const float* dy, const float* w, fl
   a.accumulate = accumulate ? 1 : 0; a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
   a.kh_n = d->KH; a.kw_n = d->KW;
   a.d_tap_h = (long)d->KW * a.d_tap; a.d_tap_w = a.d_tap;
-  const int ks = ksize_tag(d);
-  const size_t src_b = (size_t)d->N * a.s_n * sizeof(float);
-  const size_t dense_b = (size_t)a.taps * a.d_tap * sizeof(float);
-  a.src_bytes = (unsigned)src_b;
-  a.dense_bytes = (unsigned)dense_b;
-  const bool fast = fast_rows_ok(d->Co, ks, src_b, dense_b) && getenv("GS_NO_FAST") == nullptr;
+  const int ks = r.ks;
+  a.src_bytes = (unsigned)r.src_bytes;
+  a.dense_bytes = (unsigned)r.dense_bytes;
+  const bool fast = r.fast;
   static const bool no_bnb = getenv("GS_NO_BNBWD_FUSE") != nullptr;
   bool bnb = false, bnb_split = false;
   // short-K 1x1 data gradients over many rows: the streaming kernel (igemm_stream.h); the fused
   // BatchNorm-backward sums come out as one partial per workgroup row range
-  // (a padded 1x1 has Ho = H + 2 pad: the streaming kernel maps dy row m to dx row m, so it takes
-  // only the unpadded form; the tile kernels handle padding through base_h / base_w)
-  const bool same_rows = d->pad == 0 && d->H == d->Ho && d->W == d->Wo;
-  const StreamPlan sp = (fast && ks == 1 && d->stride == 1 && same_rows)
-                            ? stream_plan(M, d->Ci, d->Co, true, std::max<long>(d->x_sw, bw ? std::max(bw->ldy, bw->ldact) : 0))
-                            : StreamPlan{0, 0, 0, 0, 0};
-  if (sp.ok) {
+  if (r.path == PATH_STREAM) {
+    const StreamPlan& sp = r.stream;
     if (bnbwd_fuse_ok(bw, d, workspace) && !no_bnb &&
         (size_t)2 * d->Ci * sp.row_groups * sizeof(float) <= workspace_bytes) {
       a.bw_y = bw->y; a.bw_ldy = bw->ldy; a.bw_act = bw->act; a.bw_ldact = bw->ldact;
@@ -213,7 +176,7 @@ int conv2d_dgrad_impl(const gs_conv_desc* d, const float* dy, const float* w, fl
   }
   // split-K on the fast row kernels: combined inside the launch (igemm_core.h splitk_publish); the
   // tile's last workgroup then runs the unsplit epilogue, the fused BatchNorm-backward one included
-  if (splitk_combine_ok(pl) && d->stride == 1 && fast && need < (1ull << 32)) {
+  if (r.combine) {
     a.tickets = splitk_tickets(st, (long)pl.tiles_m * pl.tiles_n);
     a.slab_bytes = (unsigned)need;
   }
@@ -240,8 +203,8 @@ int conv2d_dgrad_impl(const gs_conv_desc* d, const float* dy, const float* w, fl
     }
   }
   if (d->stride == 1) {
-    if (fast && ks == 1) launch_rows_fast<true, 1>(pl, a, st);
-    else if (fast && ks == 3) launch_rows_fast<true, 3>(pl, a, st);
+    if (fast && ks == 1) launch_rows_fast<true, 1>(pl, r.kloop, a, st);
+    else if (fast) launch_rows_fast<true, 3>(pl, r.kloop, a, st);
     else if (ks == 1) launch_rows<true, false, false, 1>(pl, a, st);
     else if (ks == 3) launch_rows<true, false, false, 3>(pl, a, st);
     else launch_rows<true, false, false, 0>(pl, a, st);

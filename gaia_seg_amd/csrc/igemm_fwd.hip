@@ -2,28 +2,14 @@
 #include <map>
 #include <mutex>
 #include <vector>
-#include "igemm_core.h"
-#include "igemm_stream.h"
+#include "igemm_route.h"
 
 using namespace gs;
 
-size_t gs_dgrad_strided_slab_bytes(const gs_conv_desc* d);  // igemm_dgrad.hip
-size_t gs_wgrad_slab_bytes(const gs_conv_desc* d);          // igemm_wgrad.hip
-#include "fused_internal.h"
-
 extern "C" size_t gs_conv2d_workspace_bytes(const gs_conv_desc* d) {
   if (check_desc(d) != GS_OK) return 0;
-  size_t b = 0;
-  {
-    const Plan pl = plan_fwd(d);
-    b = std::max(b, slab_bytes(pl, (long)d->N * d->Ho * d->Wo, d->Co));
-  }
-  if (d->x_sc == 1 && (d->Ci & 3) == 0) {
-    const Plan pl = plan_dgrad(d);
-    b = std::max(b, slab_bytes(pl, (long)d->N * d->H * d->W, d->Ci));
-    if (d->stride > 1) b = std::max(b, gs_dgrad_strided_slab_bytes(d));
-  }
-  b = std::max(b, gs_wgrad_slab_bytes(d));
+  size_t b = std::max(route_forward(d).reserve, route_wgrad(d).reserve);
+  if (d->x_sc == 1 && (d->Ci & 3) == 0) b = std::max(b, route_dgrad(d).reserve);
   return b;
 }
 
@@ -91,18 +77,6 @@ unsigned* column_tickets(hipStream_t st, long tiles_m, long tiles_n, int kind) {
   return p ? p + kMaxTickets : nullptr;
 }
 
-// the streaming 1x1 kernel takes a forward when: 1x1, stride 1, no padding, NHWC x with contiguous
-// pixel rows, no bias / addend, and stream_plan() finds a column-block width whose weights fit in LDS
-static StreamPlan stream_fwd_plan(const gs_conv_desc* d, bool fast, const float* bias,
-                                  const float* addend) {
-  StreamPlan none{0, 0, 0, 0, 0};
-  if (!fast || bias || addend || d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0)
-    return none;
-  if (d->x_sh != (int64_t)d->W * d->x_sw || d->x_sn != (int64_t)d->H * d->x_sh) return none;
-  if (d->in_affine && d->Ci > 256) return none;
-  return stream_plan((long)d->N * d->Ho * d->Wo, d->Co, d->Ci, false, d->ldy);
-}
-
 // Forward with the options of the fused conv+BN entry point (fused_layers.hip):
 //   want_stats: the caller wants BatchNorm batch statistics of y.  Without split-K the epilogue
 //     writes per-tile partials to the start of `workspace` (info->mode = 1); with split-K the
@@ -117,11 +91,12 @@ int conv2d_forward_impl(const gs_conv_desc* d, const float* x, const float* w, c
   if (!aligned16(w) || !aligned16(y) || (bias && !aligned16(bias)) || (addend && !aligned16(addend)))
     return GS_E_ALIGN;
   if (addend && ((d->ld_add & 3) || d->ld_add < d->Co)) return GS_E_ALIGN;
-  const bool vec = x_is_vector(d);
+  const ConvRoute r = route_forward(d, RouteHints{bias || addend, 0});
+  const bool vec = r.vec, fast = r.fast;
   if (vec && !aligned16(x)) return GS_E_ALIGN;
-  const Plan pl = plan_fwd(d);
+  const Plan& pl = r.plan;
   const long M = (long)d->N * d->Ho * d->Wo;
-  const size_t need = slab_bytes(pl, M, d->Co);
+  const size_t need = r.need;
   if (need > workspace_bytes || (need && !workspace)) return GS_E_WORKSPACE;
 
   IgemmArgs a{};
@@ -139,21 +114,18 @@ int conv2d_forward_impl(const gs_conv_desc* d, const float* x, const float* w, c
   a.nk_total = pl.nk_total; a.nk_per_split = pl.nk_per_split;
   a.accumulate = 0; a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
   hipStream_t st = as_stream(stream);
-  const int ks = ksize_tag(d);
+  const int ks = r.ks;
   a.kh_n = d->KH; a.kw_n = d->KW;
   a.d_tap_h = (long)d->KW * a.d_tap; a.d_tap_w = a.d_tap;
-  const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
-  const size_t dense_b = (size_t)a.taps * a.d_tap * sizeof(float);
-  a.src_bytes = (unsigned)src_b;
-  a.dense_bytes = (unsigned)dense_b;
-  const bool fast = vec && fast_rows_ok(d->Ci, ks, src_b, dense_b) && getenv("GS_NO_FAST") == nullptr;
+  a.src_bytes = (unsigned)r.src_bytes;
+  a.dense_bytes = (unsigned)r.dense_bytes;
   if (d->in_affine) {
-    if (!conv_in_affine_ok(d) || !fast || pl.bm != 64) return GS_E_BADARG;
+    if (!conv_in_affine_ok(d)) return GS_E_BADARG;
     if (!aligned16(d->in_affine)) return GS_E_ALIGN;
     a.a_coeffs = d->in_affine;
   }
   // the stem: 7x7 stride-2 conv of the 3-channel NCHW image (stem.hip)
-  if (!vec && !bias && !addend && stem_conv_ok(d)) {
+  if (r.path == PATH_STEM) {
     const int tiles = d->N * d->Ho * (d->Wo / 128);
     float* ts = nullptr;
     int mode = 0;
@@ -170,8 +142,8 @@ int conv2d_forward_impl(const gs_conv_desc* d, const float* x, const float* w, c
     return stem_forward(d, x, w, y, ts, nullptr, st);
   }
   // short-K 1x1 convs over many rows: the streaming kernel (igemm_stream.h)
-  const StreamPlan sp = stream_fwd_plan(d, fast, bias, addend);
-  if (sp.ok) {
+  if (r.path == PATH_STREAM) {
+    const StreamPlan& sp = r.stream;
     int mode = 0;
     if (want_stats && info) {
       const size_t part_b = (size_t)3 * d->Co * sp.row_groups * sizeof(float);
@@ -199,7 +171,7 @@ int conv2d_forward_impl(const gs_conv_desc* d, const float* x, const float* w, c
   const size_t part_b = (size_t)3 * d->Co * pl.tiles_m * sizeof(float);
   const size_t part_off = pl.splits > 1 ? ((need + 255) & ~(size_t)255) : 0;
   const bool part_fits = workspace && part_off + part_b <= workspace_bytes && aligned16(workspace);
-  if (splitk_combine_ok(pl) && vec && fast && need < (1ull << 32) && (!stats_ok || part_fits))
+  if (r.combine && (!stats_ok || part_fits))
     a.tickets = splitk_tickets(st, (long)pl.tiles_m * pl.tiles_n);
   a.slab_bytes = (unsigned)need;
   int mode = 0;
@@ -239,9 +211,9 @@ int conv2d_forward_impl(const gs_conv_desc* d, const float* x, const float* w, c
     info->tile_part = a.tile_stats;
   }
   if (!vec) launch_rows<false, false, true, 0>(pl, a, st);
-  else if (fast && ks == 1) launch_rows_fast<false, 1>(pl, a, st);
-  else if (fast && ks == 3 && d->role == GS_CONV_ROLE_BOTTLENECK3X3) launch_rows_fast<false, 3, 1>(pl, a, st);
-  else if (fast && ks == 3) launch_rows_fast<false, 3>(pl, a, st);
+  else if (fast && ks == 1) launch_rows_fast<false, 1>(pl, r.kloop, a, st);
+  else if (fast && d->role == GS_CONV_ROLE_BOTTLENECK3X3) launch_rows_fast<false, 3, 1>(pl, r.kloop, a, st);
+  else if (fast) launch_rows_fast<false, 3>(pl, r.kloop, a, st);
   else if (ks == 1) launch_rows<false, false, false, 1>(pl, a, st);
   else if (ks == 3) launch_rows<false, false, false, 3>(pl, a, st);
   else launch_rows<false, false, false, 0>(pl, a, st);
@@ -281,72 +253,16 @@ extern "C" int gs_debug_query_plan(int32_t M, int32_t N, int32_t K, int32_t max_
   return GS_OK;
 }
 
-// Test hook: what the three conv entry points would launch for this descriptor (mirrors their
-// dispatch; tests/test_hip_ops_gpu.py asserts it equals gs_debug_last_conv_launch after real calls).
+// Test hook: what the three conv entry points would launch for this descriptor -- the route they
+// take (tests/test_hip_ops_gpu.py asserts it equals gs_debug_last_conv_launch after real calls).
 extern "C" int gs_debug_query_conv_launch(const gs_conv_desc* d, int32_t op, gs_debug_launch* out) {
   if (!out) return GS_E_NULL;
   int rc = check_desc(d);
   if (rc != GS_OK) return rc;
   if (op < GS_OP_FORWARD || op > GS_OP_WGRAD) return GS_E_BADARG;
-  const int ks = ksize_tag(d);
-  const bool vec = x_is_vector(d);
-  const bool no_fast = getenv("GS_NO_FAST") != nullptr;
-  const size_t w_bytes = (size_t)d->KH * d->KW * d->Ci_max * d->Co_ld * sizeof(float);
-  Plan pl{};
-  int kloop = GS_KLOOP_GENERIC;
-  const bool aff = d->in_affine != nullptr && op != GS_OP_DGRAD;
-  if (!vec && (op == GS_OP_FORWARD || (op == GS_OP_WGRAD && stem_wgrad_on())) && stem_conv_ok(d)) {
-    // stem.hip: 128-row tiles, its own loops
-    const int tiles = d->N * d->Ho * (d->Wo / 128);
-    if (op == GS_OP_FORWARD) pl = Plan{128, d->Co, 1, 37, 37, tiles, 1};
-    else {
-      const int groups = (int)(stem_wgrad_slab_bytes(d) / ((size_t)147 * d->Co * sizeof(float)));
-      pl = Plan{128, d->Co, groups, tiles, (int)ceil_div(tiles, groups), 1, 1};
-    }
-    *out = gs_debug_launch{op, GS_KLOOP_GENERIC, pl.bm, pl.bn, pl.splits, pl.nk_per_split, 0, 0};
-    return GS_OK;
-  }
-  if (op == GS_OP_FORWARD) {
-    pl = plan_fwd(d);
-    const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
-    if (vec && fast_rows_ok(d->Ci, ks, src_b, w_bytes) && !no_fast) {
-      kloop = rows_fast_kloop<false>(pl, aff, ks);
-      const StreamPlan sp = stream_fwd_plan(d, true, nullptr, nullptr);
-      if (sp.ok) {
-        kloop = GS_KLOOP_STREAM;
-        pl = Plan{kStreamBM, sp.bnw, 1, (int)ceil_div(d->Ci, BK), (int)ceil_div(d->Ci, BK), sp.row_groups, sp.ncb};
-      }
-    }
-  } else if (op == GS_OP_DGRAD) {
-    const size_t dy_b = (size_t)d->N * d->Ho * d->Wo * d->ldy * sizeof(float);
-    const bool fast = fast_rows_ok(d->Co, ks, dy_b, w_bytes) && !no_fast;
-    if (d->stride > 1 && fast && (long)d->N * d->H * d->W * d->x_sw < (1L << 31)) {
-      const int s = d->stride;
-      const TapAxis th = tap_axis(0, d->pad, d->dil, s, d->KH), tw = tap_axis(0, d->pad, d->dil, s, d->KW);
-      const long Mc = (long)d->N * class_len(d->H, s, 0) * class_len(d->W, s, 0);
-      pl = f16_dgrad_plan(make_plan((int)Mc, d->Ci, std::max(1, th.n * tw.n) * d->Co, true), d->Ci);
-      kloop = rows_fast_kloop<true>(pl, false);
-    } else {
-      pl = plan_dgrad(d);
-      if (d->stride == 1 && fast) {
-        kloop = rows_fast_kloop<true>(pl, false);
-        const bool same_rows = d->pad == 0 && d->H == d->Ho && d->W == d->Wo;
-        const StreamPlan sp = (ks == 1 && same_rows)
-                                  ? stream_plan((long)d->N * d->H * d->W, d->Ci, d->Co, true, d->x_sw)
-                                  : StreamPlan{0, 0, 0, 0, 0};
-        if (sp.ok && d->x_sc == 1) {
-          kloop = GS_KLOOP_STREAM;
-          pl = Plan{kStreamBM, sp.bnw, 1, (int)ceil_div(d->Co, BK), (int)ceil_div(d->Co, BK), sp.row_groups, sp.ncb};
-        }
-      }
-    }
-  } else {
-    pl = plan_wgrad(d);
-    const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
-    const size_t dy_b = (size_t)d->N * d->Ho * d->Wo * d->ldy * sizeof(float);
-    if (vec && src_b < (1ull << 31) && dy_b < (1ull << 31) && !no_fast)
-      kloop = pair_loop_ok(pl) ? GS_KLOOP_FP32_PAIRS : GS_KLOOP_FP32;
-  }
-  *out = gs_debug_launch{op, kloop, pl.bm, pl.bn, pl.splits, pl.nk_per_split, aff ? 1 : 0, 0};
+  const ConvRoute r = op == GS_OP_FORWARD ? route_forward(d)
+                                          : (op == GS_OP_DGRAD ? route_dgrad(d) : route_wgrad(d));
+  *out = gs_debug_launch{op, r.kloop, r.shown.bm, r.shown.bn, r.shown.splits, r.shown.nk_per_split,
+                         r.aff ? 1 : 0, 0};
   return GS_OK;
 }

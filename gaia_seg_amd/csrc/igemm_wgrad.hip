@@ -1,14 +1,7 @@
 // DynConv2d weight gradient (implicit GEMM over pixels, split-K) — see igemm_core.h
-#include "igemm_core.h"
-#include "fused_internal.h"
+#include "igemm_route.h"
 
 using namespace gs;
-
-// slab bytes of the weight-gradient path gs_conv2d_wgrad takes for this descriptor
-size_t gs_wgrad_slab_bytes(const gs_conv_desc* d) {
-  const Plan pl = plan_wgrad(d);
-  return std::max(slab_bytes(pl, (long)d->KH * d->KW * d->Ci, d->Co), stem_wgrad_slab_bytes(d));
-}
 
 extern "C" int gs_conv2d_wgrad(const gs_conv_desc* d, const float* x, const float* dy, float* dw,
                                void* workspace, size_t workspace_bytes, void* stream) {
@@ -16,13 +9,14 @@ extern "C" int gs_conv2d_wgrad(const gs_conv_desc* d, const float* x, const floa
   if (rc != GS_OK) return rc;
   if (!x || !dy || !dw) return GS_E_NULL;
   if (!aligned16(dy) || !aligned16(dw)) return GS_E_ALIGN;
-  const bool vec = x_is_vector(d);
+  const ConvRoute r = route_wgrad(d);
+  const bool vec = r.vec, fast = r.fast;
   if (vec && !aligned16(x)) return GS_E_ALIGN;
-  if (!vec && stem_wgrad_on() && stem_conv_ok(d))   // the stem: stem.hip
+  if (r.path == PATH_STEM)   // the stem: stem.hip
     return stem_wgrad(d, x, dy, dw, workspace, workspace_bytes, as_stream(stream));
-  const Plan pl = plan_wgrad(d);
+  const Plan& pl = r.plan;
   const long M = (long)d->KH * d->KW * d->Ci;
-  const size_t need = slab_bytes(pl, M, d->Co);
+  const size_t need = r.need;
   if (need > workspace_bytes || (need && !workspace)) return GS_E_WORKSPACE;
 
   IgemmArgs a{};
@@ -39,21 +33,17 @@ extern "C" int gs_conv2d_wgrad(const gs_conv_desc* d, const float* x, const floa
   a.nk_total = pl.nk_total; a.nk_per_split = pl.nk_per_split;
   a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
   hipStream_t st = as_stream(stream);
-  const int ks = ksize_tag(d);
-  const size_t src_b = (size_t)d->N * d->x_sn * sizeof(float);
-  const size_t dense_b = (size_t)a.npix * d->ldy * sizeof(float);
-  a.src_bytes = (unsigned)src_b;
-  a.dense_bytes = (unsigned)dense_b;
-  const bool fast = vec && src_b < (1ull << 31) && dense_b < (1ull << 31) &&
-                    getenv("GS_NO_FAST") == nullptr;
+  const int ks = r.ks;
+  a.src_bytes = (unsigned)r.src_bytes;
+  a.dense_bytes = (unsigned)r.dense_bytes;
   if (d->in_affine) {
     if (!conv_in_affine_ok(d) || !fast || pl.bm != 64 || (ks != 1 && ks != 3)) return GS_E_BADARG;
     if (!aligned16(d->in_affine)) return GS_E_ALIGN;
     a.a_coeffs = d->in_affine;
   }
-  if (fast && ks == 1) launch_wgrad_fast<1>(pl, a, st);
-  else if (fast && ks == 3) launch_wgrad_fast<3>(pl, a, st);
-  else if (fast) launch_wgrad_fast<0>(pl, a, st);
+  if (fast && ks == 1) launch_wgrad_fast<1>(pl, r.kloop, a, st);
+  else if (fast && ks == 3) launch_wgrad_fast<3>(pl, r.kloop, a, st);
+  else if (fast) launch_wgrad_fast<0>(pl, r.kloop, a, st);
   else if (!vec) launch_wgrad<true, 0>(pl, a, st);
   else if (ks == 1) launch_wgrad<false, 1>(pl, a, st);
   else if (ks == 3) launch_wgrad<false, 3>(pl, a, st);

@@ -78,7 +78,7 @@ typedef struct gs_conv_desc {
 int gs_conv2d_in_affine_supported(const gs_conv_desc* d);
 /* role = GS_CONV_ROLE_BOTTLENECK3X3 marks conv2 of DynamicBottleneck (SURVEY.md K3,
  * gaiaseg/models/utils/dynamic_res_layer.py:96-106): the forward dispatches an identically compiled
- * but separately NAMED kernel instantiation (igemm_rows_fast_kernel<..., 1> and
+ * but separately NAMED kernel instantiation (igemm_rows_fast_kernel<..., ROLE = 1, ...> and
  * splitk_reduce_kernel<false, 1>), so a rocprofv3 kernel trace reports the headline kernel of
  * bench.py's roofline on its own rows. */
 #define GS_CONV_ROLE_GENERIC 0

@@ -1,4 +1,4 @@
-"""Operator-level parity of the bf16x3 data-gradient K loop (csrc/igemm_core.h: x3_k_loop), the default
+"""Operator-level parity of the bf16x3 data-gradient K loop (csrc/igemm_core.h: packed_k_loop<PackBf16x3>), the default
 contraction of every stride-1 DynConv2d data gradient whose grid fills the chip
 (gaiaseg/models/utils/dynamic_res_layer.py:105-125: the autograd dgrad of conv1 / conv2 / conv3).
 

@@ -1,4 +1,4 @@
-"""fp16 training on the MI355X: the f16 data-gradient K loop (csrc/igemm_core.h f16_k_loop<BFWD=false>,
+"""fp16 training on the MI355X: the f16 data-gradient K loop (csrc/igemm_core.h packed_k_loop<PackF16, ..., BFWD=false>,
 gs_set_train_precision(1)) at operator level, and the training step with fp16 operands and a static
 loss scale (core/runner.py Fp16ArenaOptimizerHook).
 

@@ -1,4 +1,4 @@
-"""The fp16 forward K loop (csrc/igemm_core.h f16_k_loop, gs_set_forward_precision(1)) at operator
+"""The fp16 forward K loop (csrc/igemm_core.h packed_k_loop<PackF16>, gs_set_forward_precision(1)) at operator
 level, its isolation from training, and a whole subnet's eval logits against an fp16-rounded oracle.
 
 Operator witness: an fp64 convolution of the operands rounded to fp16 (round to nearest even; the

@@ -1,4 +1,4 @@
-"""Operator-level parity of the FORWARD on the bf16x3 K loop (csrc/igemm_core.h x3_k_loop<BFWD>: the
+"""Operator-level parity of the FORWARD on the bf16x3 K loop (csrc/igemm_core.h packed_k_loop<PackBf16x3, ..., BFWD>: the
 [k][n] weights are staged one k row per thread and step, the two steps of a 32-channel slab
 interleaved so that a column's (step 1, step 2) pair is one 32-bit LDS store per bf16 piece) --
 DynConv2d forward of the bottleneck conv2 / conv1 / conv3 and the head convs

@@ -14,6 +14,7 @@ import csv
 import gzip
 import json
 import os
+import re
 import sys
 from collections import defaultdict
 
@@ -71,7 +72,8 @@ def hbm(fetch, write, out):
             name = d["name"]
             if counter not in d:
                 continue
-            if "igemm_rows_fast_kernel" in name and ", 0, 1, true, " in name:
+            # <BM, BN, BTRANS, KS, ROLE, KLOOP, AFF, SK, TIMELINE>: the forward 3x3 with ROLE = 1
+            if re.search(r"igemm_rows_fast_kernel<\d+, \d+, false, 3, 1, ", name):
                 conv += d[counter]
                 n_conv += 1
             elif "splitk_reduce_kernel<false, 1>" in name or ("splitk_reduce_stats_kernel<1>" in name):
@@ -83,7 +85,7 @@ def hbm(fetch, write, out):
     assert n1 == n2 and n1 > 0, (n1, n2)
     per_launch = lambda v: v * 1024.0 / n1
     res = {
-        "kernel": "igemm_rows_fast_kernel<64,BN,false,3,0,1,...> (split-K slabs combined inside the launch; with "
+        "kernel": "igemm_rows_fast_kernel<64,BN,false,3,1,...> (split-K slabs combined inside the launch; with "
                   "GS_SPLITK_INKERNEL=0 + its reduce launch splitk_reduce_kernel<false,1> / splitk_reduce_stats_kernel<1>): "
                   "bottleneck conv2 forward, sampled subnet mix of bench.py, bs 2, 512x1024",
         "k3_launches": n1, "reduce_launches": nr1,

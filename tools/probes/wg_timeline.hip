@@ -1,4 +1,4 @@
-// Per-workgroup timeline of the fast forward conv kernel (diagnostic build ABL = 9): entry, start of
+// Per-workgroup timeline of the fast forward conv kernel (diagnostic build TIMELINE): entry, start of
 // the K loop, loop length, end of the epilogue -- 100 MHz s_memrealtime stamps per workgroup.
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +12,7 @@ using namespace gs;
 // histogram comes from HW_REG_HW_ID / HW_REG_XCC_ID read by every wave of the stamped build.
 template <int KS, bool PAIR = false>
 void run(const char* name, int H, int W, int Ci, int Co, int pad = 0) {
+  constexpr int KLOOP = PAIR ? GS_KLOOP_FP32_PAIRS : GS_KLOOP_FP32;
   const int N = 2; const long M = (long)N * H * W;
   float *x, *w, *y; unsigned long long* dbg;
   CK(hipMalloc(&x, M * Ci * 4)); CK(hipMalloc(&w, (long)KS * KS * Ci * Co * 4)); CK(hipMalloc(&y, M * Co * 4));
@@ -30,14 +31,14 @@ void run(const char* name, int H, int W, int Ci, int Co, int pad = 0) {
   CK(hipMalloc(&dbg, (long)tiles * 4 * 64)); CK(hipMemset(dbg, 0, (long)tiles * 4 * 64));
   // timing of the production build
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((igemm_rows_fast_kernel<64, 64, false, KS, 0, 0, true, PAIR, false>), dim3(tiles), dim3(256), pad, 0, a);
+  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((igemm_rows_fast_kernel<64, 64, false, KS, 0, KLOOP, false, false>), dim3(tiles), dim3(256), pad, 0, a);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(e0));
-  for (int i = 0; i < 20; ++i) hipLaunchKernelGGL((igemm_rows_fast_kernel<64, 64, false, KS, 0, 0, true, PAIR, false>), dim3(tiles), dim3(256), pad, 0, a);
+  for (int i = 0; i < 20; ++i) hipLaunchKernelGGL((igemm_rows_fast_kernel<64, 64, false, KS, 0, KLOOP, false, false>), dim3(tiles), dim3(256), pad, 0, a);
   CK(hipEventRecord(e1)); CK(hipDeviceSynchronize());
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));
   IgemmArgs b = a; b.slab = reinterpret_cast<float*>(dbg);
-  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((igemm_rows_fast_kernel<64, 64, false, KS, 9, 0, true, PAIR, false>), dim3(tiles), dim3(256), pad, 0, b);
+  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((igemm_rows_fast_kernel<64, 64, false, KS, 0, KLOOP, false, false, true>), dim3(tiles), dim3(256), pad, 0, b);
   CK(hipDeviceSynchronize());
   std::vector<unsigned long long> h((size_t)tiles * 4 * 8);
   CK(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));

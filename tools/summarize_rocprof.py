@@ -23,9 +23,9 @@ def short(name):
 
 
 def group(name):
-    if "igemm_rows_fast_kernel" in name:     # <BM, BN, BTRANS, KS, ABL, ROLE, PIPE, PAIR>
+    if "igemm_rows_fast_kernel" in name:     # <BM, BN, BTRANS, KS, ROLE, KLOOP, AFF, SK, TIMELINE>
         t = name.split("<")[1].split(">")[0].split(", ")
-        if len(t) > 5 and t[5] == "1":
+        if len(t) > 4 and t[4] == "1":
             return K3
         kind = "conv dgrad" if t[2] == "true" else "conv forward"
         return "%s %s" % (kind, {"1": "1x1", "3": "3x3"}.get(t[3], "other"))
