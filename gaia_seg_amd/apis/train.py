@@ -57,7 +57,11 @@ def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_cl
     (gaiaseg/apis/train.py:74-84, tools/train_supernet.py:197) for this path: a config dict naming a
     registered file-backed dataset (``CityscapesDataset19`` of the in-tree configs, ``CityscapesDataset``,
     ``CustomDataset``) becomes a loader whose transforms run on the GPU; ``SyntheticSegDataset`` gives
-    the seeded synthetic batches; anything else that is already an iterable of batches passes through."""
+    the seeded synthetic batches; anything else that is already an iterable of batches passes through
+    (a list of batches -- dicts with an ``img`` and no ``type`` -- included)."""
+    if isinstance(dataset_cfg, (list, tuple)) and dataset_cfg and all(
+            isinstance(b, dict) and "img" in b and "type" not in b for b in dataset_cfg):
+        return dataset_cfg
     if isinstance(dataset_cfg, (list, tuple)):
         if len(dataset_cfg) != 1:
             raise NotImplementedError("concatenated datasets (%d entries)" % len(dataset_cfg))
@@ -101,12 +105,20 @@ def optimizer_hook(optimizer_config):
     return ArenaOptimizerHook()
 
 
-def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed=False,
-                    validate=False, timestamp=None, meta=None, logger=None):
-    opt_hook = optimizer_hook(cfg.get("optimizer_config"))
-    if cfg.get("use_distillation", False) and isinstance(opt_hook, Fp16ArenaOptimizerHook):
-        raise ValueError("use_distillation with fp16 training (optimizer_config type "
-                         "'Fp16OptimizerHook') is not supported")
+def check_lr_policy(cfg):
+    """``cfg.lr_config`` -> (policy, its other keys); anything but 'poly' and 'fixed' is refused."""
+    lrc = dict(cfg.get("lr_config") or dict(policy="fixed"))
+    policy = lrc.pop("policy", "fixed")
+    if policy not in ("poly", "fixed"):
+        raise NotImplementedError("lr_config.policy=%r: only 'poly' and 'fixed'" % (policy,))
+    return policy, lrc
+
+
+def prepare_training(model, cfg):
+    """The part of a training set-up that belongs to the MODEL, not to a run: the model on the
+    device, its parameter arena (after the DDP wrap-time broadcast, gaiaseg/apis/train.py:88-96), the
+    gradient reducer over it and the parameter groups of ``cfg.optimizer``.  train_segmentor makes
+    one per call; apis/finetune.py makes one for a whole model space."""
     device = torch.device("cuda", torch.cuda.current_device())
     model = model.to(device)
     arena = ParamArena(model)
@@ -116,6 +128,21 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
     # optimizer keys the arena SGD does not implement are errors, and paramwise_cfg becomes parameter
     # groups (core/optimizer.py; None = the one-group path)
     param_groups = build_param_groups(model, cfg.optimizer)
+    return model, arena, reducer, param_groups
+
+
+def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler, dataset, cfg,
+                 opt_hook, validate=False, meta=None, logger=None, val_loader=None,
+                 eval_num_batches=None, checkpoints=True, before_run=None):
+    """The body of train_segmentor on a prepared (model, arena, reducer, parameter groups): build the
+    runner, register the hooks ``cfg`` names, load ``cfg.resume_from`` / ``cfg.load_from``, apply
+    ``caliberate_bn.reset_stats``, build the train loader and run.  ``dataset`` is a dataset config
+    or an iterable of batches (a loader built earlier passes through build_dataloader untouched).
+    ``val_loader`` / ``eval_num_batches``: a prepared loader and batch count for the CrossArchEvalHook
+    instead of the ones ``cfg`` describes.  ``checkpoints=False`` registers no CheckpointHook and
+    reads no checkpoint (the caller owns the weights).  ``before_run(runner)`` is called right before
+    ``runner.run``."""
+    device = arena.device
     opt = dict(cfg.optimizer)
     lr = opt["lr"]
     lr_scaler = cfg.get("lr_scaler")      # gaiaseg/apis/train.py:103-113
@@ -136,14 +163,11 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
         runner.register_hook(SandwichHook(train_sampler, cfg.get("distill_cfg")))
     elif cfg.get("manipulate_arch", True):  # :142-146
         runner.register_hook(ManipulateArchHook(train_sampler))
-    lrc = dict(cfg.get("lr_config") or dict(policy="fixed"))
-    policy = lrc.pop("policy", "fixed")
-    if policy not in ("poly", "fixed"):
-        raise NotImplementedError("lr_config.policy=%r: only 'poly' and 'fixed'" % (policy,))
+    policy, lrc = check_lr_policy(cfg)
     runner.register_hook(PolyLrUpdaterHook(**lrc) if policy == "poly" else FixedLrUpdaterHook(**lrc))
     runner.register_hook(opt_hook)
     ck = cfg.get("checkpoint_config")
-    if ck:
+    if ck and checkpoints:
         runner.register_hook(CheckpointHook(**dict(ck)))
     lg = cfg.get("log_config")
     if lg:
@@ -152,23 +176,38 @@ def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed
         # gaiaseg/apis/train.py:150-170: (Dist)CrossArchEvalHook over the val anchors
         from ..core.evaluation import CrossArchEvalHook
         ev = dict(cfg.evaluation)
-        val_cfg = cfg.data.get("val") or cfg.data["train"]
-        val_loader = build_dataloader(val_cfg, cfg.data["samples_per_gpu"], seed=12345,
-                                      device=device, train=cfg.data.get("val") is None,
-                                      workers_per_gpu=cfg.data.get("workers_per_gpu", 2),
-                                      device_cache_gb=cfg.data.get("device_cache_gb"))
+        if val_loader is None:
+            val_cfg = cfg.data.get("val") or cfg.data["train"]
+            val_loader = build_dataloader(val_cfg, cfg.data["samples_per_gpu"], seed=12345,
+                                          device=device, train=cfg.data.get("val") is None,
+                                          workers_per_gpu=cfg.data.get("workers_per_gpu", 2),
+                                          device_cache_gb=cfg.data.get("device_cache_gb"))
         runner.register_hook(CrossArchEvalHook(val_loader, val_sampler,
                                                interval=ev.get("interval", 8000),
-                                               num_batches=ev.get("num_batches", 4),
+                                               num_batches=eval_num_batches or ev.get("num_batches", 4),
                                                num_classes=model.num_classes, logger=logger))
-    if cfg.get("resume_from"):
-        runner.resume(cfg.resume_from)
-    elif cfg.get("load_from"):
-        runner.load_checkpoint(cfg.load_from)
+    if checkpoints:
+        if cfg.get("resume_from"):
+            runner.resume(cfg.resume_from)
+        elif cfg.get("load_from"):
+            runner.load_checkpoint(cfg.load_from)
     from .test import apply_bn_calibration
     apply_bn_calibration(model, cfg.get("caliberate_bn"), "train")   # gaiaseg/apis/train.py:177-184
     loader = build_dataloader(dataset, cfg.data["samples_per_gpu"], seed=cfg.get("seed") or 0,
                               device=device, workers_per_gpu=cfg.data.get("workers_per_gpu", 2),
                               device_cache_gb=cfg.data.get("device_cache_gb"))
+    if before_run is not None:
+        before_run(runner)
     runner.run([loader], cfg.get("workflow", [("train", 1)]))
     return runner
+
+
+def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed=False,
+                    validate=False, timestamp=None, meta=None, logger=None):
+    opt_hook = optimizer_hook(cfg.get("optimizer_config"))
+    if cfg.get("use_distillation", False) and isinstance(opt_hook, Fp16ArenaOptimizerHook):
+        raise ValueError("use_distillation with fp16 training (optimizer_config type "
+                         "'Fp16OptimizerHook') is not supported")
+    model, arena, reducer, param_groups = prepare_training(model, cfg)
+    return run_training(model, arena, reducer, param_groups, train_sampler, val_sampler, dataset, cfg,
+                        opt_hook, validate=validate, meta=meta, logger=logger)

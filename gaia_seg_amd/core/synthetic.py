@@ -30,6 +30,10 @@ class SyntheticLoader:
     def __iter__(self):
         return self
 
+    def restart(self):
+        """Back to the first batch (apis/finetune.py: every subnet trains on the same stream)."""
+        self.i = 0
+
     def __next__(self):
         b = self.batches[self.i % len(self.batches)]
         self.i += 1

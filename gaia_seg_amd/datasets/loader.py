@@ -78,10 +78,16 @@ class _Prefetcher:
         self.fill(index_iter)
         return sample
 
-    def close(self):
+    def drop_pending(self):
+        """Forget what was asked for ahead of time (the index stream is about to change); samples
+        already decoded onto the device stay cached."""
         for f in self.pending:
-            f.cancel()
+            if hasattr(f, "cancel"):
+                f.cancel()
         self.pending.clear()
+
+    def close(self):
+        self.drop_pending()
         self.pool.shutdown(wait=False)
 
 
@@ -97,7 +103,8 @@ class FileBatchLoader:
         if len(epoch_indices(len(dataset), 0, self.seed, rank, world, shuffle)) < self.bs:
             raise ValueError("%d samples over %d rank(s) give less than one batch of %d"
                              % (len(dataset), world, self.bs))
-        self.pipeline = GpuTrainPipeline(seed=self.seed * 1000003 + rank * 1009, device=device,
+        self._pipeline_seed = self.seed * 1000003 + rank * 1009
+        self.pipeline = GpuTrainPipeline(seed=self._pipeline_seed, device=device,
                                          src_is_rgb=True, ignore_index=dataset.ignore_index,
                                          **pipeline_kwargs)
         self.epoch = 0
@@ -114,6 +121,15 @@ class FileBatchLoader:
 
     def __iter__(self):
         return self
+
+    def restart(self):
+        """The stream of batches from its beginning: epoch 0 of the seed and the augmentation draws
+        of a fresh loader.  The device cache of decoded samples is kept (apis/finetune.py restarts
+        the data for every subnet; only the first one pays for decoding)."""
+        self._pre.drop_pending()
+        self.epoch = 0
+        self._indices = self._index_stream()
+        self.pipeline.rng.seed(self._pipeline_seed)
 
     def __next__(self):
         samples = [self._pre.get(self._indices) for _ in range(self.bs)]
