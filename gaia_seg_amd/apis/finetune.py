@@ -16,7 +16,8 @@ import torch
 
 from ..core import dist as gdist
 from ..core.dynamic import fold_dict
-from ..core.model_space import _listify, build_model_sampler
+from ..core.input_shape import INPUT_SHAPE_KEY
+from ..core.model_space import _listify, build_model_sampler, parse_input_shape
 from .train import (build_dataloader, check_lr_policy, optimizer_hook, prepare_training,
                     run_training, set_random_seed)
 
@@ -51,6 +52,10 @@ def check_finetune_cfg(cfg, metas):
     if not metas:
         raise ValueError("fast-finetune: no subnet to finetune (empty metas)")
     optimizer_hook(cfg.get("optimizer_config"))   # grad_clip / dynamic loss scale: refused here
+    if cfg.get("apply_input_shape", False):          # a scale no batch can take: refused here
+        for meta in metas:
+            if meta.get(INPUT_SHAPE_KEY) is not None:
+                parse_input_shape(meta[INPUT_SHAPE_KEY])
     check_lr_policy(cfg)
 
 
@@ -120,8 +125,9 @@ def finetune_model_space(model, metas, cfg, train_data, val_loader, num_batches,
     restore S0, ``set_random_seed(seed)`` and restart the train data, train ``cfg.runner.max_iters``
     iterations exactly as train_segmentor trains the anchor ``{'name': <name>, **meta}`` (same
     hooks from the same config keys; no CheckpointHook, no checkpoint read), evaluate in eval mode
-    under the subnet's arch, and emit the row (finetune_row).  ``on_subnet(row, model)`` runs while the
-    model still holds the finetuned weights.  Afterwards the model is S0 again, with the arch, the
+    under the subnet's arch, and emit the row (finetune_row).  With ``cfg.apply_input_shape`` a row
+    that carries ``data.input_shape`` is trained and evaluated at that size.
+    ``on_subnet(row, model)`` runs while the model still holds the finetuned weights.  Afterwards the model is S0 again, with the arch, the
     training mode and the fp16_enabled flags it came with.
 
     ``optimizer.lr = 0`` makes it a calibration-only run: no parameter moves, the BatchNorm running
@@ -133,6 +139,7 @@ def finetune_model_space(model, metas, cfg, train_data, val_loader, num_batches,
     check_finetune_cfg(cfg, metas)
     log = (logger.info if logger is not None else print) if gdist.rank() == 0 else (lambda msg: None)
 
+    apply_input_shape = bool(cfg.get("apply_input_shape", False))
     model, arena, reducer, param_groups = prepare_training(model, cfg)
     snap = SupernetSnapshot(model, arena)
     train_loader = build_dataloader(train_data, cfg.data["samples_per_gpu"], seed=cfg.get("seed") or 0,
@@ -167,7 +174,8 @@ def finetune_model_space(model, metas, cfg, train_data, val_loader, num_batches,
             t1 = time.perf_counter()
             model.eval()
             model.manipulate_arch(fold_dict(anchor)["arch"])
-            res = evaluate_model(model, val_loader, num_batches, model.num_classes)
+            res = evaluate_model(model, val_loader, num_batches, model.num_classes,
+                                 input_shape=anchor.get(INPUT_SHAPE_KEY) if apply_input_shape else None)
             t2 = time.perf_counter()
             row = finetune_row(meta, res, metric_tag)
             rows.append(row)

@@ -85,7 +85,7 @@ def multi_gpu_test(model, data_loader, size=None, **kw):
 
 
 def test_model_space(model, loader, metas, num_batches, num_classes, ignore_index=255,
-                     calib_cfg=None, metric_tag="direct", logger=None):
+                     calib_cfg=None, metric_tag="direct", logger=None, apply_input_shape=None):
     """Evaluate every subnet of a model space (the loop of the reference's tools/test_supernet.py).
 
     For each flat meta: ``manipulate_arch`` with its arch, ``apply_bn_calibration(.., 'test')`` with
@@ -93,15 +93,27 @@ def test_model_space(model, loader, metas, num_batches, num_classes, ignore_inde
     over ``num_batches`` batches of ``loader`` (on-device confusion matrix, one all-reduce when
     distributed: every rank returns the same rows).  Returns one row per meta: the meta (other
     metric tags included) plus ``metric.<tag>.mIoU`` / ``.mAcc`` / ``.aAcc``.  The model's
-    ``fp16_enabled`` (core.fp16_utils.wrap_fp16_model) decides the conv precision."""
+    ``fp16_enabled`` (core.fp16_utils.wrap_fp16_model) decides the conv precision.
+    ``apply_input_shape``: a row that carries ``data.input_shape`` is evaluated at that size
+    (DESIGN.md section 20); without it the column is carried, not applied.  None (the default, what
+    tools/test_supernet.py passes) reads the top-level ``apply_input_shape`` of the config the model
+    was built from (``model.top_cfg``, models/builder.py)."""
     from ..core.dynamic import fold_dict
     from ..core.evaluation import evaluate_model
-    from ..core.model_space import _listify
+    from ..core.input_shape import INPUT_SHAPE_KEY
+    from ..core.model_space import _listify, parse_input_shape
+    if apply_input_shape is None:
+        apply_input_shape = bool((getattr(model, "top_cfg", None) or {}).get("apply_input_shape", False))
+    if apply_input_shape:      # a bad value is refused before the first subnet is evaluated
+        for meta in metas:
+            if meta.get(INPUT_SHAPE_KEY) is not None:
+                parse_input_shape(meta[INPUT_SHAPE_KEY])
     apply_bn_calibration(model, calib_cfg, "test")
     rows = []
     for i, meta in enumerate(metas):
         model.manipulate_arch(_listify(fold_dict(meta).get("arch", {})))
-        res = evaluate_model(model, loader, num_batches, num_classes, ignore_index)
+        res = evaluate_model(model, loader, num_batches, num_classes, ignore_index,
+                             input_shape=meta.get(INPUT_SHAPE_KEY) if apply_input_shape else None)
         row = dict(meta)
         for k in ("mIoU", "mAcc", "aAcc"):
             row["metric.%s.%s" % (metric_tag, k)] = res[k]

@@ -23,7 +23,8 @@ from ..core.optimizer import build_param_groups
 from ..core.param_arena import ParamArena
 from ..core.runner import (ArenaOptimizerHook, CheckpointHook, FixedLrUpdaterHook,
                            Fp16ArenaOptimizerHook, IterBasedRunner, ManipulateArchHook,
-                           PolyLrUpdaterHook, SandwichHook, TextLoggerHook, check_sandwich_model)
+                           PolyLrUpdaterHook, SANDWICH_INPUT_SHAPE, SandwichHook, TextLoggerHook,
+                           check_sandwich_model)
 from ..core.synthetic import SyntheticLoader
 
 
@@ -114,6 +115,16 @@ def check_lr_policy(cfg):
     return policy, lrc
 
 
+def check_input_shape_cfg(cfg):
+    """``apply_input_shape`` (elastic input resolution): the flag's value, after
+    refusing what it does not combine with (in-place distillation: teacher and students at different
+    resolutions are out of scope)."""
+    apply = bool(cfg.get("apply_input_shape", False))
+    if apply and cfg.get("use_distillation", False):
+        raise ValueError(SANDWICH_INPUT_SHAPE)
+    return apply
+
+
 def prepare_training(model, cfg):
     """The part of a training set-up that belongs to the MODEL, not to a run: the model on the
     device, its parameter arena (after the DDP wrap-time broadcast, gaiaseg/apis/train.py:88-96), the
@@ -143,6 +154,7 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
     reads no checkpoint (the caller owns the weights).  ``before_run(runner)`` is called right before
     ``runner.run``."""
     device = arena.device
+    apply_input_shape = check_input_shape_cfg(cfg)
     opt = dict(cfg.optimizer)
     lr = opt["lr"]
     lr_scaler = cfg.get("lr_scaler")      # gaiaseg/apis/train.py:103-113
@@ -155,7 +167,8 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
     runner = IterBasedRunner(model, arena, reducer, base_lr=lr, momentum=opt.get("momentum", 0.0),
                              weight_decay=opt.get("weight_decay", 0.0),
                              max_iters=cfg.runner["max_iters"], work_dir=cfg.get("work_dir"),
-                             logger=logger, meta=meta, param_groups=param_groups)
+                             logger=logger, meta=meta, param_groups=param_groups,
+                             apply_input_shape=apply_input_shape)
     if cfg.get("use_distillation", False):
         # the sandwich iteration takes the place of the one-subnet draw (core/runner.py SandwichHook);
         # train_sampler is the concat of sandwich_train_sampler(cfg)
@@ -185,7 +198,8 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
         runner.register_hook(CrossArchEvalHook(val_loader, val_sampler,
                                                interval=ev.get("interval", 8000),
                                                num_batches=eval_num_batches or ev.get("num_batches", 4),
-                                               num_classes=model.num_classes, logger=logger))
+                                               num_classes=model.num_classes, logger=logger,
+                                               apply_input_shape=apply_input_shape))
     if checkpoints:
         if cfg.get("resume_from"):
             runner.resume(cfg.resume_from)
@@ -205,6 +219,7 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
 def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed=False,
                     validate=False, timestamp=None, meta=None, logger=None):
     opt_hook = optimizer_hook(cfg.get("optimizer_config"))
+    check_input_shape_cfg(cfg)
     if cfg.get("use_distillation", False) and isinstance(opt_hook, Fp16ArenaOptimizerHook):
         raise ValueError("use_distillation with fp16 training (optimizer_config type "
                          "'Fp16OptimizerHook') is not supported")

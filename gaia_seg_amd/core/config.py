@@ -27,6 +27,16 @@ class ConfigDict(dict):
         return ConfigDict({k: copy.deepcopy(v, memo) for k, v in self.items()})
 
 
+def _adopt(root):
+    """Every top-level dict entry remembers the config it is part of (``entry._root``, an attribute,
+    not a key): code that is handed one entry -- ``build_segmentor(cfg.model)`` -- can still read a
+    run-level key of the same config.  Copies do not carry it."""
+    for v in root.values():
+        if isinstance(v, ConfigDict):
+            object.__setattr__(v, "_root", root)
+    return root
+
+
 def _to_config_dict(obj):
     if isinstance(obj, dict):
         return ConfigDict({k: _to_config_dict(v) for k, v in obj.items()})
@@ -87,7 +97,7 @@ class Config:
         cfg_dict = {} if cfg_dict is None else cfg_dict
         if not isinstance(cfg_dict, dict):
             raise TypeError("cfg_dict must be a dict, but got %s" % type(cfg_dict))
-        object.__setattr__(self, "_cfg_dict", _to_config_dict(cfg_dict))
+        object.__setattr__(self, "_cfg_dict", _adopt(_to_config_dict(cfg_dict)))
         object.__setattr__(self, "_filename", filename)
 
     @staticmethod
@@ -108,7 +118,7 @@ class Config:
                 d = d.setdefault(sub, {})
             d[keys[-1]] = v
         merged = _merge_a_into_b(option_cfg, self._cfg_dict)
-        object.__setattr__(self, "_cfg_dict", _to_config_dict(merged))
+        object.__setattr__(self, "_cfg_dict", _adopt(_to_config_dict(merged)))
 
     def get(self, key, default=None):
         return self._cfg_dict.get(key, default)
@@ -120,10 +130,11 @@ class Config:
         return self._cfg_dict[name]
 
     def __setattr__(self, name, value):
-        self._cfg_dict[name] = _to_config_dict(value)
+        self[name] = value
 
     def __setitem__(self, name, value):
         self._cfg_dict[name] = _to_config_dict(value)
+        _adopt(self._cfg_dict)
 
     def __contains__(self, name):
         return name in self._cfg_dict

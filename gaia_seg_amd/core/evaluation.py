@@ -13,6 +13,7 @@ from ..hip import lib as _lib
 from ..hip.runtime import current_stream_ptr
 from . import dist as gdist
 from .dynamic import fold_dict
+from .input_shape import INPUT_SHAPE_KEY, rescale_batch
 from .runner import Hook
 
 
@@ -45,8 +46,11 @@ def metrics_from_confusion(conf):
                 IoU=iou.tolist(), Acc=acc.tolist())
 
 
-def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255):
-    """Test-mode pass over ``num_batches`` batches of dict(img, img_metas, gt_semantic_seg)."""
+def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255, input_shape=None):
+    """Test-mode pass over ``num_batches`` batches of dict(img, img_metas, gt_semantic_seg).
+    ``input_shape``: a ``data.input_shape`` value to evaluate at (core/input_shape.py): the image is
+    rescaled, ``ori_shape`` and the labels are not -- the test epilogue brings the predictions back
+    to the label size."""
     was_training = model.training
     model.eval()
     conf = None
@@ -54,6 +58,8 @@ def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255):
     with torch.no_grad():
         for _ in range(num_batches):
             batch = next(it)
+            if input_shape is not None:
+                batch = rescale_batch(batch, input_shape, with_labels=False)[0]
             img, metas, gt = batch["img"], batch["img_metas"], batch["gt_semantic_seg"]
             preds = model.simple_test_device(img, metas)
             conf = confusion_matrix(preds, gt, num_classes, ignore_index, conf)
@@ -65,10 +71,12 @@ def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255):
 
 
 class CrossArchEvalHook(Hook):
-    """Every ``interval`` iterations evaluate every val anchor (cross_arch_eval_hooks.py:59-92)."""
+    """Every ``interval`` iterations evaluate every val anchor (cross_arch_eval_hooks.py:59-92).
+    ``apply_input_shape``: an anchor that carries ``data.input_shape`` is evaluated at that size."""
 
     def __init__(self, dataloader, model_sampler, interval=1, num_batches=4, num_classes=19,
-                 ignore_index=255, logger=None):
+                 ignore_index=255, logger=None, apply_input_shape=False):
+        self.apply_input_shape = apply_input_shape
         self.dataloader, self.sampler = dataloader, model_sampler
         self.interval, self.num_batches = interval, num_batches
         self.num_classes, self.ignore_index = num_classes, ignore_index
@@ -94,7 +102,8 @@ class CrossArchEvalHook(Hook):
             meta = gdist.broadcast_object(meta, src=0)   # :59 broadcast_object(fold_dict(meta))
             runner.model.manipulate_arch(fold_dict(meta)["arch"])
             res = evaluate_model(runner.model, self.dataloader, self.num_batches,
-                                 self.num_classes, self.ignore_index)
+                                 self.num_classes, self.ignore_index,
+                                 input_shape=meta.get(INPUT_SHAPE_KEY) if self.apply_input_shape else None)
             name = meta.get("name", str(i))
             out[name] = res
             msg = "eval %s: mIoU %.4f mAcc %.4f aAcc %.4f" % (name, res["mIoU"], res["mAcc"], res["aAcc"])

@@ -403,3 +403,59 @@ def build_sample_rule(cfg):
         return _MergeRule()
     raise ValueError("unknown model-sampling rule type %r (have eval, sequential, parallel, sample, "
                      "merge)" % (t,))
+
+
+# ------------------------------------------------------------------------------------------------
+# data.input_shape: the third elastic dimension
+#
+# A reconstruction: gaiavision's ``ScaleManipulator`` is an absent dependency and the reference has
+# its calls commented out.  The value forms are the ones the reference writes down: the scale
+# sampler's ints (a short side, configs/_dynamic_/model_samplers/ar50to101v2_scale.py), the
+# ``x['data.input_shape'][-1] == 800`` of its rules (a sequence ending in H, W) and the string
+# "3,800,800" that its tools/count_flops.py accepts.
+# ------------------------------------------------------------------------------------------------
+
+
+def _positive_int(x, v):
+    if isinstance(x, bool) or not isinstance(x, int) or x <= 0:
+        raise ValueError("data.input_shape=%r: sizes must be positive integers" % (v,))
+    return x
+
+
+def parse_input_shape(v):
+    """A meta's ``data.input_shape`` value -> ('short', S) or ('exact', H, W); ValueError otherwise.
+
+    An int S is a short side; a sequence (H, W) or (C, H, W) with C == 3, or the same as a
+    comma-separated string, is an exact target."""
+    if isinstance(v, str):
+        try:
+            v = tuple(int(p) for p in v.split(","))
+        except ValueError:
+            raise ValueError("data.input_shape=%r: a string must be comma-separated integers" % (v,))
+        if len(v) == 1:
+            raise ValueError("data.input_shape=%r: a string names (H, W) or (C, H, W)" % (v,))
+    if isinstance(v, (list, tuple)):
+        if len(v) not in (2, 3):
+            raise ValueError("data.input_shape=%r: a sequence must be (H, W) or (C, H, W)" % (v,))
+        if len(v) == 3 and (isinstance(v[0], bool) or v[0] != 3):
+            raise ValueError("data.input_shape=%r: C must be 3" % (v,))
+        return ("exact", _positive_int(v[-2], v), _positive_int(v[-1], v))
+    return ("short", _positive_int(v, v))
+
+
+def resolve_input_shape(v, h, w):
+    """The size (H, W) a batch of size (h, w) takes under ``data.input_shape = v``.
+
+    int S: the short side becomes S and the long side floor(S * long / short + 0.5) (integer
+    arithmetic, so the result does not depend on floating-point rounding); a sequence or string:
+    exactly its last two entries, the aspect ratio is not kept.  The caller passes the batch through
+    when the result equals (h, w).  Anything else raises ValueError."""
+    parsed = parse_input_shape(v)
+    if parsed[0] == "exact":
+        return parsed[1], parsed[2]
+    s = parsed[1]
+    if h <= 0 or w <= 0:
+        raise ValueError("resolve_input_shape: batch size (%r, %r) must be positive" % (h, w))
+    short, long_ = min(h, w), max(h, w)
+    scaled = (2 * s * long_ + short) // (2 * short)     # floor(S * long / short + 0.5)
+    return (s, scaled) if h <= w else (scaled, s)

@@ -18,7 +18,8 @@ import torch
 
 from . import dist as gdist
 from .dynamic import fold_dict
-from .model_space import arch_key
+from .input_shape import INPUT_SHAPE_KEY, rescale_batch
+from .model_space import arch_key, parse_input_shape
 
 
 class Hook:
@@ -96,6 +97,10 @@ def check_sandwich_model(model):
                          "'aux_teacher_logits'); %s has no distillation branch" % type(aux).__name__)
 
 
+SANDWICH_INPUT_SHAPE = ("apply_input_shape with use_distillation (sandwich) is not supported: teacher "
+                        "and students at different resolutions are out of scope")
+
+
 class SandwichHook(Hook):
     """In-place distillation (tools/train_supernet.py:180-187; US-Nets' sandwich rule): before every
     train iteration rank 0 draws the member list with ``ConcatSampler.candidates()`` -- MAX, MIN, then
@@ -118,6 +123,8 @@ class SandwichHook(Hook):
 
     def before_run(self, runner):
         check_sandwich_model(runner.model)
+        if runner.apply_input_shape:
+            raise ValueError(SANDWICH_INPUT_SHAPE)
 
     def before_train_iter(self, runner):
         members = self.sampler.candidates() if gdist.rank() == 0 else None
@@ -370,6 +377,8 @@ class TextLoggerHook(Hook):
         self._t0 = time.time()
         if runner.train_precision != "fp32" or runner.loss_scale != 1.0:
             items += ", loss_scale: %g" % runner.loss_scale
+        if runner.apply_input_shape and runner.input_size is not None:
+            items += ", input: %dx%d" % runner.input_size
         msg = "Iter [%d/%d]\tlr: %.3e, arch: %s, time: %.3f, %s" % (
             runner.iter + 1, runner.max_iters, runner.lr, runner.arch_name, dt, items)
         if gdist.rank() == 0:
@@ -404,8 +413,15 @@ class IterBasedRunner:
     """``run(data_loaders, workflow)`` drives ``model.train_step`` for ``max_iters`` iterations."""
 
     def __init__(self, model, arena, reducer, base_lr=0.01, momentum=0.9, weight_decay=5e-4,
-                 max_iters=80000, work_dir=None, logger=None, meta=None, param_groups=None):
+                 max_iters=80000, work_dir=None, logger=None, meta=None, param_groups=None,
+                 apply_input_shape=False):
         self.model, self.arena, self.reducer = model, arena, reducer
+        # elastic input resolution (config key apply_input_shape, DESIGN.md section 20): with the flag
+        # set_arch remembers the meta's data.input_shape and _train_iter rescales the batch to it;
+        # without it the key is carried and nothing reads it
+        self.apply_input_shape = bool(apply_input_shape)
+        self.input_shape = None        # the current meta's data.input_shape value (flag on only)
+        self.input_size = None         # (H, W) of the last step's batch (flag on only: the logger's)
         self.base_lr = self.lr = base_lr
         self.momentum, self.weight_decay = momentum, weight_decay
         # parameter groups (core/optimizer.py build_param_groups; None = one lr / weight decay):
@@ -492,12 +508,17 @@ class IterBasedRunner:
     def set_arch(self, meta):
         """Apply a sampled meta (None = keep the current, max, architecture)."""
         if meta is not None:
+            shape = meta.get(INPUT_SHAPE_KEY) if self.apply_input_shape else None
+            if shape is not None:
+                parse_input_shape(shape)      # (refused at first sight, before anything is switched)
             self.model.manipulate_arch(fold_dict(meta)["arch"])
             self.arch_name = meta.get("name", "random")
             self.arch_key = arch_key(meta)
             self.arch_meta = meta
+            self.input_shape = shape
         else:
             self.arch_key = ("current",)
+            self.input_shape = None
         self.refresh_active()
 
     def refresh_active(self, force=False):
@@ -585,6 +606,16 @@ class IterBasedRunner:
         return (self.arch_key, tuple(sig), self.model.training, grouping, self.train_precision,
                 self.loss_scale)
 
+    def _apply_input_shape(self, data_batch):
+        """The batch at the current meta's data.input_shape (flag on; a copy: the caller's batch is
+        left alone).  The result's tensor shapes are part of _graph_key, so every (subnet,
+        resolution) pair gets a step graph of its own."""
+        if self.input_shape is None:
+            self.input_size = tuple(int(d) for d in data_batch["img"].shape[-2:])
+            return data_batch
+        data_batch, self.input_size = rescale_batch(data_batch, self.input_shape)
+        return data_batch
+
     def grad_scale(self):
         """SGD's gradient scale: the all-reduce sums world_size ranks' gradients of the loss times S."""
         return 1.0 / (gdist.world_size() * self.loss_scale)
@@ -656,8 +687,11 @@ class IterBasedRunner:
         step on ``data_batch``; the architecture in place before the call is restored."""
         keep = self.arch_meta
         done = 0
+        batch0 = data_batch
         for meta in metas:
             self.set_arch(meta)
+            if self.apply_input_shape:
+                data_batch = self._apply_input_shape(batch0)
             gkey = self._graph_key(data_batch)
             if gkey is None or gkey in self._graphs:
                 continue
@@ -726,6 +760,8 @@ class IterBasedRunner:
             self._after_hooks(False)
             self.iter += 1
             return self.outputs
+        if self.apply_input_shape:
+            data_batch = self._apply_input_shape(data_batch)
         t1 = time.perf_counter() if prof is not None else 0.0
         gkey = self._graph_key(data_batch)
         if self.graphs_enabled and gdist.world_size() == 1:

@@ -1322,3 +1322,40 @@ def add_grad_passthrough(tape, src, dst):
                    "gs_copy2d")
 
     tape.record(backward)
+
+
+# diagnostics for the tests only (like BNBWD_FUSED_COUNT): gs_batch_rescale launches batch_rescale
+# has made; nothing in the package reads it
+BATCH_RESCALE_CALLS = 0
+
+
+def batch_rescale(img, gt, size):
+    """A normalised batch at another resolution (data.input_shape): ``img``
+    fp32 NCHW [N,3,h,w] bilinear (align_corners=False), ``gt`` int64 [N,1,h,w] nearest or None, both
+    in ONE gs_batch_rescale launch on the current stream.  ``size`` = (H, W); a size equal to (h, w)
+    returns the inputs themselves without a launch.  Returns (img, gt) as new tensors."""
+    global BATCH_RESCALE_CALLS
+    H, W = int(size[0]), int(size[1])
+    if not img.is_cuda or (gt is not None and not gt.is_cuda):
+        raise _lib.HipLibraryError("batch_rescale needs device tensors (no CPU fallback)")
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32:
+        raise ValueError("batch_rescale: img must be fp32 [N,3,h,w], got %s %s"
+                         % (img.dtype, tuple(img.shape)))
+    n, _, h, w = img.shape
+    if gt is not None and (gt.dtype != torch.int64 or tuple(gt.shape) != (n, 1, h, w)):
+        raise ValueError("batch_rescale: gt_semantic_seg must be int64 [%d,1,%d,%d], got %s %s"
+                         % (n, h, w, gt.dtype, tuple(gt.shape)))
+    if (H, W) == (h, w):
+        return img, gt
+    img = img.contiguous()
+    out = torch.empty((n, 3, H, W), dtype=torch.float32, device=img.device)
+    out_gt = None
+    if gt is not None:
+        gt = gt.contiguous()
+        out_gt = torch.empty((n, 1, H, W), dtype=torch.int64, device=img.device)
+    _lib.check(_L().gs_batch_rescale(img.data_ptr(), gt.data_ptr() if gt is not None else None,
+                                     n, h, w, out.data_ptr(),
+                                     out_gt.data_ptr() if gt is not None else None, H, W,
+                                     current_stream_ptr()), "gs_batch_rescale")
+    BATCH_RESCALE_CALLS += 1
+    return out, out_gt

@@ -40,4 +40,8 @@ def build_segmentor(cfg, train_cfg=None, test_cfg=None):
         "train_cfg specified in both outer field and model field "
     assert cfg.get("test_cfg") is None or test_cfg is None, \
         "test_cfg specified in both outer field and model field "
-    return build_from_cfg(cfg, SEGMENTORS, dict(train_cfg=train_cfg, test_cfg=test_cfg))
+    model = build_from_cfg(cfg, SEGMENTORS, dict(train_cfg=train_cfg, test_cfg=test_cfg))
+    # the config whose ``model`` entry this is (core/config.py _adopt; None for a plain dict): loops
+    # that are handed the model alone read run-level keys such as apply_input_shape from it
+    model.top_cfg = getattr(cfg, "_root", None)
+    return model

@@ -598,6 +598,22 @@ typedef struct gs_augment_desc {
 int gs_seg_augment(const gs_augment_desc* d, const uint8_t* img, const uint8_t* label,
                    float* out_img, int64_t* out_label, void* stream);
 
+/* Elastic input resolution (data.input_shape): one launch resamples a
+ * normalised batch on the device.
+ *   img    fp32 NCHW [N][3][h][w] -> out_img [N][3][H][W]: bilinear, align_corners=False, ATen's fp32
+ *          source indices and weights (F.interpolate's);
+ *   label  int64 [N][1][h][w] -> out_label [N][1][H][W]: nearest, source index
+ *          min(floor(dst * (float)in / out), in - 1) in fp32 (ATen's); every value, 255 included, is
+ *          copied as it is.  label and out_label may both be NULL (evaluation rescales the image only).
+ * All four tensors are contiguous; the sources and the destinations must not overlap.  No workspace,
+ * no atomics, launched on `stream` (capturable).  The output is written in aligned 16-byte pieces
+ * over the flat tensors, so out_img and out_label must be 16-byte aligned; img needs 4-byte and label
+ * 8-byte alignment.  GS_E_NULL: img or out_img NULL, or only one of label / out_label given;
+ * GS_E_BADARG: a size <= 0, a plane of more than 2^31 - 1 pixels, or a source or output image of
+ * 2^63 elements and more; GS_E_ALIGN. */
+int gs_batch_rescale(const float* img, const int64_t* label, int32_t N, int32_t h, int32_t w,
+                     float* out_img, int64_t* out_label, int32_t H, int32_t W, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Forward precision of the convolutions (inference; tools/test_supernet.py with cfg.fp16).       */
 /*   0 = fp32 (default): every launch as documented above.                                     */

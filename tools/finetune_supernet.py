@@ -17,8 +17,9 @@ BatchNorm running statistics of each subnet re-estimated on the train data, no w
 
 Deviations from the reference:
   * its hard-coded list of skipped ``overhead.flops`` values (:266) is not reproduced;
-  * ``data.input_shape`` is carried through the rows but not applied (the reference has that code
-    commented out, :275-277);
+  * ``data.input_shape`` is carried through the rows; with ``cfg.apply_input_shape = True`` each
+    row is trained and evaluated at its own input size and rows of one arch at different sizes are
+    rows of their own (DESIGN.md section 20; the reference has that code commented out, :275-277);
   * step and by-epoch ``lr_config`` schedules (the reference's detection finetune configs) stay
     refused: 'poly' and 'fixed' by iteration only;
   * the output file is rewritten (atomically) after EVERY subnet, and two flags are added where the
@@ -129,25 +130,31 @@ def has_tag(row, tag):
     return all("metric.%s.%s" % (tag, k) in row for k in ("mIoU", "mAcc", "aAcc"))
 
 
-def pending_metas(metas, existing_rows, tag):
+def scale_key(meta):
+    """A row's identity with ``cfg.apply_input_shape``: its arch and its input size."""
+    v = meta.get("data.input_shape")
+    return arch_key(meta), tuple(v) if isinstance(v, (list, tuple)) else v
+
+
+def pending_metas(metas, existing_rows, tag, key=arch_key):
     """``--resume``: the metas whose arch has no ``metric.<tag>.*`` in the existing output rows."""
-    done = {arch_key(r) for r in existing_rows if has_tag(r, tag)}
-    return [m for m in metas if arch_key(m) not in done]
+    done = {key(r) for r in existing_rows if has_tag(r, tag)}
+    return [m for m in metas if key(m) not in done]
 
 
-def merge_rows(metas, existing_rows, new_rows, tag):
+def merge_rows(metas, existing_rows, new_rows, tag, key=arch_key):
     """The output file's rows: one per selected meta in selection order -- the freshly finetuned row,
     else the existing row that carries the tag -- then the existing rows outside the selection."""
-    new = {arch_key(r): r for r in new_rows}
-    old = {arch_key(r): r for r in existing_rows if has_tag(r, tag)}
+    new = {key(r): r for r in new_rows}
+    old = {key(r): r for r in existing_rows if has_tag(r, tag)}
     out, used = [], set()
     for m in metas:
-        k = arch_key(m)
+        k = key(m)
         r = new.get(k) or old.get(k)
         if r is not None and k not in used:
             out.append(r)
             used.add(k)
-    out.extend(r for r in existing_rows if arch_key(r) not in used)
+    out.extend(r for r in existing_rows if key(r) not in used)
     return out
 
 
@@ -230,7 +237,8 @@ def main(argv=None):
     if not any(k.startswith("metric.") for m in metas for k in m):
         logger.warning("`metric` is absent during finetuning.")
     existing = load_model_space(out) if args.resume and osp.exists(out) else []
-    todo = pending_metas(metas, existing, args.metric_tag)
+    key = scale_key if cfg.get("apply_input_shape", False) else arch_key
+    todo = pending_metas(metas, existing, args.metric_tag, key)
     if len(todo) < len(metas):
         logger.info("--resume: %d of %d subnets already carry metric.%s in %s"
                     % (len(metas) - len(todo), len(metas), args.metric_tag, out))
@@ -274,7 +282,7 @@ def main(argv=None):
             if rank == 0:
                 save_checkpoint(net, path, meta=dict(ck_meta, version=__version__, **_listify(dict(row))))
         if rank == 0:
-            write_rows(merge_rows(metas, existing, done, args.metric_tag), out)
+            write_rows(merge_rows(metas, existing, done, args.metric_tag, key), out)
 
     rows = finetune_model_space(model, todo, cfg, cfg.data["train"], val_loader, num_batches,
                                 metric_tag=args.metric_tag, validate=not args.no_validate, seed=seed,
@@ -284,7 +292,7 @@ def main(argv=None):
             print("%s mIoU %.4f mAcc %.4f aAcc %.4f" % (
                 r.get("name", "-"), r["metric.%s.mIoU" % args.metric_tag],
                 r["metric.%s.mAcc" % args.metric_tag], r["metric.%s.aAcc" % args.metric_tag]))
-        print("wrote %d rows to %s" % (len(merge_rows(metas, existing, done, args.metric_tag)), out))
+        print("wrote %d rows to %s" % (len(merge_rows(metas, existing, done, args.metric_tag, key)), out))
     if dist.is_initialized():
         dist.destroy_process_group()
 

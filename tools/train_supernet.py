@@ -3,6 +3,10 @@
 the same sequence (:99-214): Config -> cfg-options -> dist init -> work_dir / logger / seed ->
 build_segmentor -> build_model_sampler x2 -> dataset -> train_segmentor.
 
+``apply_input_shape = True`` in the config applies every sampled meta's ``data.input_shape`` to the
+batch before the step (elastic input resolution, DESIGN.md section 20;
+configs/supernet/fcn_ar50to101v2_elastic_scale.py).
+
 Launch one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         tools/train_supernet.py configs/supernet/pspnet_ar50to101v2.py --launcher pytorch
