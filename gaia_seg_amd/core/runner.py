@@ -239,21 +239,6 @@ def _ranges_union(a, b):
     return [tuple(r) for r in out]
 
 
-def _member_backward(runner, loss):
-    """ArenaOptimizerHook.after_train_iter up to (not including) the SGD step: backward with the
-    gradient exchange, then every stream joined, so the member's gradients are final and reduced."""
-    from ..hip import ops
-    ops.SIDE_CHECKPOINT = None
-    ops.DEFER_JOIN = True
-    try:
-        loss.backward()
-    finally:
-        ops.DEFER_JOIN = False
-    ops.join_branch_streams()
-    runner.reducer.finish()
-    ops.join_side_streams()
-
-
 class ArenaOptimizerHook(Hook):
     """OptimizerHook for the flat-arena SGD: the step touches only the active subnet's ranges.
 
@@ -270,49 +255,25 @@ class ArenaOptimizerHook(Hook):
 
     def after_train_iter(self, runner):
         from ..hip import ops
-        prof = runner.host_prof
-        t0 = time.perf_counter() if prof is not None else 0.0
-        ops.SIDE_CHECKPOINT = None
-        ops.DEFER_JOIN = True          # the tapes hand their weight gradients over but do not join
-        runner.mark("fwd_end")
-        try:
-            loss = runner.outputs["loss"]
-            if runner.loss_scale != 1.0:
-                loss.backward(gradient=runner.loss_seed(loss))   # (static loss scale S)
-            else:
-                loss.backward()
-        finally:
-            ops.DEFER_JOIN = False
-        t1 = time.perf_counter() if prof is not None else 0.0
-        runner.mark("bwd_end_main")
-        side = ops.side_stream(runner.arena.device)
-        if side is not None:
-            runner.mark("bwd_end_side0", side)
-        ops.join_branch_streams()      # (auxiliary head / shortcut work on the branch stream)
-        runner.reducer.finish()
+        ck = runner.backward(runner.outputs["loss"])
+        t0 = runner._tick()
         scale = runner.grad_scale()
         early, late = runner.split_ranges()
-        ck = ops.SIDE_CHECKPOINT
         if ck is not None and early:
             # gradients of everything behind the checkpoint are final once the side stream has passed
             # it: update those parameters while the stem / stage-1 weight gradients still run
             for ev in ck:
                 torch.cuda.current_stream().wait_event(ev)
-            runner.arena.sgd_step(early, runner.opt_lr, runner.momentum, runner.opt_wd, scale, True,
-                                  hyper=runner.hyper)
+            runner._sgd(early, scale, runner.hyper)
             ops.join_side_streams()
-            runner.arena.sgd_step(late, runner.opt_lr, runner.momentum, runner.opt_wd, scale, True,
-                                  hyper=runner.hyper)
+            runner._sgd(late, scale, runner.hyper)
         else:
             ops.join_side_streams()
-            runner.arena.sgd_step(runner.active_ranges, runner.opt_lr, runner.momentum,
-                                  runner.opt_wd, scale, True, hyper=runner.hyper)
+            runner._sgd(runner.active_ranges, scale, runner.hyper)
         # the step cleared exactly the ranges backward wrote: the next zero_grad has nothing to do
         runner.arena.grads_clean = True
         runner.mark("step_end")
-        if prof is not None:
-            prof["backward"] = prof.get("backward", 0.0) + (t1 - t0)
-            prof["finish+sgd"] = prof.get("finish+sgd", 0.0) + (time.perf_counter() - t1)
+        runner._tick("finish+sgd", t0)
 
 
 class Fp16ArenaOptimizerHook(ArenaOptimizerHook):
@@ -462,6 +423,7 @@ class IterBasedRunner:
         self.hyper = None              # device {lr, momentum, weight_decay, grad_scale} (graphs on)
         self.graph_stats = {"captured": 0, "replayed": 0, "eager": 0}
         self.sandwich = None           # (members, kd_cfg) of THIS iteration, set by SandwichHook
+        self.last_checkpoint = None    # the last backward's side-stream checkpoint (see backward)
         # fp16 training (Fp16ArenaOptimizerHook sets both; settable independently): the conv operand
         # precision of every train_iter ('fp32' / 'fp16', ops.train_precision) and the static loss
         # scale S that seeds backward (SGD divides it out: grad_scale)
@@ -501,10 +463,6 @@ class IterBasedRunner:
         for h in self.hooks:
             getattr(h, name)(self)
 
-    @property
-    def raw_model(self):
-        return self.model
-
     def set_arch(self, meta):
         """Apply a sampled meta (None = keep the current, max, architecture)."""
         if meta is not None:
@@ -528,7 +486,7 @@ class IterBasedRunner:
         so they must neither decay nor move (gaiaseg/models/backbones/dynamic_resnet.py:304-334).
         The sets of a named / sampled subnet are cached by its arch key (the module walk costs
         ~0.4 ms per step otherwise); ``force`` drops the cache (requires_grad flags were edited)."""
-        key = self.arch_key if self.arch_key != ("current",) else None
+        key = self.cache_key
         if force:
             self._active_cache.clear()
         hit = self._active_cache.get(key) if key is not None else None
@@ -546,7 +504,13 @@ class IterBasedRunner:
             for r in (self.active_ranges,) + tuple(self.split_ranges()):
                 self.arena.chunk_table(r)
 
-    # what the optimizer hooks hand to arena.sgd_step: one value, or one per parameter group
+    @property
+    def cache_key(self):
+        """The arch key the per-subnet caches (active sets, ranges, gradient buckets) are filed
+        under; None for an architecture nobody named (set_arch(None)): not cached."""
+        return self.arch_key if self.arch_key != ("current",) else None
+
+    # what _sgd hands to arena.sgd_step: one value, or one per parameter group
     @property
     def opt_lr(self):
         return self.lr if self.group_lr is None else self.group_lr
@@ -558,7 +522,7 @@ class IterBasedRunner:
     def split_ranges(self):
         """(early, late) parts of active_ranges: `late` covers the parameters whose weight gradients
         are produced last in backward (backbone.late_gradient_parameters), `early` the rest."""
-        key = self.arch_key if self.arch_key != ("current",) else None
+        key = self.cache_key
         cached = self._split_cache.get(key) if key is not None else None
         if cached is not None:
             return cached
@@ -640,6 +604,51 @@ class IterBasedRunner:
         if self.group_lr is not None:
             self.arena.write_group_hyper(self.group_lr, self.group_wd, self.momentum, self.grad_scale())
 
+    def _tick(self, key=None, since=0.0):
+        """GS_HOST_PROF: the host clock (0.0 with the profile off); with ``key`` the seconds since
+        ``since`` are added to host_prof[key]."""
+        if self.host_prof is None:
+            return 0.0
+        now = time.perf_counter()
+        if key is not None:
+            self.host_prof[key] = self.host_prof.get(key, 0.0) + (now - since)
+        return now
+
+    def _begin_step(self):
+        """Before a subnet's forward: its gradients zero and marked dirty, the reducer armed."""
+        self.arena.zero_grad(self.active_ranges, trust_clean=True)   # (a no-op after a clearing optimizer step)
+        self.arena.grads_clean = False
+        self.reducer.begin(self.trainable_params, self.cache_key)
+
+    def backward(self, loss):
+        """``loss.backward()`` (seeded with the static loss scale) under ops.deferred_join, then the
+        branch streams joined and the reducer finished.  Returns the side stream's checkpoint events
+        or None (kept in ``last_checkpoint``); joining the side stream is left to the caller, which
+        may step the early instalment first (ArenaOptimizerHook)."""
+        from ..hip import ops
+        t0 = self._tick()
+        self.mark("fwd_end")
+        with ops.deferred_join() as dj:
+            if self.loss_scale != 1.0:
+                loss.backward(gradient=self.loss_seed(loss))   # (static loss scale S)
+            else:
+                loss.backward()
+        t1 = self._tick("backward", t0)
+        self.mark("bwd_end_main")
+        side = ops.side_stream(self.arena.device)
+        if side is not None:
+            self.mark("bwd_end_side0", side)
+        ops.join_branch_streams()      # (auxiliary head / shortcut work on the branch stream)
+        self.reducer.finish()
+        self._tick("finish+sgd", t1)
+        self.last_checkpoint = dj.checkpoint
+        return dj.checkpoint
+
+    def _sgd(self, ranges, grad_scale, hyper=None):
+        """One fused SGD step on ``ranges`` that clears the gradients it consumed."""
+        self.arena.sgd_step(ranges, self.opt_lr, self.momentum, self.opt_wd, grad_scale, True,
+                            hyper=hyper)
+
     def _after_hooks(self, in_graph):
         for h in self.hooks:
             if bool(getattr(h, "in_graph", False)) == in_graph:
@@ -670,6 +679,20 @@ class IterBasedRunner:
         graph.replay()                 # the capture only recorded the step: this performs it
         return entry
 
+    def _step(self, capture_key, data_batch):
+        """One training step outside a replay: eager, or (``capture_key``) captured into a step graph
+        and run once.  Returns the host clock after _begin_step and after the forward / the capture."""
+        self._begin_step()
+        t2 = self._tick()
+        if capture_key is not None:
+            self._capture_step(capture_key, data_batch)
+            return t2, self._tick()
+        self.outputs = self.model.train_step(data_batch, None)
+        t3 = self._tick()
+        self._after_hooks(True)
+        self.graph_stats["eager"] += 1
+        return t2, t3
+
     def _replay_step(self, entry, data_batch):
         for k, v in entry.static.items():
             if torch.is_tensor(v):
@@ -687,26 +710,16 @@ class IterBasedRunner:
         step on ``data_batch``; the architecture in place before the call is restored."""
         keep = self.arch_meta
         done = 0
-        batch0 = data_batch
         for meta in metas:
             self.set_arch(meta)
-            if self.apply_input_shape:
-                data_batch = self._apply_input_shape(batch0)
-            gkey = self._graph_key(data_batch)
+            batch = self._apply_input_shape(data_batch) if self.apply_input_shape else data_batch
+            gkey = self._graph_key(batch)
             if gkey is None or gkey in self._graphs:
                 continue
-            for eager in ((True, False) if self.graph_stats["eager"] == 0 else (False,)):
+            for capture in ((False, True) if self.graph_stats["eager"] == 0 else (True,)):
                 self._write_hyper()
-                self.arena.zero_grad(self.active_ranges, trust_clean=True)
-                self.arena.grads_clean = False
-                self.reducer.begin(self.trainable_params, self.arch_key)
-                if eager:
-                    self.outputs = self.model.train_step(data_batch, None)
-                    self._after_hooks(True)
-                    self.graph_stats["eager"] += 1
-                else:
-                    self._capture_step(gkey, data_batch)
-                    done += 1
+                self._step(gkey if capture else None, batch)
+            done += 1
         if keep is not None:
             self.set_arch(keep)
         return done
@@ -747,8 +760,7 @@ class IterBasedRunner:
             return self._train_iter(data_batch)
 
     def _train_iter(self, data_batch):
-        prof = self.host_prof
-        t0 = time.perf_counter() if prof is not None else 0.0
+        t0 = self._tick()
         self.mark("step_begin")
         if not self.model.training:   # (a full module walk: ~1.5 ms of host time per call)
             self.model.train()
@@ -762,39 +774,28 @@ class IterBasedRunner:
             return self.outputs
         if self.apply_input_shape:
             data_batch = self._apply_input_shape(data_batch)
-        t1 = time.perf_counter() if prof is not None else 0.0
+        t1 = self._tick()
         gkey = self._graph_key(data_batch)
         if self.graphs_enabled and gdist.world_size() == 1:
             self._write_hyper()
         entry = self._graphs.get(gkey) if gkey is not None else None
-        t2 = t1
         if entry is not None:
             self._graphs.move_to_end(gkey)
             self._replay_step(entry, data_batch)
-            t3 = time.perf_counter() if prof is not None else 0.0
+            t2, t3 = t1, self._tick()
         else:
-            self.arena.zero_grad(self.active_ranges, trust_clean=True)   # (a no-op after a clearing optimizer step)
-            self.arena.grads_clean = False             # backward is about to write gradients
-            self.reducer.begin(self.trainable_params,
-                               self.arch_key if self.arch_key != ("current",) else None)
-            t2 = time.perf_counter() if prof is not None else 0.0
             # capture at first sight what is known to come back (named anchors), anything else the
             # second time it shows up; the very first step of a process always runs eagerly (module
             # loading and lazily created handles must not happen inside a capture)
             known = self.arch_name != "random" or self._arch_seen.get(self.arch_key, 0) > 0
-            if gkey is not None and known and self.graph_stats["eager"] > 0:
-                self._capture_step(gkey, data_batch)
-                t3 = time.perf_counter() if prof is not None else 0.0
-            else:
-                self.outputs = self.model.train_step(data_batch, None)
-                t3 = time.perf_counter() if prof is not None else 0.0
-                self._after_hooks(True)
-                self.graph_stats["eager"] += 1
-                if gkey is not None:
-                    self._arch_seen[self.arch_key] = self._arch_seen.get(self.arch_key, 0) + 1
-                    if len(self._arch_seen) > 4096:
-                        self._arch_seen.clear()
+            capture = gkey is not None and known and self.graph_stats["eager"] > 0
+            t2, t3 = self._step(gkey if capture else None, data_batch)
+            if gkey is not None and not capture:
+                self._arch_seen[self.arch_key] = self._arch_seen.get(self.arch_key, 0) + 1
+                if len(self._arch_seen) > 4096:
+                    self._arch_seen.clear()
         self._after_hooks(False)
+        prof = self.host_prof
         if prof is not None:
             t4 = time.perf_counter()
             for k, v in (("hooks_before", t1 - t0), ("zero+begin", t2 - t1), ("forward", t3 - t2),
@@ -813,6 +814,7 @@ class IterBasedRunner:
     # gradients over the union of the members' ranges and one fused SGD step clears them again.
     # Eager only: no step graphs, no early / split SGD instalments.
     def _sandwich_iter(self, data_batch, members, kd_cfg):
+        from ..hip import ops
         total, log_vars, union, names = None, OrderedDict(), [], []
         teacher = None
         n_random = 0
@@ -822,16 +824,15 @@ class IterBasedRunner:
             if name is None:
                 name, n_random = "random%d" % n_random, n_random + 1
             names.append(name)
-            self.arena.zero_grad(self.active_ranges, trust_clean=True)
-            self.arena.grads_clean = False
-            self.reducer.begin(self.trainable_params, self.arch_key)
+            self._begin_step()
             if i == 0:
                 out = self.model.train_step(data_batch, None, return_logits=True)
                 teacher = (out["logits"], out["aux_logits"])
             else:
                 out = self.model.train_step(data_batch, None, teacher_logits=teacher[0],
                                             aux_teacher_logits=teacher[1], **kd_cfg)
-            _member_backward(self, out["loss"])
+            self.backward(out["loss"])
+            ops.join_side_streams()    # (every stream joined: the member's gradients are final)
             self.arena.accumulate(self.active_ranges, into="buffer")
             self.arena.grads_clean = True          # (the move left zeros behind)
             union = _ranges_union(union, self.active_ranges)
@@ -841,8 +842,7 @@ class IterBasedRunner:
                 log_vars["%s.%s" % (name, k)] = v
         self.arena.accumulate(union, into="grad")
         self.arena.grads_clean = False
-        self.arena.sgd_step(union, self.opt_lr, self.momentum, self.opt_wd,
-                            1.0 / gdist.world_size(), True)
+        self._sgd(union, 1.0 / gdist.world_size())
         self.arena.grads_clean = True
         self.arch_name = "sandwich"
         log_vars["loss"] = total[1]

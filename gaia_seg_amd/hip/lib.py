@@ -33,6 +33,32 @@ class ConvDesc(Structure):
                 ("role", c_int32), ("reserved", c_int32), ("in_affine", c_void_p)]
 
 
+def conv_out_size(h, k, s, p, d):
+    return (h + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+def conv_desc(n, h, w, ci, co, k, stride=1, dil=1, pad=None, ci_max=None, co_ld=None, ldx=None,
+              ldy=None, ld_add=0, role=0):
+    """The one place that fills a ``ConvDesc``: a packed-NHWC input [n, h, w, ci] with row pitch
+    ``ldx`` (default ci), a weight of ``ci_max`` (default ci) input channels and row pitch ``co_ld``
+    (default co), ``k`` x ``k`` taps (or a (kh, kw) pair), 'same' padding ``dil * (k // 2)`` unless
+    ``pad`` is given, output row pitch ``ldy`` (default co).  ``in_affine`` stays null."""
+    kh, kw = k if isinstance(k, tuple) else (k, k)
+    ldx = ci if ldx is None else ldx
+    d = ConvDesc()
+    d.N, d.H, d.W, d.Ci, d.Co = n, h, w, ci, co
+    d.Ci_max = ci if ci_max is None else ci_max
+    d.Co_ld = co if co_ld is None else co_ld
+    d.KH, d.KW = kh, kw
+    d.stride, d.pad, d.dil = stride, dil * (kh // 2) if pad is None else pad, dil
+    d.Ho = conv_out_size(h, kh, stride, d.pad, dil)
+    d.Wo = conv_out_size(w, kw, stride, d.pad, dil)
+    d.x_sn, d.x_sh, d.x_sw, d.x_sc = h * w * ldx, w * ldx, ldx, 1
+    d.ldy, d.ld_add = co if ldy is None else ldy, ld_add
+    d.role = role
+    return d
+
+
 class BnArgs(Structure):
     """Mirror of ``gs_bn_args``."""
     _fields_ = [("gamma", c_void_p), ("beta", c_void_p), ("running_mean", c_void_p),

@@ -126,22 +126,43 @@ def flush_wgrads():
         _notify(job[3])
 
 
-DEFER_JOIN = False   # the runner sets it to overlap the optimizer step with the last weight gradients
-SIDE_CHECKPOINT = None   # events on the side streams: every weight gradient queued before them is done
+_deferred = None   # the deferred_join scope a backward runs in (None: every tape joins the side stream)
+
+
+class deferred_join:
+    """``with ops.deferred_join() as dj: loss.backward()`` -- the tapes hand their weight gradients to
+    the side stream but do not join it (runtime.Tape.backward): the caller overlaps the optimizer
+    step with the last weight gradients and joins afterwards (join_side_streams).  ``dj.checkpoint``:
+    the events ``side_checkpoint`` left on the side streams (every weight gradient queued before them
+    is done once they have fired), or None when backward crossed no checkpoint.  Nothing outside
+    this scope switches the protocol on or off."""
+
+    def __init__(self):
+        self.checkpoint = None
+
+    def __enter__(self):
+        global _deferred
+        _deferred = self
+        return self
+
+    def __exit__(self, *exc):
+        global _deferred
+        _deferred = None
+        return False
 
 
 def side_checkpoint(tape):
     """Mark a point of the backward replay (recorded in forward order, so it fires when backward
     crosses it): all weight gradients of the layers AFTER this point have been handed to the side
     stream; an event on the side stream lets the optimizer update those parameters while the side
-    stream still works on the layers before the point (the runner waits on SIDE_CHECKPOINT)."""
+    stream still works on the layers before the point (the runner waits on deferred_join.checkpoint)."""
     def backward():
-        global SIDE_CHECKPOINT
-        if not DEFER_JOIN:
+        dj = _deferred
+        if dj is None:
             return
         flush_wgrads()
         events = [st.side.record_event() for st in _streams.values() if st.side_dirty]
-        SIDE_CHECKPOINT = events or None
+        dj.checkpoint = events or None
     tape.record(backward)
 
 
@@ -439,29 +460,24 @@ def _notify(param):
         hook(param)
 
 
-def conv_out_size(h, k, s, p, d):
-    return (h + 2 * p - d * (k - 1) - 1) // s + 1
+conv_out_size = _lib.conv_out_size
 
 
 def _conv_desc(x, weight, co, stride, pad, dil, ldy, ld_add=0, role=0):
     """gs_conv_desc for activation ``x`` and a max-size weight Parameter (logical OIHW, physical
-    HWIO with row pitch ``Co_ld``)."""
+    HWIO with row pitch ``Co_ld``): lib.conv_desc with the strides of ``x`` (the stem's NCHW image
+    is not packed NHWC)."""
     co_max, ci_max, kh, kw = weight.shape
-    co_ld = weight.stride(1)
-    d = _lib.ConvDesc()
     if x.nchw_image:
         n, c, h, w = x.t.shape
-        d.x_sn, d.x_sc, d.x_sh, d.x_sw = x.t.stride()
     else:
         n, h, w, c = x.t.shape
+    d = _lib.conv_desc(n, h, w, c, co, (kh, kw), stride, dil, pad, ci_max, weight.stride(1), ldy=ldy,
+                       ld_add=ld_add, role=role)
+    if x.nchw_image:
+        d.x_sn, d.x_sc, d.x_sh, d.x_sw = x.t.stride()
+    else:
         d.x_sn, d.x_sh, d.x_sw, d.x_sc = x.t.stride()
-    d.N, d.H, d.W, d.Ci, d.Co = n, h, w, c, co
-    d.Ci_max, d.Co_ld, d.KH, d.KW = ci_max, co_ld, kh, kw
-    d.stride, d.pad, d.dil = stride, pad, dil
-    d.Ho = conv_out_size(h, kh, stride, pad, dil)
-    d.Wo = conv_out_size(w, kw, stride, pad, dil)
-    d.ldy, d.ld_add = ldy, ld_add
-    d.role = role
     if c > ci_max:
         raise ValueError("input has %d channels, conv supports at most %d" % (c, ci_max))
     return d
@@ -530,29 +546,24 @@ DEFER_BN = True   # master switch (tests flip it to compare the two forms bit fo
 DEFER_SHORTCUT_BN = os.environ.get("GS_DEFER_SHORTCUT_BN", "1") != "0"
 
 
-def materialize(tape, x):
-    """Write out relu(bn(t)) of a deferred activation (consumers without the loader fusion)."""
-    if x.affine is None:
-        return x
+def _materialize(tape, x, coeffs, relu):
     z = Act.empty(x.N, x.H, x.W, x.C, x.t.device)
-    _lib.check(_L().gs_bn_apply(x.ptr, x.rows, x.C, x.ld, x.affine.data_ptr(), None, 0, 1, z.ptr, z.ld,
+    _lib.check(_L().gs_bn_apply(x.ptr, x.rows, x.C, x.ld, coeffs.data_ptr(), None, 0, relu, z.ptr, z.ld,
                                 current_stream_ptr()), "gs_bn_apply")
     z.requires_grad = x.requires_grad
     add_grad_passthrough(tape, x, z)
     return z
 
 
+def materialize(tape, x):
+    """Write out relu(bn(t)) of a deferred activation (consumers without the loader fusion)."""
+    return x if x.affine is None else _materialize(tape, x, x.affine, 1)
+
+
 def materialize_residual(tape, r):
     """Write out bn(t) of a residual whose BatchNorm was left to its consumer (Act.res_affine), for
     consumers that take a plain addend."""
-    if r is None or r.res_affine is None:
-        return r
-    z = Act.empty(r.N, r.H, r.W, r.C, r.t.device)
-    _lib.check(_L().gs_bn_apply(r.ptr, r.rows, r.C, r.ld, r.res_affine.data_ptr(), None, 0, 0, z.ptr,
-                                z.ld, current_stream_ptr()), "gs_bn_apply")
-    z.requires_grad = r.requires_grad
-    add_grad_passthrough(tape, r, z)
-    return z
+    return r if r is None or r.res_affine is None else _materialize(tape, r, r.res_affine, 0)
 
 
 # ---- forward precision (inference) -----------------------------------------------------------
@@ -565,35 +576,27 @@ _PRECISIONS = {"fp32": _lib.PRECISION_FP32, "fp16": _lib.PRECISION_FP16}
 FORWARD_PRECISION = _lib.PRECISION_FP32
 
 
-def set_forward_precision(mode):
-    """Set the library's forward precision ('fp32' / 'fp16'); returns the previous name."""
-    global FORWARD_PRECISION
+def _check_mode(what, mode):
     if mode not in _PRECISIONS:
-        raise ValueError("forward precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
-    prev = "fp16" if FORWARD_PRECISION == _lib.PRECISION_FP16 else "fp32"
-    _lib.check(_L().gs_set_forward_precision(_PRECISIONS[mode]), "gs_set_forward_precision")
-    FORWARD_PRECISION = _PRECISIONS[mode]
+        raise ValueError("%s precision must be one of %s, got %r" % (what, sorted(_PRECISIONS), mode))
+
+
+def _set_precision(what, mode, current):
+    """Set the library's ``what`` ('forward' / 'train') precision to 'fp32' / 'fp16'; returns the
+    previous name (``current()``: the library's mode before the call)."""
+    _check_mode(what, mode)
+    prev = "fp16" if current() == _lib.PRECISION_FP16 else "fp32"
+    name = "gs_set_%s_precision" % what
+    _lib.check(getattr(_L(), name)(_PRECISIONS[mode]), name)
     return prev
 
 
-class forward_precision:
-    """``with forward_precision("fp16"): ...`` -- inference forwards with fp16 operands; the previous
-    precision is restored on exit, exceptions included.  A conv that records a tape (training)
-    inside raises: the backward kernels assume an fp32 forward."""
-
-    def __init__(self, mode):
-        if mode not in _PRECISIONS:
-            raise ValueError("forward precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
-        self.mode = mode
-        self._prev = None
-
-    def __enter__(self):
-        self._prev = set_forward_precision(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        set_forward_precision(self._prev)
-        return False
+def set_forward_precision(mode):
+    """Set the library's forward precision ('fp32' / 'fp16'); returns the previous name."""
+    global FORWARD_PRECISION
+    prev = _set_precision("forward", mode, lambda: FORWARD_PRECISION)
+    FORWARD_PRECISION = _PRECISIONS[mode]
+    return prev
 
 
 # ---- training precision ----------------------------------------------------------------------
@@ -604,31 +607,37 @@ class forward_precision:
 # switch, neither workspace sizes nor the conv_bn plan cache depend on it.
 def set_train_precision(mode):
     """Set the library's training precision ('fp32' / 'fp16'); returns the previous name."""
-    if mode not in _PRECISIONS:
-        raise ValueError("train precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
-    L = _L()
-    prev = "fp16" if L.gs_get_train_precision() == _lib.PRECISION_FP16 else "fp32"
-    _lib.check(L.gs_set_train_precision(_PRECISIONS[mode]), "gs_set_train_precision")
-    return prev
+    return _set_precision("train", mode, lambda: _L().gs_get_train_precision())
 
 
-class train_precision:
-    """``with train_precision("fp16"): ...`` -- training steps with fp16 conv operands (forward and
-    data gradient); the previous precision is restored on exit, exceptions included."""
+class _precision_scope:
+    """``with <scope>(mode): ...`` -- the previous precision is restored on exit, exceptions included."""
+    what = set = None
 
     def __init__(self, mode):
-        if mode not in _PRECISIONS:
-            raise ValueError("train precision must be one of %s, got %r" % (sorted(_PRECISIONS), mode))
+        _check_mode(self.what, mode)
         self.mode = mode
         self._prev = None
 
     def __enter__(self):
-        self._prev = set_train_precision(self.mode)
+        self._prev = self.set(self.mode)
         return self
 
     def __exit__(self, *exc):
-        set_train_precision(self._prev)
+        self.set(self._prev)
         return False
+
+
+class forward_precision(_precision_scope):
+    """``with forward_precision("fp16"): ...`` -- inference forwards with fp16 operands.  A conv that
+    records a tape (training) inside raises: the backward kernels assume an fp32 forward."""
+    what, set = "forward", staticmethod(set_forward_precision)
+
+
+class train_precision(_precision_scope):
+    """``with train_precision("fp16"): ...`` -- training steps with fp16 conv operands (forward and
+    data gradient)."""
+    what, set = "train", staticmethod(set_train_precision)
 
 
 def _check_precision(tape):
@@ -692,24 +701,41 @@ def conv2d(tape, x, weight, bias, co, stride=1, pad=0, dil=1, out=None, tag=None
                                    wsb.data_ptr(), wsb.numel(), s), "gs_colsum")
             _notify(bias)
         if x.requires_grad:
-            acc = x.g is not None
-            if not acc:
-                x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+            acc = _input_grad(x)
             _lib.check(L.gs_conv2d_dgrad(ctypes.byref(d), dy.data_ptr(), weight.data_ptr(),
-                                         x.g.data_ptr(), 1 if acc else 0, ws_b.data_ptr(),
+                                         x.g.data_ptr(), acc, ws_b.data_ptr(),
                                          ws_b.numel(), s), "gs_conv2d_dgrad")
 
     tape.record(backward)
     return out
 
 
-def _alloc_parent_grad(a):
-    """Gradient storage for a channel slice: allocate (zeroed) on the owning buffer."""
-    root = a
+def _input_grad(x):
+    """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
+    x.g already held a contribution, else 0 after allocating it (a channel slice's storage is
+    allocated, zeroed, on the buffer that owns it)."""
+    if x.g is not None:
+        return 1
+    root = x
     while root.parent is not None:
         root = root.parent
-    if root.g is None:
+    if root is x:
+        x.new_grad()
+    elif root.g is None:
         root.new_grad().zero_()
+    return 0
+
+
+def _pass_residual_grad(L, residual, src, rows, C, stream):
+    """Hand the gradient ``src`` of an identity edge to ``residual``: aliased as residual.g when it
+    is the first contribution and the layouts match, else copied (added where residual.g holds a
+    contribution or is a slice of a zeroed buffer)."""
+    if residual.g is None and residual.parent is None and src.stride() == residual.t.stride():
+        residual.g = src
+        return
+    acc = 1 if (_input_grad(residual) or residual.parent is not None) else 0
+    _lib.check(L.gs_copy2d(src.data_ptr(), src.stride(2), residual.g.data_ptr(),
+                           residual.g.stride(2), rows, C, 1.0, acc, stream), "gs_copy2d")
 
 
 class BNParams:
@@ -865,7 +891,7 @@ def batchnorm(tape, x, bn, relu=False, residual=None, out=None, inplace=False):
         mask_apply = 0 if want_g else mask  # dy already masked in place
         if x.g is not None:
             raise RuntimeError("BN input has more than one consumer; unsupported")
-        x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        _input_grad(x)
         _lib.check(L.gs_bn_bwd_apply(dy.data_ptr(), dy.stride(2), x.ptr, x.ld, out.ptr, out.ld,
                                      rows, C, coeffs_ptr, bsums.data_ptr(), bcount,
                                      mask_apply, 1 if use_batch else 0, x.g.data_ptr(),
@@ -877,17 +903,8 @@ def batchnorm(tape, x, bn, relu=False, residual=None, out=None, inplace=False):
         if bgrad:
             _notify(bn.bias)
         if residual is not None and residual.requires_grad:
-            src = dy  # masked (relu) or plain (no relu) upstream gradient
-            if residual.g is None and residual.parent is None and src.stride() == residual.t.stride():
-                residual.g = src
-            else:
-                if residual.g is None:
-                    residual.new_grad() if residual.parent is None else _alloc_parent_grad(residual)
-                    acc = 0 if residual.parent is None else 1
-                else:
-                    acc = 1
-                _lib.check(L.gs_copy2d(src.data_ptr(), src.stride(2), residual.g.data_ptr(),
-                                       residual.g.stride(2), rows, C, 1.0, acc, s), "gs_copy2d")
+            # dy: the masked (relu) or plain (no relu) upstream gradient
+            _pass_residual_grad(L, residual, dy, rows, C, s)
 
     tape.record(backward)
     return out
@@ -1062,9 +1079,7 @@ def conv_bn(tape, x, weight, co, bn, stride=1, pad=0, dil=1, relu=False, residua
         acc = 0
         dx_ptr = None
         if x.requires_grad:
-            acc = 1 if x.g is not None else 0
-            if not acc:
-                x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+            acc = _input_grad(x)
             dx_ptr = x.g.data_ptr()
         fuse, fused_flag = None, None
         if x_bnb is not None and dx_ptr is not None and x.parent is None:
@@ -1110,17 +1125,8 @@ def conv_bn(tape, x, weight, co, bn, stride=1, pad=0, dil=1, relu=False, residua
         elif gw is not None:
             _notify(weight)
         if residual is not None and residual.requires_grad:
-            src = dz  # masked (relu) or plain (no relu) upstream gradient
-            if residual.g is None and residual.parent is None and src.stride() == residual.t.stride():
-                residual.g = src
-            else:
-                if residual.g is None:
-                    residual.new_grad() if residual.parent is None else _alloc_parent_grad(residual)
-                    racc = 0 if residual.parent is None else 1
-                else:
-                    racc = 1
-                _lib.check(L.gs_copy2d(src.data_ptr(), src.stride(2), residual.g.data_ptr(),
-                                       residual.g.stride(2), rows, C, 1.0, racc, s), "gs_copy2d")
+            # dz: the masked (relu) or plain (no relu) upstream gradient
+            _pass_residual_grad(L, residual, dz, rows, C, s)
 
     tape.record(backward)
     return out
@@ -1142,12 +1148,10 @@ def maxpool(tape, x, k=3, s=2, p=1):
         dy = out.g
         if dy is None or not x.requires_grad:
             return
-        acc = x.g is not None
-        if not acc:
-            x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        acc = _input_grad(x)
         _lib.check(L.gs_maxpool_backward(dy.data_ptr(), dy.stride(2), idx.data_ptr(), x.N, x.H, x.W,
                                          x.C, k, s, p, ho, wo, x.g.data_ptr(), x.g.stride(2),
-                                         1 if acc else 0, current_stream_ptr()),
+                                         acc, current_stream_ptr()),
                    "gs_maxpool_backward")
 
     tape.record(backward)
@@ -1168,11 +1172,9 @@ def avgpool_ceil(tape, x, s):
         dy = out.g
         if dy is None or not x.requires_grad:
             return
-        acc = x.g is not None
-        if not acc:
-            x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        acc = _input_grad(x)
         _lib.check(L.gs_avgpool_ceil_backward(dy.data_ptr(), dy.stride(2), x.N, x.H, x.W, x.C, s,
-                                              x.g.data_ptr(), x.g.stride(2), 1 if acc else 0,
+                                              x.g.data_ptr(), x.g.stride(2), acc,
                                               current_stream_ptr()), "gs_avgpool_ceil_backward")
 
     tape.record(backward)
@@ -1189,11 +1191,9 @@ def copy_into(tape, x, dst):
         dg = dst.g
         if dg is None or not x.requires_grad:
             return
-        acc = x.g is not None
-        if not acc:
-            x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        acc = _input_grad(x)
         _lib.check(L.gs_copy2d(dg.data_ptr(), dg.stride(2), x.g.data_ptr(), x.g.stride(2), x.rows,
-                               x.C, 1.0, 1 if acc else 0, current_stream_ptr()), "gs_copy2d")
+                               x.C, 1.0, acc, current_stream_ptr()), "gs_copy2d")
 
     tape.record(backward)
     return dst
@@ -1230,11 +1230,9 @@ def adaptive_avgpool(tape, x, scales):
             if o.g is not None:
                 gbuf[off2:off2 + n_el].view(x.N, s, s, x.C).copy_(o.g)
             off2 += n_el
-        acc = x.g is not None
-        if not acc:
-            x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        acc = _input_grad(x)
         _lib.check(L.gs_adaptive_avgpool_backward(gbuf.data_ptr(), x.N, x.H, x.W, x.C, arr, ns,
-                                                  x.g.data_ptr(), x.g.stride(2), 1 if acc else 0,
+                                                  x.g.data_ptr(), x.g.stride(2), acc,
                                                   current_stream_ptr()),
                    "gs_adaptive_avgpool_backward")
 
@@ -1259,13 +1257,11 @@ def bilinear(tape, x, size, align_corners=False, out=None, accumulate=False):
         dy = out.g
         if dy is None or not x.requires_grad:
             return
-        acc = x.g is not None
-        if not acc:
-            x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        acc = _input_grad(x)
         nb = L.gs_bilinear_backward_workspace_bytes(x.N, x.H, x.W, x.C, ho, wo)
         ws = _ws.get(nb, dev)
         _lib.check(L.gs_bilinear_backward(dy.data_ptr(), dy.stride(2), x.N, x.H, x.W, x.C, ho, wo,
-                                          al, x.g.data_ptr(), x.g.stride(2), 1 if acc else 0,
+                                          al, x.g.data_ptr(), x.g.stride(2), acc,
                                           ws.data_ptr(), ws.numel(), current_stream_ptr()),
                    "gs_bilinear_backward")
 
@@ -1293,7 +1289,7 @@ def dropout2d(tape, x, p, training, generator=None):
             return
         if x.g is not None:
             raise RuntimeError("dropout input has more than one consumer; unsupported")
-        x.new_grad() if x.parent is None else _alloc_parent_grad(x)
+        _input_grad(x)
         _lib.check(L.gs_scale_nc(dy.data_ptr(), dy.stride(2), mask.data_ptr(), x.N, ppi, x.C,
                                  x.g.data_ptr(), x.g.stride(2), current_stream_ptr()),
                    "gs_scale_nc")
@@ -1310,16 +1306,7 @@ def add_grad_passthrough(tape, src, dst):
         dg = dst.g
         if dg is None or not src.requires_grad:
             return
-        if src.g is None and src.parent is None and dg.stride() == src.t.stride():
-            src.g = dg
-            return
-        acc = src.g is not None
-        if not acc:
-            src.new_grad() if src.parent is None else _alloc_parent_grad(src)
-            acc = src.parent is not None
-        _lib.check(L.gs_copy2d(dg.data_ptr(), dg.stride(2), src.g.data_ptr(), src.g.stride(2),
-                               src.rows, src.C, 1.0, 1 if acc else 0, current_stream_ptr()),
-                   "gs_copy2d")
+        _pass_residual_grad(L, src, dg, src.rows, src.C, current_stream_ptr())
 
     tape.record(backward)
 

@@ -212,7 +212,7 @@ class Tape:
         for fn in reversed(ops):
             fn()
         from . import ops as _ops
-        if _ops.DEFER_JOIN:
+        if _ops._deferred is not None:
             _ops.flush_wgrads()        # the caller joins (runner: after the early part of the SGD step)
         else:
             _ops.join_side_streams()   # weight gradients queued on the side stream

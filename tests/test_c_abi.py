@@ -55,6 +55,22 @@ def test_descriptor_struct_sizes_match_header():
     assert ctypes.sizeof(lib.SlideDesc) == 16 * 4
 
 
+def test_conv_desc_is_the_one_constructor():
+    """lib.conv_desc: defaults, the output size and the packed-NHWC strides; ops._conv_desc fills the
+    same bytes for an activation of the same geometry."""
+    import torch
+    from gaia_seg_amd.hip import ops
+    from gaia_seg_amd.hip.runtime import Act
+    d = lib.conv_desc(1, 5, 7, 8, 12, 3, stride=2, dil=2, ldx=12, ci_max=16, co_ld=16)
+    assert (d.pad, d.Ho, d.Wo) == (2, 3, 4)
+    assert (d.x_sn, d.x_sh, d.x_sw, d.x_sc) == (5 * 7 * 12, 7 * 12, 12, 1)
+    assert (d.Ci_max, d.Co_ld, d.ldy) == (16, 16, 12)
+    assert d.in_affine is None
+    x = Act(torch.empty(1, 5, 7, 12)[..., :8])
+    weight = torch.empty(3, 3, 16, 16).permute(3, 2, 0, 1)   # logical OIHW on HWIO storage
+    assert bytes(ops._conv_desc(x, weight, 12, 2, 2, 2, 12)) == bytes(d)
+
+
 def test_argument_validation_needs_no_gpu():
     """Bad descriptors are rejected before any launch (return codes, not exceptions)."""
     L = lib.load()
@@ -115,12 +131,12 @@ def test_x3_dgrad_cases_pass_the_dispatch_gate_without_gpu():
     GPU test re-checks it against the launch that really happened)."""
     if os.environ.get("GS_X3", "4") == "0":
         pytest.skip("bf16x3 switched off")
-    from test_dgrad_x3_gpu import X3_CASES, _desc
+    from test_dgrad_x3_gpu import X3_CASES
     L = lib.load()
     seen_bn, seen_split, seen_odd = set(), False, False
     for case in X3_CASES:
         n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy, acc, force = case
-        d = _desc(lib, n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy)
+        d = lib.conv_desc(n, h, w, ci, co, k, dil=dil, ci_max=ci_max, co_ld=co_ld, ldx=ldx, ldy=ldy)
         if force:
             assert L.gs_debug_force_plan(*force) == 0
         q = lib.DebugLaunch()
@@ -139,7 +155,7 @@ def test_x3_dgrad_cases_pass_the_dispatch_gate_without_gpu():
         seen_odd |= q.splits == 1 and q.ksteps_per_split % 2 == 1
     assert seen_bn == {64, 48} and seen_split and seen_odd
     # forward and weight gradient of a bf16x3 data-gradient shape stay on the fp32 loops
-    d = _desc(lib, 2, 64, 64, 1024, 256, 1, 1, 1024, 256, 1024, 256)
+    d = lib.conv_desc(2, 64, 64, 1024, 256, 1)
     assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_DGRAD, ctypes.byref(q)) == 0
     assert q.kloop == lib.KLOOP_BF16X3
     for op in (lib.OP_FORWARD, lib.OP_WGRAD):
@@ -154,26 +170,31 @@ def test_stream_1x1_cases_dispatch_without_gpu():
     stage-3/4 shapes and the 3x3s do not."""
     if os.environ.get("GS_STREAM", "1") == "0":
         pytest.skip("streaming kernel switched off")
-    from test_stream_1x1_gpu import STREAM_CASES, _sdesc
+    from test_stream_1x1_gpu import STREAM_CASES
     L = lib.load()
     q = lib.DebugLaunch()
     widths = set()
     # production dispatch (mode 1): one column block, short data-gradient contractions
-    d = _sdesc(lib, STREAM_CASES[0])      # 64 -> 256 at 2 x 128 x 256
+    d = _stream_desc(STREAM_CASES[0])     # 64 -> 256 at 2 x 128 x 256
     assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_FORWARD, ctypes.byref(q)) == 0
     assert q.kloop == lib.KLOOP_STREAM and q.bn == 256
     assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_DGRAD, ctypes.byref(q)) == 0
     assert q.kloop == lib.KLOOP_BF16X3    # K = 256: stays on the tile kernel's bf16x3 loop
     assert L.gs_debug_set_stream_mode(2) == 0 and L.gs_debug_set_stream_mode(5) == -1
     try:
-        _stream_all_shapes(L, STREAM_CASES, _sdesc, q, widths)
+        _stream_all_shapes(L, STREAM_CASES, q, widths)
     finally:
         L.gs_debug_set_stream_mode(-1)
 
 
-def _stream_all_shapes(L, STREAM_CASES, _sdesc, q, widths):
+def _stream_desc(case):
+    n, h, w, ci, co, ci_max, co_ld, ldx, ldy = case[:9]
+    return lib.conv_desc(n, h, w, ci, co, 1, ci_max=ci_max, co_ld=co_ld, ldx=ldx, ldy=ldy)
+
+
+def _stream_all_shapes(L, STREAM_CASES, q, widths):
     for case in STREAM_CASES:
-        d = _sdesc(lib, case)
+        d = _stream_desc(case)
         for op in case[-1]:
             assert L.gs_debug_query_conv_launch(ctypes.byref(d), op, ctypes.byref(q)) == 0
             assert q.kloop == lib.KLOOP_STREAM and q.bm == 128 and q.splits == 1, (case, op)
@@ -181,8 +202,6 @@ def _stream_all_shapes(L, STREAM_CASES, _sdesc, q, widths):
     assert widths == {64, 128, 256}
     for n, h, w, ci, co, k in [(2, 32, 64, 256, 1024, 1), (2, 16, 32, 2048, 512, 1), (2, 128, 256, 64, 64, 3),
                                (2, 64, 128, 512, 128, 1)]:
-        d = lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci, Co_ld=co, KH=k, KW=k, stride=1, pad=k // 2,
-                         dil=1, Ho=h, Wo=w, x_sn=h * w * ci, x_sh=w * ci, x_sw=ci, x_sc=1, ldy=co,
-                         ld_add=0, role=0, reserved=0, in_affine=None)
+        d = lib.conv_desc(n, h, w, ci, co, k)
         assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_FORWARD, ctypes.byref(q)) == 0
         assert q.kloop != lib.KLOOP_STREAM

@@ -28,13 +28,6 @@ TOL = 3e-5
 X3_ON = os.environ.get("GS_X3", "4") != "0"
 
 
-def _desc(lib, n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy):
-    p = dil * (k // 2)
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci_max, Co_ld=co_ld, KH=k, KW=k, stride=1,
-                        pad=p, dil=dil, Ho=h, Wo=w, x_sn=h * w * ldx, x_sh=w * ldx, x_sw=ldx, x_sc=1,
-                        ldy=ldy, ld_add=0, role=0, reserved=0, in_affine=None)
-
-
 def _launch_record(lib, L):
     rec = lib.DebugLaunch()
     assert L.gs_debug_last_conv_launch(ctypes.byref(rec)) == 0
@@ -83,7 +76,7 @@ def _run_case(hip_lib, case, expect=None):
     dy_buf[..., :co] = dy.to(DEV)
     prior = torch.randn(n, h, w, ldx)
     dx_buf = prior.to(DEV).clone()
-    d = _desc(lib, n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy)
+    d = lib.conv_desc(n, h, w, ci, co, k, dil=dil, ci_max=ci_max, co_ld=co_ld, ldx=ldx, ldy=ldy)
     if force:
         assert hip_lib.gs_debug_force_plan(*force) == 0
     try:

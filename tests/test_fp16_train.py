@@ -9,14 +9,6 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _x3_desc(lib, case):
-    n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy, acc, force = case
-    p = dil * (k // 2)
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci_max, Co_ld=co_ld, KH=k, KW=k, stride=1,
-                        pad=p, dil=dil, Ho=h, Wo=w, x_sn=h * w * ldx, x_sh=w * ldx, x_sw=ldx, x_sc=1,
-                        ldy=ldy, ld_add=0, role=0, reserved=0, in_affine=None)
-
-
 def _query(L, lib, d, op):
     q = lib.DebugLaunch()
     assert L.gs_debug_query_conv_launch(ctypes.byref(d), op, ctypes.byref(q)) == 0
@@ -29,7 +21,11 @@ def test_train_precision_dispatch_without_gpu():
     L = lib.load()
     assert L.gs_get_train_precision() == 0
     assert L.gs_set_train_precision(2) == -1 and L.gs_set_train_precision(-1) == -1
-    descs = [(case, _x3_desc(lib, case)) for case in X3_CASES]
+    descs = []
+    for case in X3_CASES:
+        n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy = case[:11]
+        descs.append((case, lib.conv_desc(n, h, w, ci, co, k, dil=dil, ci_max=ci_max, co_ld=co_ld,
+                                          ldx=ldx, ldy=ldy)))
     ops_ = (lib.OP_FORWARD, lib.OP_DGRAD, lib.OP_WGRAD)
     for case, d in descs:
         if case[-1]:

@@ -34,18 +34,10 @@ CASES = [
 ]
 
 
-def _desc(lib, n, h, w, ci, co, k, s, dil, ldx):
-    p = dil * (k // 2)
-    ho, wo = (h + 2 * p - dil * (k - 1) - 1) // s + 1, (w + 2 * p - dil * (k - 1) - 1) // s + 1
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci, Co_ld=co, KH=k, KW=k, stride=s, pad=p,
-                        dil=dil, Ho=ho, Wo=wo, x_sn=h * w * ldx, x_sh=w * ldx, x_sw=ldx, x_sc=1, ldy=co,
-                        ld_add=0, role=0, reserved=0, in_affine=None)
-
-
 def _dgrad(hip_lib, lib, case, dy, w_log, train_mode):
     from gaia_seg_amd.hip.runtime import current_stream_ptr
     n, h, wd, ci, co, k, s, dil, ldx, force = case
-    d = _desc(lib, n, h, wd, ci, co, k, s, dil, ldx)
+    d = lib.conv_desc(n, h, wd, ci, co, k, s, dil, ldx=ldx)
     w_phys = w_log.permute(2, 3, 1, 0).contiguous().to(DEV)
     dx = torch.full((n, h, wd, ldx), 7.0, device=DEV)
     hip_lib.gs_debug_set_stream_mode(0)

@@ -33,14 +33,6 @@ CASES = [
 ]
 
 
-def _desc(lib, n, h, w, ci, co, k, s, dil):
-    p = dil * (k // 2)
-    ho, wo = (h + 2 * p - dil * (k - 1) - 1) // s + 1, (w + 2 * p - dil * (k - 1) - 1) // s + 1
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci, Co_ld=co, KH=k, KW=k, stride=s, pad=p,
-                        dil=dil, Ho=ho, Wo=wo, x_sn=h * w * ci, x_sh=w * ci, x_sw=ci, x_sc=1, ldy=co,
-                        ld_add=0, role=0, reserved=0, in_affine=None)
-
-
 def _affine(ci, g):
     # powers of two: (x - mean) * scale is exact, so fused or not, the loader rounds once (+ beta)
     scale = torch.pow(2.0, torch.randint(-1, 2, (ci,), generator=g).float())
@@ -59,7 +51,7 @@ def _act(x, coeffs):
 def _run(hip_lib, lib, case, x, w_log, coeffs):
     from gaia_seg_amd.hip.runtime import current_stream_ptr
     n, h, wd, ci, co, k, s, dil, aff, force = case
-    d = _desc(lib, n, h, wd, ci, co, k, s, dil)
+    d = lib.conv_desc(n, h, wd, ci, co, k, s, dil)
     xd = x.to(DEV).contiguous()
     wd_phys = w_log.permute(2, 3, 1, 0).contiguous().to(DEV)
     cd = coeffs.to(DEV).contiguous() if aff else None

@@ -33,13 +33,6 @@ FWD_X3_CASES = [
 ]
 
 
-def _desc(lib, n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy):
-    p = dil * (k // 2)
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci_max, Co_ld=co_ld, KH=k, KW=k, stride=1,
-                        pad=p, dil=dil, Ho=h, Wo=w, x_sn=h * w * ldx, x_sh=w * ldx, x_sw=ldx, x_sc=1,
-                        ldy=ldy, ld_add=0, role=0, reserved=0, in_affine=None)
-
-
 @pytest.mark.parametrize("x3", [True, False], ids=["bf16x3", "fp32"])
 @pytest.mark.parametrize("case", FWD_X3_CASES, ids=lambda c: "x".join(str(v) for v in c[:7]))
 def test_forward_on_the_bf16x3_loop_matches_conv2d(hip_lib, case, x3):
@@ -55,7 +48,7 @@ def test_forward_on_the_bf16x3_loop_matches_conv2d(hip_lib, case, x3):
     x_buf[..., :ci] = x.to(DEV)
     prior = torch.randn(n, h, w, ldy)
     y_buf = prior.to(DEV).clone()
-    d = _desc(lib, n, h, w, ci, co, k, dil, ci_max, co_ld, ldx, ldy)
+    d = lib.conv_desc(n, h, w, ci, co, k, dil=dil, ci_max=ci_max, co_ld=co_ld, ldx=ldx, ldy=ldy)
     hip_lib.gs_debug_set_x3_fwd(2 if x3 else 0)
     hip_lib.gs_debug_set_stream_mode(0)        # (the 1x1 cases are about the tile kernel's loops)
     if force:

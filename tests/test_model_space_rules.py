@@ -151,11 +151,7 @@ def _r50_eval_descs(lib):
             if first:
                 convs.append((h, w, ci, cout, 1, s, False))
             for (hh, ww, c_in, c_out, k, st, aff) in convs:
-                hq, wq = (hh + 2 * (k // 2) - k) // st + 1, (ww + 2 * (k // 2) - k) // st + 1
-                d = lib.ConvDesc(N=1, H=hh, W=ww, Ci=c_in, Co=c_out, Ci_max=c_in, Co_ld=c_out, KH=k, KW=k,
-                                 stride=st, pad=k // 2, dil=1, Ho=hq, Wo=wq, x_sn=hh * ww * c_in,
-                                 x_sh=ww * c_in, x_sw=c_in, x_sc=1, ldy=c_out, ld_add=0,
-                                 role=1 if k == 3 else 0, reserved=0, in_affine=None)
+                d = lib.conv_desc(1, hh, ww, c_in, c_out, k, st, role=1 if k == 3 else 0)
                 out.append(("s%d %dx%d %d->%d" % (stage + 1, k, k, c_in, c_out), d, aff))
             if first:
                 h, w = ho, wo

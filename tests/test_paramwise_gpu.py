@@ -338,9 +338,8 @@ def _instalments(runner):
     """The range lists ArenaOptimizerHook steps, by its own rule: early then late when the
     weight-gradient stream left a checkpoint in the step that just ran and there is an early part,
     else the merged ranges in one go."""
-    from gaia_seg_amd.hip import ops
     early, late = runner.split_ranges()
-    if ops.SIDE_CHECKPOINT is not None and early:
+    if runner.last_checkpoint is not None and early:
         return [early, late]
     return [runner.active_ranges]
 

@@ -225,3 +225,50 @@ def test_high_priority_training_stream_is_bitwise_the_same_training(hip_lib):
     assert torch.equal(p0, p1) and torch.equal(m0, m1)
     assert b0.keys() == b1.keys() and all(torch.equal(b0[k], b1[k]) for k in b0)
     assert float(m1.abs().max()) > 0
+
+
+def test_prepare_graphs_is_the_same_training_as_capturing_at_first_sight(hip_lib):
+    """IterBasedRunner.prepare_graphs captures the anchors' step graphs ahead of time: one real eager
+    step first (none has run yet), then one captured step per anchor, the previous arch restored.
+    The same steps driven through train_iter -- eager, capture at the anchor's second sight, capture
+    of the next anchor at first sight -- are the same launches on the same data, so after two
+    replayed steps on another batch parameters and momentum must be BIT-identical and the graph
+    counters equal.  (The heads' dropout ratio is 0: no RNG stream is involved.)"""
+    from gaia_seg_amd.models import build_segmentor
+    anchors = [_anchor("sub"), _anchor("min")]
+
+    def run(prepare):
+        torch.manual_seed(0)
+        model = build_segmentor(copy.deepcopy(model_cfg(fcn_head()))).cuda().train()
+        runner, arena = _runner(model)
+        runner.graphs_enabled = True
+        runner.set_arch(_anchor("max"))
+        before = (runner.arch_key, runner.arch_name, [tuple(r) for r in runner.active_ranges])
+        captured = None
+        if prepare:
+            captured = runner.prepare_graphs(anchors, _batch(0))
+            assert (runner.arch_key, runner.arch_name, [tuple(r) for r in runner.active_ranges]) == before
+        else:
+            for meta in (anchors[0], anchors[0], anchors[1]):
+                runner.set_arch(meta)
+                runner.train_iter(_batch(0))
+        for meta in anchors:
+            runner.set_arch(meta)
+            runner.train_iter(_batch(1))
+        torch.cuda.synchronize()
+        return captured, dict(runner.graph_stats), arena.flat_param.clone(), arena.flat_mom.clone()
+
+    default = torch.cuda.default_stream()
+    try:
+        n_a, st_a, p_a, m_a = run(True)
+        torch.cuda.synchronize()
+        torch.cuda.set_stream(default)
+        n_b, st_b, p_b, m_b = run(False)
+    finally:
+        torch.cuda.synchronize()
+        torch.cuda.set_stream(default)
+    assert n_a == 2
+    assert st_a == {"captured": 2, "replayed": 2, "eager": 1} and st_b == st_a, (st_a, st_b)
+    assert torch.equal(p_a.view(torch.int32), p_b.view(torch.int32))
+    assert torch.equal(m_a.view(torch.int32), m_b.view(torch.int32))
+    assert float(m_a.abs().max()) > 0

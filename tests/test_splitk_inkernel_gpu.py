@@ -56,18 +56,6 @@ def splitk_mode(hip_lib):
     hip_lib.gs_debug_set_splitk_inkernel(-1)
 
 
-def _desc(lib, n, h, w, ci, co, k, stride=1, dil=1, ci_max=None, co_ld=None, ldx=None, ldy=None,
-          ld_add=0, role=0):
-    p = dil * (k // 2)
-    ho = (h + 2 * p - dil * (k - 1) - 1) // stride + 1
-    wo = (w + 2 * p - dil * (k - 1) - 1) // stride + 1
-    ldx = ldx or ci
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci_max or ci, Co_ld=co_ld or co, KH=k, KW=k,
-                        stride=stride, pad=p, dil=dil, Ho=ho, Wo=wo, x_sn=h * w * ldx, x_sh=w * ldx,
-                        x_sw=ldx, x_sc=1, ldy=ldy or co, ld_add=ld_add, role=role, reserved=0,
-                        in_affine=None), ho, wo
-
-
 def _same(a, b, splits):
     """bit equality where the reduce launch sums in split order too (its sequential form)"""
     if splits < 16:
@@ -96,7 +84,7 @@ FWD_CASES = [
 def _fwd_once(hip_lib, lib, case, x, w_phys, bias, addend, y_buf):
     from gaia_seg_amd.hip.runtime import current_stream_ptr
     n, h, w, ci, co, k, has_b, has_a, ldy_extra, role = case
-    d, ho, wo = _desc(lib, n, h, w, ci, co, k, ldy=co + ldy_extra, ld_add=co if has_a else 0, role=role)
+    d = lib.conv_desc(n, h, w, ci, co, k, ldy=co + ldy_extra, ld_add=co if has_a else 0, role=role)
     need = hip_lib.gs_conv2d_workspace_bytes(ctypes.byref(d))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=DEV)
     lib.check(hip_lib.gs_conv2d_forward(ctypes.byref(d), x.data_ptr(), w_phys.data_ptr(),
@@ -192,7 +180,8 @@ def test_dgrad_combined_in_the_launch_is_bit_identical_to_the_reduce_launch(hip_
     n, h, w, ci, co, k, stride, acc, ldx_extra = case
     torch.manual_seed(5)
     w_log = torch.randn(co, ci, k, k) * 0.1
-    d, ho, wo = _desc(lib, n, h, w, ci, co, k, stride=stride, ldx=ci + ldx_extra)
+    d = lib.conv_desc(n, h, w, ci, co, k, stride=stride, ldx=ci + ldx_extra)
+    ho, wo = d.Ho, d.Wo
     dy = torch.randn(n, ho, wo, co)
     x_ref = torch.zeros(n, ci, h, w, requires_grad=True)
     F.conv2d(x_ref, w_log, None, stride, k // 2).backward(dy.permute(0, 3, 1, 2))

@@ -52,13 +52,6 @@ STREAM_CASES = [
 ]
 
 
-def _sdesc(lib, case):
-    n, h, w, ci, co, ci_max, co_ld, ldx, ldy = case[:9]
-    return lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci_max, Co_ld=co_ld, KH=1, KW=1, stride=1,
-                        pad=0, dil=1, Ho=h, Wo=w, x_sn=h * w * ldx, x_sh=w * ldx, x_sw=ldx, x_sc=1,
-                        ldy=ldy, ld_add=0, role=0, reserved=0, in_affine=None)
-
-
 def _expect(lib, rec):
     if STREAM_ON:
         assert rec.kloop == lib.KLOOP_STREAM, "case does not reach the streaming kernel (%d)" % rec.kloop
@@ -74,7 +67,7 @@ def test_stream_kernel_matches_conv2d(hip_lib, case):
     torch.manual_seed(99)
     w_log = torch.randn(co_ld, ci_max, 1, 1) * 0.2
     w_phys = w_log.permute(2, 3, 1, 0).contiguous().to(DEV)
-    d = _sdesc(lib, case)
+    d = lib.conv_desc(n, h, w, ci, co, 1, ci_max=ci_max, co_ld=co_ld, ldx=ldx, ldy=ldy)
     need = hip_lib.gs_conv2d_workspace_bytes(ctypes.byref(d))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=DEV)
     rec = lib.DebugLaunch()

@@ -56,16 +56,12 @@ def main():
     ks_list = [int(v) for v in args.ks.split(",")]
     rows = []
     for name, n, h, w, ci, co, k, stride in shapes(ks_list, widths):
-        p = k // 2
-        ho, wo = (h + 2 * p - k) // stride + 1, (w + 2 * p - k) // stride + 1
+        d = lib.conv_desc(n, h, w, ci, co, k, stride)
         x = torch.randn(n, h, w, ci, device=dev)
-        y = torch.randn(n, ho, wo, co, device=dev)
+        y = torch.randn(n, d.Ho, d.Wo, co, device=dev)
         wt = torch.randn(k, k, ci, co, device=dev) * 0.05
         dx = torch.zeros_like(x)
         dw = torch.zeros_like(wt)
-        d = lib.ConvDesc(N=n, H=h, W=w, Ci=ci, Co=co, Ci_max=ci, Co_ld=co, KH=k, KW=k, stride=stride,
-                         pad=p, dil=1, Ho=ho, Wo=wo, x_sn=h * w * ci, x_sh=w * ci, x_sw=ci, x_sc=1,
-                         ldy=co, ld_add=0, role=0, reserved=0, in_affine=None)
         need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
         ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
         calls = {
@@ -76,7 +72,7 @@ def main():
             "wgrad": lambda: L.gs_conv2d_wgrad(ctypes.byref(d), x.data_ptr(), y.data_ptr(), dw.data_ptr(),
                                                ws.data_ptr(), ws.numel(), st),
         }
-        fl = 2.0 * n * ho * wo * ci * co * k * k
+        fl = 2.0 * n * d.Ho * d.Wo * ci * co * k * k
         by = 4.0 * (x.numel() + y.numel() + wt.numel())
         for op in args.ops.split(","):
             run = calls[op]

@@ -97,20 +97,16 @@ def bench_shapes(args, L):
                 ph, pw = RES[s - 1]
                 cases.append(("%s s%d.0 conv2 3x3/2 %d" % (wname, s + 1, wd), ph, pw, wd, wd, 3, 2, True))
             for name, hh, ww, ci, co, k, stride, aff in cases:
-                p = k // 2
-                ho, wo = (hh + 2 * p - k) // stride + 1, (ww + 2 * p - k) // stride + 1
+                d = lib.conv_desc(1, hh, ww, ci, co, k, stride, role=1 if k == 3 else 0)
                 x = torch.randn(1, hh, ww, ci, device=dev)
-                y = torch.empty(1, ho, wo, co, device=dev)
+                y = torch.empty(1, d.Ho, d.Wo, co, device=dev)
                 wt = torch.randn(k, k, ci, co, device=dev) * 0.05
                 coeffs = torch.stack([torch.ones(ci), torch.zeros(ci), torch.zeros(ci), torch.ones(ci)]).to(dev)
-                d = lib.ConvDesc(N=1, H=hh, W=ww, Ci=ci, Co=co, Ci_max=ci, Co_ld=co, KH=k, KW=k, stride=stride,
-                                 pad=p, dil=1, Ho=ho, Wo=wo, x_sn=hh * ww * ci, x_sh=ww * ci, x_sw=ci, x_sc=1,
-                                 ldy=co, ld_add=0, role=1 if k == 3 else 0, reserved=0, in_affine=None)
                 if aff and L.gs_conv2d_in_affine_supported(ctypes.byref(d)):
                     d.in_affine = coeffs.data_ptr()
                 need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
                 wsb = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-                fl = 2.0 * ho * wo * ci * co * k * k
+                fl = 2.0 * d.Ho * d.Wo * ci * co * k * k
                 out = [name]
                 for mode in (0, 1):
                     L.gs_set_forward_precision(mode)

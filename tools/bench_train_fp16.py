@@ -129,14 +129,10 @@ def bench_shapes(args, L):
                 ph, pw = RES[s - 1]
                 cases.append(("%s s%d.0 conv2 3x3/2 %d" % (wname, s + 1, wd), ph, pw, wd, wd, 3, 2))
             for name, hh, ww, ci, co, k, stride in cases:
-                p = k // 2
-                ho, wo = (hh + 2 * p - k) // stride + 1, (ww + 2 * p - k) // stride + 1
-                dy = torch.randn(N, ho, wo, co, device=dev)
+                d = lib.conv_desc(N, hh, ww, ci, co, k, stride)
+                dy = torch.randn(N, d.Ho, d.Wo, co, device=dev)
                 dx = torch.empty(N, hh, ww, ci, device=dev)
                 wt = torch.randn(k, k, ci, co, device=dev) * 0.05
-                d = lib.ConvDesc(N=N, H=hh, W=ww, Ci=ci, Co=co, Ci_max=ci, Co_ld=co, KH=k, KW=k,
-                                 stride=stride, pad=p, dil=1, Ho=ho, Wo=wo, x_sn=hh * ww * ci, x_sh=ww * ci,
-                                 x_sw=ci, x_sc=1, ldy=co, ld_add=0, role=0, reserved=0, in_affine=None)
                 need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
                 wsb = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
                 fl = 2.0 * N * hh * ww * ci * co * k * k / (stride * stride)

@@ -32,12 +32,7 @@ def main():
         x = torch.randn(n, h, w, ci, device=dev)
         dy = torch.randn(n, h, w, co, device=dev)
         dw = torch.zeros(k, k, ci, co, device=dev)
-        d = lib.ConvDesc()
-        d.N, d.H, d.W, d.Ci, d.Co = n, h, w, ci, co
-        d.Ci_max, d.Co_ld, d.KH, d.KW = ci, co, k, k
-        d.stride, d.pad, d.dil, d.Ho, d.Wo = 1, k // 2, 1, h, w
-        d.x_sn, d.x_sh, d.x_sw, d.x_sc = h * w * ci, w * ci, ci, 1
-        d.ldy = co
+        d = lib.conv_desc(n, h, w, ci, co, k)
         need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
         ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
 

@@ -52,8 +52,7 @@ FIELDS = ("N", "H", "W", "Ci", "Co", "Ci_max", "Co_ld", "K", "stride", "pad", "d
           "role", "in_affine", "nchw")
 
 
-def _out(h, k, s, p, d):
-    return (h + 2 * p - d * (k - 1) - 1) // s + 1
+_out = lib.conv_out_size
 
 
 def grid():
@@ -113,19 +112,10 @@ def grid():
 
 def make_desc(row):
     f = dict(zip(FIELDS, row))
-    d = lib.ConvDesc()
-    d.N, d.H, d.W, d.Ci, d.Co = f["N"], f["H"], f["W"], f["Ci"], f["Co"]
-    d.Ci_max, d.Co_ld, d.KH, d.KW = f["Ci_max"], f["Co_ld"], f["K"], f["K"]
-    d.stride, d.pad, d.dil = f["stride"], f["pad"], f["dil"]
-    d.Ho = _out(f["H"], f["K"], f["stride"], f["pad"], f["dil"])
-    d.Wo = _out(f["W"], f["K"], f["stride"], f["pad"], f["dil"])
+    d = lib.conv_desc(f["N"], f["H"], f["W"], f["Ci"], f["Co"], f["K"], f["stride"], f["dil"], f["pad"],
+                      f["Ci_max"], f["Co_ld"], f["x_sw"], f["ldy"], role=f["role"])
     if f["nchw"]:
         d.x_sw, d.x_sh, d.x_sc, d.x_sn = 1, f["W"], f["H"] * f["W"], f["Ci"] * f["H"] * f["W"]
-    else:
-        d.x_sc, d.x_sw = 1, f["x_sw"]
-        d.x_sh = f["W"] * d.x_sw
-        d.x_sn = f["H"] * d.x_sh
-    d.ldy, d.ld_add, d.role, d.reserved = f["ldy"], 0, f["role"], 0
     d.in_affine = 0x1000 if f["in_affine"] else None      # never dereferenced by the queries
     return d
 

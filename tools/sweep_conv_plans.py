@@ -50,7 +50,7 @@ def main():
         gy = torch.randn_like(y.t)
         gx = torch.empty_like(x.t)
         gw = ops.ensure_grad(m.weight)
-        d = ops._conv_desc(x, m.weight, co, 1, k // 2, 1, y.ld)
+        d = lib.conv_desc(2, h, w, ci, co, k, co_ld=m.weight.stride(1), ldx=x.ld, ldy=y.ld)
         M = 2 * h * w
         for mode in args.modes.split(","):
             if mode == "wgrad":
