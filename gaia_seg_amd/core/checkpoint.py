@@ -36,6 +36,9 @@ def load_checkpoint(model, filename, map_location="cpu", strict=False, logger=No
     sd = ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
     own = model.state_dict()
+    # a DynamicDistiller checkpoint written by mmcv carries its frozen teacher; here the teacher is
+    # not part of any state_dict (models/segmentors/dynamic_distiller.py): such keys are dropped
+    sd = {k: v for k, v in sd.items() if k in own or not k.startswith("teacher_segmentor.")}
     missing = [k for k in own if k not in sd]
     unexpected = [k for k in sd if k not in own]
     with torch.no_grad():

@@ -78,7 +78,12 @@ def check_sandwich_model(model):
     out (the decode head's logits as 'teacher_logits', the auxiliary head's as 'aux_teacher_logits'):
     a PSP decode head and at most one FCN auxiliary head.  Anything else is refused here rather than
     guessed: an FCN decode head would read the auxiliary teacher's logits (another resolution), a
-    UPer head has no distillation branch (its reference forward_train takes no kwargs)."""
+    UPer head has no distillation branch (its reference forward_train takes no kwargs).  A fixed
+    teacher (DynamicDistiller) does not combine with the sandwich: its forward_train takes no teacher
+    logits."""
+    if getattr(model, "fixed_teacher", False):
+        raise ValueError("use_distillation (sandwich) with a %s is not supported: the segmentor "
+                         "distils from its own fixed teacher" % type(model).__name__)
     dec = model.decode_head
     if getattr(dec, "kd_teacher_key", None) != "teacher_logits":
         raise ValueError(
@@ -555,7 +560,8 @@ class IterBasedRunner:
         from ..hip import ops
         if (not self.graphs_enabled or self.graphs_paused or self.arch_key is None
                 or self.arch_key == ("current",) or gdist.world_size() != 1
-                or ops.RELU_TRACE is not None or ops.POOL_TRACE is not None or ops.TIMER is not None):
+                or ops.RELU_TRACE is not None or ops.POOL_TRACE is not None or ops.TIMER is not None
+                or not getattr(self.model, "step_graph_capturable", True)):
             return None
         sig = []
         for k in sorted(data_batch):

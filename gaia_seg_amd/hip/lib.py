@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class HipLibraryError(RuntimeError):
@@ -109,6 +109,25 @@ class KdDesc(Structure):
                 ("interpolation", c_int32), ("reserved", c_int32)]
 
 
+class DistillDesc(Structure):
+    """Mirror of ``gs_distill_desc``."""
+    _fields_ = [("N", c_int32), ("Cls", c_int32), ("hs", c_int32), ("ws", c_int32), ("ht", c_int32),
+                ("wt", c_int32), ("H", c_int32), ("W", c_int32), ("s_sn", c_int64), ("s_sh", c_int64),
+                ("s_sw", c_int64), ("s_sc", c_int64), ("t_sn", c_int64), ("t_sh", c_int64),
+                ("t_sw", c_int64), ("t_sc", c_int64), ("T", c_float), ("align_corners", c_int32)]
+
+
+PAIRWISE_MAX_P = 128   # GS_PAIRWISE_MAX_P
+
+
+class PairwiseDesc(Structure):
+    """Mirror of ``gs_pairwise_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("N", "Cs", "Ct", "H", "W", "Ht", "Wt", "y0", "y1", "x0", "x1",
+                                        "reserved")] +
+                [(k, c_int64) for k in ("s_sn", "s_sc", "s_sh", "s_sw", "t_sn", "t_sc", "t_sh", "t_sw")] +
+                [("T", c_float), ("reserved2", c_int32)])
+
+
 class SlideDesc(Structure):
     """Mirror of ``gs_slide_desc``."""
     _fields_ = [(k, c_int32) for k in ("N", "C", "ld", "hl", "wl", "hc", "wc", "H", "W", "Ho", "Wo",
@@ -142,6 +161,7 @@ class SgdChunk(Structure):
 _P = c_void_p  # device pointers and the stream travel as plain addresses
 _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
 _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
+_DD, _PW = POINTER(DistillDesc), POINTER(PairwiseDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -200,6 +220,13 @@ PROTOTYPES = {
     "gs_kd_forward": (_i32, [_KD, _P, _P, _P, _P, _f32, _P, _P, _sz, _P]),
     "gs_kd_backward_workspace_bytes": (_sz, [_KD, _i32]),
     "gs_kd_backward": (_i32, [_KD, _P, _P, _P, _P, _f32, _P, _i32, _P, _sz, _P]),
+    "gs_distill_workspace_bytes": (_sz, [_DD]),
+    "gs_distill_forward": (_i32, [_DD, _P, _P, _P, _P, _f32, _P, _P, _sz, _P]),
+    "gs_distill_backward_workspace_bytes": (_sz, [_DD, _i32]),
+    "gs_distill_backward": (_i32, [_DD, _P, _P, _P, _P, _f32, _P, _i32, _P, _sz, _P]),
+    "gs_pairwise_save_bytes": (_sz, [_PW]),
+    "gs_pairwise_forward": (_i32, [_PW, _P, _P, _f32, _P, _P, _sz, _P]),
+    "gs_pairwise_backward": (_i32, [_PW, _P, _P, _sz, _f32, _P, _i32, _P]),
     "gs_slide_fuse": (_i32, [POINTER(SlideDesc), POINTER(_i32), POINTER(_i32), _P, _P, _P, _P, _P]),
     "gs_debug_set_slide_strip": (_i32, [_i32]),
     "gs_seg_augment": (_i32, [POINTER(AugmentDesc), _P, _P, _P, _P, _P]),

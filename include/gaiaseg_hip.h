@@ -451,6 +451,77 @@ int gs_kd_backward(const gs_kd_desc* d, const float* student, const float* teach
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Fixed-teacher distillation (DynamicDistiller) — the logit loss and the pairwise loss        */
+/* ------------------------------------------------------------------------------------------ */
+/* distill_loss of gaiaseg/models/segmentors/dynamic_distiller.py:341-356,397-403: both low-resolution
+ * logit maps are bilinearly resized to the image size (H, W) with the STUDENT's align_corners, then
+ *   out[0] = scale * sum_{n,c,Y,X} -softmax(t'/T)[c] * log softmax(s'/T)[c]
+ * with the host's scale = distill_loss_weight / (N * H * W) (no T^2 factor).  gs_kd_desc with the
+ * teacher at a resolution of its own: (hs, ws) and (ht, wt) are independent (an OS8 teacher over an
+ * OS32 student, or the reverse).  Neither resized map is materialised.  The contract of every entry is
+ * that of its gs_kd_* namesake (lse of both maps saved at [N,H,W]; double fixed-order sums; ds dense
+ * at pixel stride ld_d with zeroed pad columns; tile form with a workspace of
+ * gs_distill_backward_workspace_bytes, gather form with less); the device code is shared, and at
+ * (ht, wt) == (hs, ws) the results equal gs_kd_forward / gs_kd_backward with interpolation = 1 bit
+ * for bit. */
+typedef struct gs_distill_desc {
+  int32_t N, Cls;
+  int32_t hs, ws;              /* student logits                                                 */
+  int32_t ht, wt;              /* teacher logits                                                 */
+  int32_t H, W;                /* evaluation grid: the image size                                */
+  int64_t s_sn, s_sh, s_sw, s_sc;   /* student strides (elements)                               */
+  int64_t t_sn, t_sh, t_sw, t_sc;   /* teacher strides                                          */
+  float T;                     /* temperature (> 0)                                             */
+  int32_t align_corners;
+} gs_distill_desc;
+size_t gs_distill_workspace_bytes(const gs_distill_desc* d);
+int gs_distill_forward(const gs_distill_desc* d, const float* student, const float* teacher,
+                       float* lse_s, float* lse_t, float scale, float* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t gs_distill_backward_workspace_bytes(const gs_distill_desc* d, int32_t ld_d);
+int gs_distill_backward(const gs_distill_desc* d, const float* student, const float* teacher,
+                        const float* lse_s, const float* lse_t, float grad_scale, float* ds,
+                        int32_t ld_d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pairwise_loss of dynamic_distiller.py:309-339 on a window of the last backbone feature maps.  The
+ * window pixels rows y0..y1-1, columns x0..x1-1 are taken row-major, P = (y1 - y0) * (x1 - x0); the
+ * host passes the reference's slice as written, one column (x1 = x0 + 1).  Each pixel's channel vector
+ * is L2-normalised (denominator max(norm, 1e-12), F.normalize), G_s and G_t are the P x P Gram
+ * matrices of the normalised student and teacher vectors, and
+ *   out[0] = scale * -sum_{n,i,j} softmax(G_t/T, over i)[n,i,j] * log_softmax(G_s/T, over j)[n,i,j]
+ * (the reference's dim=1 / dim=2) with the host's scale = pairwise_loss_weight / (N * step_h * step_w).
+ * Student and teacher have their own channel counts, map sizes (the window must lie inside both) and
+ * element strides.  P above GS_PAIRWISE_MAX_P returns GS_E_BADARG before any launch.
+ * forward: 3 launches (raw Gram tiles of both maps; per-image normalise + softmaxes + loss; final
+ * sum), backward: 3 launches (zero fill; gradient coefficients; coefficients x window).  None grows
+ * with N, P or C; no host synchronisation; fp32 sums in a fixed order, the final sum in double, no
+ * float atomics: bit-reproducible.  A channels-last map (c stride 1, other strides and the base
+ * address multiples of 4 floats) is read as float4s with a scalar tail; any other layout by scalars.
+ * `save`: gs_pairwise_save_bytes(d) bytes, 8-byte aligned, written by the forward and read (and used
+ * as scratch) by the backward. */
+#define GS_PAIRWISE_MAX_P 128
+typedef struct gs_pairwise_desc {
+  int32_t N, Cs, Ct;
+  int32_t H, W;                /* student map                                                    */
+  int32_t Ht, Wt;              /* teacher map                                                    */
+  int32_t y0, y1, x0, x1;      /* window, in both maps                                           */
+  int32_t reserved;
+  int64_t s_sn, s_sc, s_sh, s_sw;   /* student strides (elements)                               */
+  int64_t t_sn, t_sc, t_sh, t_sw;   /* teacher strides                                          */
+  float T;                     /* temperature (> 0)                                             */
+  int32_t reserved2;
+} gs_pairwise_desc;
+size_t gs_pairwise_save_bytes(const gs_pairwise_desc* d);
+int gs_pairwise_forward(const gs_pairwise_desc* d, const float* student, const float* teacher,
+                        float scale, float* out, void* save, size_t save_bytes, void* stream);
+/* ds[n,y,x,c]: the gradient of out[0] * grad_scale / scale with respect to the student map, dense at
+ * pixel stride ld_d (>= Cs, a multiple of 4; columns Cs..ld_d-1 zeroed), zero outside the window; the
+ * chain log-softmax -> Gram -> normalise includes the eps clamp (a pixel whose norm is below 1e-12
+ * gets g / 1e-12 as autograd does: finite).  The teacher receives no gradient. */
+int gs_pairwise_backward(const gs_pairwise_desc* d, const float* student, void* save,
+                         size_t save_bytes, float grad_scale, float* ds, int32_t ld_d, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Inference epilogue — K17                                                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* argmax over classes of bilinearly resized logits (softmax is monotone):
