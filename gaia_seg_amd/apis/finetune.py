@@ -134,9 +134,10 @@ def finetune_model_space(model, metas, cfg, train_data, val_loader, num_batches,
     statistics of the subnet's active slices are re-estimated on the train data.
 
     Returns the rows (identical on every rank)."""
-    from ..core.evaluation import evaluate_model
+    from ..core.evaluation import check_tta_input_shape, evaluate_model
     metas = list(metas or ())
     check_finetune_cfg(cfg, metas)
+    check_tta_input_shape(val_loader, cfg.get("apply_input_shape", False))
     log = (logger.info if logger is not None else print) if gdist.rank() == 0 else (lambda msg: None)
 
     apply_input_shape = bool(cfg.get("apply_input_shape", False))

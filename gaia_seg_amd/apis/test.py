@@ -99,11 +99,12 @@ def test_model_space(model, loader, metas, num_batches, num_classes, ignore_inde
     tools/test_supernet.py passes) reads the top-level ``apply_input_shape`` of the config the model
     was built from (``model.top_cfg``, models/builder.py)."""
     from ..core.dynamic import fold_dict
-    from ..core.evaluation import evaluate_model
+    from ..core.evaluation import check_tta_input_shape, evaluate_model
     from ..core.input_shape import INPUT_SHAPE_KEY
     from ..core.model_space import _listify, parse_input_shape
     if apply_input_shape is None:
         apply_input_shape = bool((getattr(model, "top_cfg", None) or {}).get("apply_input_shape", False))
+    check_tta_input_shape(loader, apply_input_shape)
     if apply_input_shape:      # a bad value is refused before the first subnet is evaluated
         for meta in metas:
             if meta.get(INPUT_SHAPE_KEY) is not None:

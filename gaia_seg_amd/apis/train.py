@@ -73,8 +73,9 @@ def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_cl
             return SyntheticLoader(samples_per_gpu, tuple(dataset_cfg["size"]),
                                    dataset_cfg.get("num_classes", num_classes), seed=seed,
                                    rank=gdist.rank(), device=device)
-        from ..datasets import (DATASETS, FileBatchLoader, FileEvalLoader, build_dataset,
-                                eval_pipeline_kwargs, train_pipeline_kwargs)
+        from ..datasets import (DATASETS, FileBatchLoader, FileEvalLoader, FileTtaEvalLoader,
+                                build_dataset, eval_pipeline_kwargs, train_pipeline_kwargs,
+                                tta_num_views, tta_pipeline_kwargs)
         if t not in DATASETS:
             raise NotImplementedError("dataset type %r is not registered (have %s and "
                                       "SyntheticSegDataset)" % (t, sorted(DATASETS.module_dict)))
@@ -86,11 +87,31 @@ def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_cl
             return FileBatchLoader(ds, samples_per_gpu, train_pipeline_kwargs(ds.pipeline),
                                    workers_per_gpu=workers_per_gpu, seed=seed, rank=gdist.rank(),
                                    world=gdist.world_size(), device=device, **extra)
+        common = dict(workers_per_gpu=workers_per_gpu, rank=gdist.rank(), world=gdist.world_size(),
+                      device=device, **extra)
+        if wants_tta(ds.pipeline):
+            # multi-scale / flip test-time augmentation: every batch carries all views.  (A ladder
+            # of one view over a fixed scale is the single-view loader's job.)
+            tk = tta_pipeline_kwargs(ds.pipeline)
+            if tta_num_views(tk) > 1 or tk["scales"] is None:
+                return FileTtaEvalLoader(ds, samples_per_gpu, tk, **common)
+            return FileEvalLoader(ds, samples_per_gpu, tk["scales"][0], tk["mean"], tk["std"],
+                                  tk["to_rgb"], **common)
         tk = eval_pipeline_kwargs(ds.pipeline)
         return FileEvalLoader(ds, samples_per_gpu, tk["img_scale"], tk["mean"], tk["std"], tk["to_rgb"],
-                              workers_per_gpu=workers_per_gpu, rank=gdist.rank(),
-                              world=gdist.world_size(), device=device, **extra)
+                              **common)
     return dataset_cfg  # already an iterable of batches
+
+
+def wants_tta(pipeline):
+    """Does a val / test transform list ask for what the single-view translation
+    (eval_pipeline_kwargs) refuses: flipped views, ``img_ratios`` or a list of scales?"""
+    for t in pipeline:
+        if t.get("type") == "MultiScaleFlipAug":
+            scale = t.get("img_scale")
+            return bool(t.get("flip", False) or t.get("img_ratios") is not None or scale is None
+                        or isinstance(scale, list))
+    return False
 
 
 def optimizer_hook(optimizer_config):

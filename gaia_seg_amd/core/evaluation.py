@@ -46,11 +46,31 @@ def metrics_from_confusion(conf):
                 IoU=iou.tolist(), Acc=acc.tolist())
 
 
+TTA_INPUT_SHAPE = ("multi-scale / flip test-time augmentation with apply_input_shape is not "
+                   "supported: a row's own input scale and a ladder of views do not compose")
+
+
+def is_tta_loader(loader):
+    """Does ``loader`` yield batches of views (``img`` a list: FileTtaEvalLoader, or a prepared list
+    of such batches)?"""
+    if getattr(loader, "tta", False):
+        return True
+    return bool(isinstance(loader, (list, tuple)) and loader and isinstance(loader[0], dict)
+                and isinstance(loader[0].get("img"), list))
+
+
+def check_tta_input_shape(loader, apply_input_shape):
+    """Set-up time refusal of TTA together with elastic input resolution."""
+    if apply_input_shape and is_tta_loader(loader):
+        raise ValueError(TTA_INPUT_SHAPE)
+
+
 def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255, input_shape=None):
     """Test-mode pass over ``num_batches`` batches of dict(img, img_metas, gt_semantic_seg).
     ``input_shape``: a ``data.input_shape`` value to evaluate at (core/input_shape.py): the image is
     rescaled, ``ori_shape`` and the labels are not -- the test epilogue brings the predictions back
-    to the label size."""
+    to the label size.  A batch whose ``img`` is a list holds the views of a multi-scale / flip test
+    pipeline and is averaged by ``aug_test_device``."""
     was_training = model.training
     model.eval()
     conf = None
@@ -59,9 +79,14 @@ def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255, in
         for _ in range(num_batches):
             batch = next(it)
             if input_shape is not None:
+                if isinstance(batch["img"], list):
+                    raise ValueError(TTA_INPUT_SHAPE)
                 batch = rescale_batch(batch, input_shape, with_labels=False)[0]
             img, metas, gt = batch["img"], batch["img_metas"], batch["gt_semantic_seg"]
-            preds = model.simple_test_device(img, metas)
+            if isinstance(img, list):      # one tensor per view (FileTtaEvalLoader)
+                preds = model.aug_test_device(img, metas)
+            else:
+                preds = model.simple_test_device(img, metas)
             conf = confusion_matrix(preds, gt, num_classes, ignore_index, conf)
     if gdist.is_dist():
         import torch.distributed as dist
@@ -76,6 +101,7 @@ class CrossArchEvalHook(Hook):
 
     def __init__(self, dataloader, model_sampler, interval=1, num_batches=4, num_classes=19,
                  ignore_index=255, logger=None, apply_input_shape=False):
+        check_tta_input_shape(dataloader, apply_input_shape)
         self.apply_input_shape = apply_input_shape
         self.dataloader, self.sampler = dataloader, model_sampler
         self.interval, self.num_batches = interval, num_batches

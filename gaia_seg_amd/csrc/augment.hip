@@ -27,6 +27,8 @@
 // numpy does), so that the uint8 roundings fall on the same side as in the oracle
 #pragma clang fp contract(off)
 
+#include "augment_fetch.h"   // the bilinear fetch and the normalising store, shared with tta.hip
+
 namespace gs {
 
 __device__ __forceinline__ float u8_convert(float v) {   // mmseg PhotoMetricDistortion.convert
@@ -97,25 +99,8 @@ __global__ __launch_bounds__(256) void seg_augment_kernel(const gs_augment_desc 
       out_label[i] = label[(long)ly * d.src_w + lx];
     }
     // ---- image: bilinear, rounded to uint8 ----
-    float fy = ((float)ry + 0.5f) * sy - 0.5f, fx = ((float)rx + 0.5f) * sx - 0.5f;
-    int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-    float wy = fy - (float)y0, wx = fx - (float)x0;
-    if (y0 < 0) { y0 = 0; wy = 0.f; }
-    if (x0 < 0) { x0 = 0; wx = 0.f; }
-    int y1 = y0 + 1, x1 = x0 + 1;
-    if (y1 > d.src_h - 1) { y1 = d.src_h - 1; if (y0 > d.src_h - 1) { y0 = d.src_h - 1; } }
-    if (x1 > d.src_w - 1) { x1 = d.src_w - 1; if (x0 > d.src_w - 1) { x0 = d.src_w - 1; } }
-    const uint8_t* p00 = img + ((long)y0 * d.src_w + x0) * 3;
-    const uint8_t* p01 = img + ((long)y0 * d.src_w + x1) * 3;
-    const uint8_t* p10 = img + ((long)y1 * d.src_w + x0) * 3;
-    const uint8_t* p11 = img + ((long)y1 * d.src_w + x1) * 3;
     float c[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float top = (float)p00[k] + ((float)p01[k] - (float)p00[k]) * wx;
-      const float bot = (float)p10[k] + ((float)p11[k] - (float)p10[k]) * wx;
-      c[k] = rintf(top + (bot - top) * wy);
-    }
+    fetch_bilinear_u8(img, d.src_h, d.src_w, sy, sx, ry, rx, c);
     // channel order of the source: BGR (cv2.imread) unless src_is_rgb
     float b = d.src_is_rgb ? c[2] : c[0], g = c[1], r = d.src_is_rgb ? c[0] : c[2];
     // ---- PhotoMetricDistortion ----
@@ -142,10 +127,7 @@ __global__ __launch_bounds__(256) void seg_augment_kernel(const gs_augment_desc 
       }
     }
     // ---- Normalize (to_rgb -> planes R, G, B) + DefaultFormatBundle (CHW float) ----
-    const float ch0 = d.to_rgb ? r : b, ch2 = d.to_rgb ? b : r;
-    out_img[i] = (ch0 - d.mean[0]) / d.std[0];
-    out_img[plane + i] = (g - d.mean[1]) / d.std[1];
-    out_img[2 * plane + i] = (ch2 - d.mean[2]) / d.std[2];
+    store_normalized(out_img, plane, i, b, g, r, d.to_rgb, d.mean, d.std);
   }
 }
 

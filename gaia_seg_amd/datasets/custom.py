@@ -231,3 +231,92 @@ def eval_pipeline_kwargs(pipeline):
         elif name == "Normalize":
             out.update(mean=tuple(t["mean"]), std=tuple(t["std"]), to_rgb=bool(t.get("to_rgb", True)))
     return out
+
+
+# ---- multi-scale / flip test-time augmentation --------------------------------------------------
+_TTA_INNER = ("Resize", "RandomFlip", "Normalize", "ImageToTensor", "Collect")
+TTA_MAX_VIEWS = 16     # GS_TTA_MAX_VIEWS: what one gs_tta_views launch writes
+
+
+def tta_pipeline_kwargs(pipeline):
+    """A test transform list with mmseg's ``MultiScaleFlipAug`` as the recipe of an ordered list of
+    views (``tta_views``).  This RECONSTRUCTS mmseg's transform from its documented behaviour: mmseg
+    is not available to this build, so nothing here is pinned against its code.  What is restated:
+
+      * ``img_scale`` a (w, h) tuple with ``img_ratios`` a list of floats: the scales are
+        ``(int(w * r), int(h * r))``; ``img_scale=None`` with ratios: the same from each image's own
+        (w, h); ``img_scale`` a list (or a tuple without ratios): taken as given;
+      * the views are ``for scale: for flip in ([False, True] if flip else [False]): for direction
+        in flip_direction`` -- the unflipped view is repeated once per direction, which weights it
+        in the mean of the probabilities; that weighting is kept;
+      * inside, ``Resize(keep_ratio=True)`` rescales to the view's scale (``rescale_size``),
+        ``RandomFlip`` applies the view's flip, then ``Normalize``; ``ImageToTensor`` and ``Collect``
+        only repack.  Any other inner transform, ``keep_ratio=False`` and more than ``TTA_MAX_VIEWS``
+        views raise NotImplementedError.
+
+    Returns dict(mean, std, to_rgb, scales, ratios, flips): ``scales`` the list of (w, h) scales, or
+    None when they follow each image's size by ``ratios``; ``flips`` the (flip, direction) pairs of
+    one scale, in order.  ``eval_pipeline_kwargs`` stays the single-view translation."""
+    out = dict(mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True)
+    aug = None
+    for t in pipeline:
+        t = dict(t)
+        name = t.pop("type")
+        if name == "MultiScaleFlipAug":
+            if aug is not None:
+                raise NotImplementedError("more than one MultiScaleFlipAug in a test pipeline")
+            aug = t
+        elif name == "Normalize":
+            out.update(mean=tuple(t["mean"]), std=tuple(t["std"]), to_rgb=bool(t.get("to_rgb", True)))
+        elif name not in _IGNORED:
+            raise NotImplementedError("transform %r has no GPU counterpart in a test pipeline" % name)
+    if aug is None:
+        raise ValueError("a test pipeline needs MultiScaleFlipAug")
+    for s in aug.get("transforms", []):
+        s = dict(s)
+        name = s.pop("type")
+        if name not in _TTA_INNER:
+            raise NotImplementedError("transform %r inside MultiScaleFlipAug has no GPU counterpart "
+                                      "in this build" % name)
+        if name == "Resize" and s.get("keep_ratio", True) is not True:
+            raise NotImplementedError("Resize(keep_ratio=False) inside MultiScaleFlipAug")
+        if name == "Normalize":
+            out.update(mean=tuple(s["mean"]), std=tuple(s["std"]), to_rgb=bool(s.get("to_rgb", True)))
+    ratios = aug.get("img_ratios")
+    if ratios is not None:
+        ratios = [float(r) for r in (ratios if isinstance(ratios, (list, tuple)) else [ratios])]
+    scale = aug.get("img_scale")
+    if scale is None:
+        if not ratios:
+            raise ValueError("MultiScaleFlipAug(img_scale=None) needs img_ratios")
+        scales = None
+    elif ratios and len(scale) == 2 and not isinstance(scale[0], (list, tuple)):
+        scales = [(int(scale[0] * r), int(scale[1] * r)) for r in ratios]
+        ratios = None
+    else:
+        scales = [tuple(s) for s in scale] if isinstance(scale[0], (list, tuple)) else [tuple(scale)]
+        ratios = None
+    directions = aug.get("flip_direction", "horizontal")
+    directions = list(directions) if isinstance(directions, (list, tuple)) else [directions]
+    for d in directions:
+        if d not in ("horizontal", "vertical"):
+            raise NotImplementedError("flip_direction %r" % (d,))
+    flips = [(f, d) for f in ([False, True] if aug.get("flip", False) else [False])
+             for d in directions]
+    n = len(scales if scales is not None else ratios) * len(flips)
+    if n > TTA_MAX_VIEWS:
+        raise NotImplementedError("%d test-time views (at most %d)" % (n, TTA_MAX_VIEWS))
+    out.update(scales=scales, ratios=ratios, flips=flips)
+    return out
+
+
+def tta_num_views(kw):
+    return len(kw["scales"] if kw["scales"] is not None else kw["ratios"]) * len(kw["flips"])
+
+
+def tta_views(kw, h, w):
+    """The ordered views of an h x w image: dict(scale=(w, h) scale tuple, flip, flip_direction)."""
+    scales = kw["scales"]
+    if scales is None:
+        scales = [(int(w * r), int(h * r)) for r in kw["ratios"]]
+    return [dict(scale=s, flip=f, flip_direction=d) for s in scales for f, d in kw["flips"]]

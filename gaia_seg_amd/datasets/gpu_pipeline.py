@@ -204,3 +204,57 @@ class GpuTrainPipeline:
         if gts:
             out["gt_semantic_seg"] = torch.stack(gts).unsqueeze(1)
         return out
+
+    def tta_batch(self, samples, views):
+        """The multi-scale / flip test pipeline (``datasets.custom.tta_views``) for samples of ONE
+        size: dict(img=[fp32 [N, 3, h', w'] per view], img_metas=[[meta per image] per view],
+        gt_semantic_seg int64 [N, 1, H, W] at the ORIGINAL size when the samples carry label maps) --
+        the lists ``forward_test`` / ``aug_test`` take.  One ``gs_tta_views`` launch per image writes
+        all of its views.  Views that are the same pixels (mmseg lists the unflipped view once per
+        flip direction) share one tensor.  The metas have the keys ``test_batch`` writes."""
+        if not views:
+            raise ValueError("tta_batch needs at least one view")
+        h, w = int(samples[0][0].shape[0]), int(samples[0][0].shape[1])
+        for s in samples:
+            if tuple(s[0].shape[:2]) != (h, w):
+                raise ValueError("tta_batch needs samples of one size (got %s and %s)"
+                                 % ((h, w), tuple(s[0].shape[:2])))
+        n = len(samples)
+        unique, per_view = {}, []
+        for v in views:
+            rh, rw = rescale_size(h, w, v["scale"])
+            code = _lib.FLIP_CODES[v["flip_direction"] if v["flip"] else None]
+            key = (rh, rw, code)
+            if key not in unique:
+                unique[key] = torch.empty((n, 3, rh, rw), dtype=torch.float32, device=self.device)
+            per_view.append(key)
+        if len(unique) > _lib.TTA_MAX_VIEWS:
+            raise NotImplementedError("%d distinct test-time views (at most %d)"
+                                      % (len(unique), _lib.TTA_MAX_VIEWS))
+        d = _lib.TtaDesc()
+        d.src_h, d.src_w, d.src_is_rgb = h, w, 1 if self.src_is_rgb else 0
+        d.n_views, d.to_rgb = len(unique), 1 if self.to_rgb else 0
+        for k in range(3):
+            d.mean[k], d.std[k] = self.mean[k], self.std[k]
+        for k, (rh, rw, code) in enumerate(unique):
+            d.views[k].res_h, d.views[k].res_w, d.views[k].flip = rh, rw, code
+        gts = []
+        for i, s in enumerate(samples):
+            img = s[0].to(self.device, non_blocking=True).contiguous()
+            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+                raise TypeError("expected uint8 img [H, W, 3]")
+            for k, t in enumerate(unique.values()):
+                d.views[k].out = t[i].data_ptr()
+            _lib.check(_lib.load().gs_tta_views(d, img.data_ptr(), current_stream_ptr()),
+                       "gs_tta_views")
+            if s[1] is not None:
+                gts.append(s[1].to(self.device, non_blocking=True).to(torch.int64))
+        metas = [[dict(ori_shape=(h, w, 3), img_shape=(key[0], key[1], 3),
+                       pad_shape=(key[0], key[1], 3), flip=bool(v["flip"]),
+                       flip_direction=v["flip_direction"], scale_factor=key[0] / h,
+                       filename=s[2] if len(s) > 2 else "sample_%d" % i)
+                  for i, s in enumerate(samples)] for v, key in zip(views, per_view)]
+        out = dict(img=[unique[key] for key in per_view], img_metas=metas)
+        if gts:
+            out["gt_semantic_seg"] = torch.stack(gts).unsqueeze(1)
+        return out

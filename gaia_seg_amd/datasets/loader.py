@@ -23,6 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
+from .custom import tta_views
 from .gpu_pipeline import GpuTrainPipeline
 
 
@@ -172,7 +173,7 @@ class FileEvalLoader:
     def __iter__(self):
         return self
 
-    def __next__(self):
+    def next_samples(self):
         samples = [self._pre.get(self._indices)]
         while len(samples) < self.bs:                      # a batch holds samples of one size
             nxt = self._pre.get(self._indices)
@@ -180,10 +181,31 @@ class FileEvalLoader:
                 self._pre.pending.appendleft(_Done((None, nxt)))     # (already counted / cached)
                 break
             samples.append(nxt)
-        return self.pipeline.test_batch(samples, self.img_scale)
+        return samples
+
+    def __next__(self):
+        return self.pipeline.test_batch(self.next_samples(), self.img_scale)
 
     def close(self):
         self._pre.close()
+
+
+class FileTtaEvalLoader(FileEvalLoader):
+    """FileEvalLoader whose batches carry every view of a multi-scale / flip test pipeline:
+    dict(img=[tensor per view], img_metas=[[meta per image] per view], gt_semantic_seg) -- sharding,
+    prefetching and the one-size-per-batch rule are the parent's.  ``tta_kw``:
+    datasets.custom.tta_pipeline_kwargs of the dataset's pipeline."""
+    tta = True        # core/evaluation.py: such batches go to aug_test_device
+
+    def __init__(self, dataset, samples_per_gpu, tta_kw, **kw):
+        super().__init__(dataset, samples_per_gpu, None, tta_kw["mean"], tta_kw["std"],
+                         tta_kw["to_rgb"], **kw)
+        self.tta_kw = tta_kw
+
+    def __next__(self):
+        samples = self.next_samples()
+        h, w = int(samples[0][0].shape[0]), int(samples[0][0].shape[1])
+        return self.pipeline.tta_batch(samples, tta_views(self.tta_kw, h, w))
 
 
 class _Done:

@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class HipLibraryError(RuntimeError):
@@ -145,6 +145,23 @@ class AugmentDesc(Structure):
                  ("std", c_float * 3), ("pad_val", c_float), ("seg_pad_val", c_int32)])
 
 
+TTA_MAX_VIEWS = 16   # GS_TTA_MAX_VIEWS
+FLIP_CODES = {None: 0, "horizontal": 1, "vertical": 2}   # gs_tta_view.flip, gs_slide_desc.flip
+
+
+class TtaView(Structure):
+    """Mirror of ``gs_tta_view``."""
+    _fields_ = [("res_h", c_int32), ("res_w", c_int32), ("flip", c_int32), ("reserved", c_int32),
+                ("out", c_void_p)]
+
+
+class TtaDesc(Structure):
+    """Mirror of ``gs_tta_desc`` (passed by value)."""
+    _fields_ = [("src_h", c_int32), ("src_w", c_int32), ("src_is_rgb", c_int32), ("n_views", c_int32),
+                ("to_rgb", c_int32), ("mean", c_float * 3), ("std", c_float * 3), ("reserved", c_int32),
+                ("views", TtaView * TTA_MAX_VIEWS)]
+
+
 SGD_MAX_GROUPS = 16   # GS_SGD_MAX_GROUPS
 
 
@@ -230,6 +247,8 @@ PROTOTYPES = {
     "gs_slide_fuse": (_i32, [POINTER(SlideDesc), POINTER(_i32), POINTER(_i32), _P, _P, _P, _P, _P]),
     "gs_debug_set_slide_strip": (_i32, [_i32]),
     "gs_seg_augment": (_i32, [POINTER(AugmentDesc), _P, _P, _P, _P, _P]),
+    "gs_tta_views": (_i32, [TtaDesc, _P, _P]),
+    "gs_seg_overlay": (_i32, [_P, _P, _P, _i32, _i32, _i32, _f64, _P, _P]),
     "gs_batch_rescale": (_i32, [_P, _P, _i32, _i32, _i32, _P, _P, _i32, _i32, _P]),
     "gs_ohem_workspace_bytes": (_sz, []),
     "gs_ohem_weights": (_i32, [_P, _i64, _i64, _f32, _i32, _P, _P, _sz, _P]),

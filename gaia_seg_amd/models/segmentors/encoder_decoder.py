@@ -223,10 +223,11 @@ class EncoderDecoder(nn.Module):
     def simple_test(self, img, img_meta, rescale=True):
         return list(self.simple_test_device(img, img_meta, rescale).cpu().numpy())
 
-    def aug_test(self, imgs, img_metas, rescale=True):
-        """Mean of the per-view probabilities, then argmax (dynamic_distiller.py:523-540): the running
-        sum is carried through the fused kernel; the last view writes only the label map (the
-        division by the number of views does not change the argmax)."""
+    def aug_test_device(self, imgs, img_metas, rescale=True):
+        """Mean of the per-view probabilities, then argmax (dynamic_distiller.py:523-540), with the
+        label map left on the device: int64 [N, H, W].  The running sum is carried through the fused
+        kernel; the last view writes only the label map (the division by the number of views does
+        not change the argmax)."""
         if not rescale:
             raise ValueError("aug_test needs rescale=True (views of different sizes)")
         acc = None
@@ -235,7 +236,10 @@ class EncoderDecoder(nn.Module):
                 last = k == len(imgs) - 1
                 labels, acc = self._view(img, meta, rescale, probs_in=acc, want_probs=not last,
                                          want_labels=last)
-        return list(labels.cpu().numpy())
+        return labels
+
+    def aug_test(self, imgs, img_metas, rescale=True):
+        return list(self.aug_test_device(imgs, img_metas, rescale).cpu().numpy())
 
     def forward_test(self, imgs, img_metas, **kwargs):
         if not isinstance(imgs, list) or not isinstance(img_metas, list):
@@ -252,6 +256,30 @@ class EncoderDecoder(nn.Module):
         if return_loss:
             return self.forward_train(img, img_metas, **kwargs)
         return self.forward_test(img, img_metas, **kwargs)
+
+    # ---- visualisation ----
+    def show_result(self, img, result, palette=None, opacity=0.5, out_file=None):
+        """mmseg's ``show_result`` blend on the device (``gs_seg_overlay``): ``img`` a file path or a
+        uint8 BGR array [H, W, 3], ``result`` the list ``inference_segmentor`` returns (its first
+        label map is drawn) or one label map.  ``palette``: [C, 3] RGB; default ``self.PALETTE``, or
+        a palette drawn like mmseg's (``np.random.seed(42)``, randint(0, 255)) over the classes.
+        Returns the blended BGR array; ``out_file`` also gets it as an image."""
+        import numpy as np
+        from ...core.visual import overlay, read_bgr, write_bgr
+        img = read_bgr(img) if isinstance(img, str) else np.ascontiguousarray(img)
+        seg = result[0] if isinstance(result, (list, tuple)) else result
+        if palette is None:
+            palette = getattr(self, "PALETTE", None)
+        if palette is None:
+            state = np.random.get_state()
+            np.random.seed(42)
+            palette = np.random.randint(0, 255, size=(self.num_classes, 3))
+            np.random.set_state(state)
+        device = next(self.parameters()).device
+        out = overlay(seg, img, palette, opacity, device)
+        if out_file is not None:
+            write_bgr(out_file, out)
+        return out
 
     # ---- runner interface (SURVEY.md Appendix A12) ----
     def train_step(self, data_batch, optimizer=None, **kwargs):

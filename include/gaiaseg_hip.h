@@ -669,6 +669,45 @@ typedef struct gs_augment_desc {
 int gs_seg_augment(const gs_augment_desc* d, const uint8_t* img, const uint8_t* label,
                    float* out_img, int64_t* out_label, void* stream);
 
+/* Test-time augmentation views (mmseg's MultiScaleFlipAug test pipeline): ONE
+ * launch writes every view of one decoded uint8 image [src_h][src_w][3] (BGR, or RGB with
+ * src_is_rgb as in gs_augment_desc).  View k is the image resized to res_h x res_w (gs_seg_augment's
+ * bilinear: half-pixel centres, edge-clamped, rounded to uint8), then flipped (0 none, 1 horizontal,
+ * 2 vertical), then normalised ((x - mean) / std, RGB planes when to_rgb): fp32 [3][res_h][res_w] at
+ * `out`, usually this image's slot of the view's [N][3][res_h][res_w] batch tensor.  The arithmetic is
+ * gs_seg_augment's own (separately rounded fp32 operations), so an unflipped view equals what that
+ * kernel writes for the same size bit for bit, and a flipped view is the exact mirror image of its
+ * unflipped twin.  There is no label input or output; nothing outside the 3 * res_h * res_w floats
+ * of each slot is written, and a slot needs 4-byte alignment only.  The descriptor travels by value.
+ * GS_E_NULL (img or a view's out) / GS_E_BADARG (n_views outside [1, GS_TTA_MAX_VIEWS], a
+ * non-positive size, flip outside {0, 1, 2}, std <= 0) before any launch. */
+#define GS_TTA_MAX_VIEWS 16
+typedef struct gs_tta_view {
+  int32_t res_h, res_w;
+  int32_t flip;        /* 0 none, 1 horizontal, 2 vertical */
+  int32_t reserved;    /* 0 */
+  float* out;
+} gs_tta_view;
+typedef struct gs_tta_desc {
+  int32_t src_h, src_w, src_is_rgb;
+  int32_t n_views;
+  int32_t to_rgb;
+  float mean[3], std[3];
+  int32_t reserved;    /* 0 */
+  gs_tta_view views[GS_TTA_MAX_VIEWS];   /* entries >= n_views ignored */
+} gs_tta_desc;
+int gs_tta_views(gs_tta_desc d, const uint8_t* img, void* stream);
+
+/* mmseg's show_result blend on the device: labels int64 [H][W], img uint8 [H][W][3] in BGR, palette
+ * uint8 [num_classes][3] in RGB -> out uint8 [H][W][3] in BGR,
+ *   out = uint8(img * (1 - opacity) + colour_bgr * opacity)
+ * evaluated in double and truncated (numpy's result for a Python float opacity, exactly).  A label
+ * outside [0, num_classes) takes colour (0, 0, 0), as mmseg's zero-initialised color_seg does.  out
+ * must not overlap img.  GS_E_NULL / GS_E_BADARG (a size or num_classes <= 0, opacity outside [0, 1]). */
+int gs_seg_overlay(const int64_t* labels, const uint8_t* img, const uint8_t* palette,
+                   int32_t num_classes, int32_t H, int32_t W, double opacity, uint8_t* out,
+                   void* stream);
+
 /* Elastic input resolution (data.input_shape): one launch resamples a
  * normalised batch on the device.
  *   img    fp32 NCHW [N][3][h][w] -> out_img [N][3][H][W]: bilinear, align_corners=False, ATen's fp32
