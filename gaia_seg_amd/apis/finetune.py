@@ -49,6 +49,10 @@ def check_finetune_cfg(cfg, metas):
         raise ValueError("caliberate_bn.use_minibatch_stats with fast-finetune is not supported: it "
                          "drops the running statistics for good, and the subnets after the first "
                          "could not be restored")
+    if (cfg.get("caliberate_bn") or {}).get("recalibrate") is not None:
+        raise ValueError("caliberate_bn.recalibrate with fast-finetune is not supported: a finetuned "
+                         "subnet's BatchNorm statistics are already its own; re-calibration belongs to "
+                         "tools/test_supernet.py")
     if not metas:
         raise ValueError("fast-finetune: no subnet to finetune (empty metas)")
     optimizer_hook(cfg.get("optimizer_config"))   # grad_clip / dynamic loss scale: refused here

@@ -85,7 +85,8 @@ def multi_gpu_test(model, data_loader, size=None, **kw):
 
 
 def test_model_space(model, loader, metas, num_batches, num_classes, ignore_index=255,
-                     calib_cfg=None, metric_tag="direct", logger=None, apply_input_shape=None):
+                     calib_cfg=None, metric_tag="direct", logger=None, apply_input_shape=None,
+                     calibrator=None):
     """Evaluate every subnet of a model space (the loop of the reference's tools/test_supernet.py).
 
     For each flat meta: ``manipulate_arch`` with its arch, ``apply_bn_calibration(.., 'test')`` with
@@ -97,7 +98,23 @@ def test_model_space(model, loader, metas, num_batches, num_classes, ignore_inde
     ``apply_input_shape``: a row that carries ``data.input_shape`` is evaluated at that size
     (DESIGN.md section 20); without it the column is carried, not applied.  None (the default, what
     tools/test_supernet.py passes) reads the top-level ``apply_input_shape`` of the config the model
-    was built from (``model.top_cfg``, models/builder.py)."""
+    was built from (``model.top_cfg``, models/builder.py).
+    ``calibrator`` (core.bn_calibration.BNCalibrator over this model): every row is evaluated inside
+    ``calibrator.calibrated(...)``, i.e. with BatchNorm running statistics re-estimated for its subnet
+    (at the row's ``data.input_shape`` when that is applied), and the supernet is put back bit for bit
+    before the next row.  Calibration is independent of the validation views, so test-time-augmentation
+    loaders need nothing special.  Without a calibrator, a ``calib_cfg`` that carries ``recalibrate``
+    (what tools/test_supernet.py passes: ``cfg.caliberate_bn``) builds one from the config the model was
+    built from (``model.top_cfg``: its ``data.train`` supplies the calibration batches)."""
+    import contextlib
+    from ..core.bn_calibration import BNCalibrator, build_calibration_batches, parse_recalibrate_cfg
+    if calibrator is None and parse_recalibrate_cfg(calib_cfg) is not None:
+        top = getattr(model, "top_cfg", None)
+        if top is None or top.get("data") is None:
+            raise ValueError("caliberate_bn.recalibrate needs the calibration batches: pass a "
+                             "calibrator, or build the model from a config that has data.train")
+        calibrator = BNCalibrator(model, build_calibration_batches(
+            top, device=next(model.parameters()).device, num_classes=num_classes, calib_cfg=calib_cfg))
     from ..core.dynamic import fold_dict
     from ..core.evaluation import check_tta_input_shape, evaluate_model
     from ..core.input_shape import INPUT_SHAPE_KEY
@@ -113,8 +130,11 @@ def test_model_space(model, loader, metas, num_batches, num_classes, ignore_inde
     rows = []
     for i, meta in enumerate(metas):
         model.manipulate_arch(_listify(fold_dict(meta).get("arch", {})))
-        res = evaluate_model(model, loader, num_batches, num_classes, ignore_index,
-                             input_shape=meta.get(INPUT_SHAPE_KEY) if apply_input_shape else None)
+        input_shape = meta.get(INPUT_SHAPE_KEY) if apply_input_shape else None
+        with (calibrator.calibrated(input_shape) if calibrator is not None
+              else contextlib.nullcontext()):
+            res = evaluate_model(model, loader, num_batches, num_classes, ignore_index,
+                                 input_shape=input_shape)
         row = dict(meta)
         for k in ("mIoU", "mAcc", "aAcc"):
             row["metric.%s.%s" % (metric_tag, k)] = res[k]

@@ -53,13 +53,17 @@ def sandwich_train_sampler(cfg):
 
 
 def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_classes=19,
-                     workers_per_gpu=2, train=True, device_cache_gb=None):
+                     workers_per_gpu=2, train=True, device_cache_gb=None, rank=None, world=None):
     """mmseg ``build_dataset`` + ``build_dataloader(..., dist, seed, drop_last=True)``
     (gaiaseg/apis/train.py:74-84, tools/train_supernet.py:197) for this path: a config dict naming a
     registered file-backed dataset (``CityscapesDataset19`` of the in-tree configs, ``CityscapesDataset``,
     ``CustomDataset``) becomes a loader whose transforms run on the GPU; ``SyntheticSegDataset`` gives
     the seeded synthetic batches; anything else that is already an iterable of batches passes through
-    (a list of batches -- dicts with an ``img`` and no ``type`` -- included)."""
+    (a list of batches -- dicts with an ``img`` and no ``type`` -- included).  ``rank`` / ``world``:
+    the shard this loader reads instead of the process's own (core/bn_calibration.py: every rank
+    reads rank 0 of 1)."""
+    rank = gdist.rank() if rank is None else rank
+    world = gdist.world_size() if world is None else world
     if isinstance(dataset_cfg, (list, tuple)) and dataset_cfg and all(
             isinstance(b, dict) and "img" in b and "type" not in b for b in dataset_cfg):
         return dataset_cfg
@@ -72,7 +76,7 @@ def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_cl
         if t == "SyntheticSegDataset":
             return SyntheticLoader(samples_per_gpu, tuple(dataset_cfg["size"]),
                                    dataset_cfg.get("num_classes", num_classes), seed=seed,
-                                   rank=gdist.rank(), device=device)
+                                   rank=rank, device=device)
         from ..datasets import (DATASETS, FileBatchLoader, FileEvalLoader, FileTtaEvalLoader,
                                 build_dataset, eval_pipeline_kwargs, train_pipeline_kwargs,
                                 tta_num_views, tta_pipeline_kwargs)
@@ -85,10 +89,9 @@ def build_dataloader(dataset_cfg, samples_per_gpu, seed=0, device="cuda", num_cl
         extra = {} if device_cache_gb is None else dict(device_cache_bytes=int(device_cache_gb * (1 << 30)))
         if train:
             return FileBatchLoader(ds, samples_per_gpu, train_pipeline_kwargs(ds.pipeline),
-                                   workers_per_gpu=workers_per_gpu, seed=seed, rank=gdist.rank(),
-                                   world=gdist.world_size(), device=device, **extra)
-        common = dict(workers_per_gpu=workers_per_gpu, rank=gdist.rank(), world=gdist.world_size(),
-                      device=device, **extra)
+                                   workers_per_gpu=workers_per_gpu, seed=seed, rank=rank,
+                                   world=world, device=device, **extra)
+        common = dict(workers_per_gpu=workers_per_gpu, rank=rank, world=world, device=device, **extra)
         if wants_tta(ds.pipeline):
             # multi-scale / flip test-time augmentation: every batch carries all views.  (A ladder
             # of one view over a fixed scale is the single-view loader's job.)
@@ -216,11 +219,16 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
                                           device=device, train=cfg.data.get("val") is None,
                                           workers_per_gpu=cfg.data.get("workers_per_gpu", 2),
                                           device_cache_gb=cfg.data.get("device_cache_gb"))
+        # ``caliberate_bn.recalibrate``: the anchors are scored under re-calibrated BatchNorm statistics
+        from ..core.bn_calibration import BNCalibrator, build_calibration_batches
+        calib = build_calibration_batches(cfg, device=device, num_classes=model.num_classes)
         runner.register_hook(CrossArchEvalHook(val_loader, val_sampler,
                                                interval=ev.get("interval", 8000),
                                                num_batches=eval_num_batches or ev.get("num_batches", 4),
                                                num_classes=model.num_classes, logger=logger,
-                                               apply_input_shape=apply_input_shape))
+                                               apply_input_shape=apply_input_shape,
+                                               calibrator=BNCalibrator(model, calib)
+                                               if calib is not None else None))
     if checkpoints:
         if cfg.get("resume_from"):
             runner.resume(cfg.resume_from)

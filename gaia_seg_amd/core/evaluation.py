@@ -7,6 +7,8 @@ design: predictions never leave the device — each batch is folded into a CxC c
 HIP kernel (``gs_confusion_matrix``) and the matrices (not pickled per-image results as in
 gaiaseg/apis/test.py:119-173) are summed across ranks with one all-reduce.
 """
+import contextlib
+
 import torch
 
 from ..hip import lib as _lib
@@ -97,12 +99,16 @@ def evaluate_model(model, loader, num_batches, num_classes, ignore_index=255, in
 
 class CrossArchEvalHook(Hook):
     """Every ``interval`` iterations evaluate every val anchor (cross_arch_eval_hooks.py:59-92).
-    ``apply_input_shape``: an anchor that carries ``data.input_shape`` is evaluated at that size."""
+    ``apply_input_shape``: an anchor that carries ``data.input_shape`` is evaluated at that size.
+    ``calibrator`` (core.bn_calibration.BNCalibrator over the runner's model): every anchor is
+    evaluated under BatchNorm statistics re-calibrated for it; the training run's running statistics
+    and counters are put back bit for bit."""
 
     def __init__(self, dataloader, model_sampler, interval=1, num_batches=4, num_classes=19,
-                 ignore_index=255, logger=None, apply_input_shape=False):
+                 ignore_index=255, logger=None, apply_input_shape=False, calibrator=None):
         check_tta_input_shape(dataloader, apply_input_shape)
         self.apply_input_shape = apply_input_shape
+        self.calibrator = calibrator
         self.dataloader, self.sampler = dataloader, model_sampler
         self.interval, self.num_batches = interval, num_batches
         self.num_classes, self.ignore_index = num_classes, ignore_index
@@ -127,9 +133,11 @@ class CrossArchEvalHook(Hook):
         for i, meta in enumerate(metas):
             meta = gdist.broadcast_object(meta, src=0)   # :59 broadcast_object(fold_dict(meta))
             runner.model.manipulate_arch(fold_dict(meta)["arch"])
-            res = evaluate_model(runner.model, self.dataloader, self.num_batches,
-                                 self.num_classes, self.ignore_index,
-                                 input_shape=meta.get(INPUT_SHAPE_KEY) if self.apply_input_shape else None)
+            input_shape = meta.get(INPUT_SHAPE_KEY) if self.apply_input_shape else None
+            with (self.calibrator.calibrated(input_shape) if self.calibrator is not None
+                  else contextlib.nullcontext()):
+                res = evaluate_model(runner.model, self.dataloader, self.num_batches,
+                                     self.num_classes, self.ignore_index, input_shape=input_shape)
             name = meta.get("name", str(i))
             out[name] = res
             msg = "eval %s: mIoU %.4f mAcc %.4f aAcc %.4f" % (name, res["mIoU"], res["mAcc"], res["aAcc"])

@@ -627,6 +627,33 @@ __global__ __launch_bounds__(256) void bn_sync_merge_kernel(const double* __rest
   merged[2 * C + c] = (float)gmean;
 }
 
+// ---------------- BatchNorm re-calibration fold (one launch over every visited layer) -----------
+// One workgroup per table entry; entry i owns bank[offset .. offset + 2c) = [mean[c] | var[c]].
+// A moved statistic is one fp32 operation, so the order of threads does not matter to the result.
+// An entry that does not fit the bank (or has a null buffer) is skipped, never followed.
+__global__ __launch_bounds__(256) void bn_calib_fold_kernel(const GsBnCalibLayer* __restrict__ layers,
+                                                            float* bank, long bank_floats, int op,
+                                                            float scale) {
+  const GsBnCalibLayer e = layers[blockIdx.x];
+  const int c = e.channels;
+  if (c < 0 || e.offset < 0 || (long)e.offset + 2L * c > bank_floats) return;
+  if (!e.running_mean || !e.running_var) return;
+  float* bm = bank + e.offset;
+  float* bv = bm + c;
+  for (int i = threadIdx.x; i < c; i += blockDim.x) {
+    if (op == GS_BN_CALIB_SAVE) {
+      bm[i] = e.running_mean[i];
+      bv[i] = e.running_var[i];
+    } else if (op == GS_BN_CALIB_ADD) {
+      bm[i] = bm[i] + e.running_mean[i];
+      bv[i] = bv[i] + e.running_var[i];
+    } else {
+      e.running_mean[i] = bm[i] * scale;
+      e.running_var[i] = bv[i] * scale;
+    }
+  }
+}
+
 // ---- host helpers ----
 struct RedGeom {
   int gx, gy;
@@ -958,5 +985,15 @@ extern "C" int gs_bn_sync_merge(const double* gathered, int32_t world, int32_t C
   if (C <= 0 || world <= 0) return GS_E_BADARG;
   hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((C + 255) / 256), dim3(256), 0, as_stream(stream),
                      gathered, world, C, merged);
+  return launch_status();
+}
+
+extern "C" int gs_bn_calib_fold(const GsBnCalibLayer* layers, int32_t n_layers, float* bank,
+                                int64_t bank_floats, int32_t op, float scale, void* stream) {
+  if (!layers || !bank) return GS_E_NULL;
+  if (n_layers <= 0 || bank_floats <= 0 || op < GS_BN_CALIB_SAVE || op > GS_BN_CALIB_WRITE)
+    return GS_E_BADARG;
+  hipLaunchKernelGGL(bn_calib_fold_kernel, dim3(n_layers), dim3(256), 0, as_stream(stream), layers,
+                     bank, (long)bank_floats, (int)op, scale);
   return launch_status();
 }

@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class HipLibraryError(RuntimeError):
@@ -175,6 +175,15 @@ class SgdChunk(Structure):
     _fields_ = [(k, c_int32) for k in ("begin", "length", "group", "reserved")]
 
 
+class BnCalibLayer(Structure):
+    """Mirror of ``GsBnCalibLayer``: one BatchNorm's buffers, its active width and its bank offset."""
+    _fields_ = [("running_mean", c_void_p), ("running_var", c_void_p), ("channels", c_int32),
+                ("offset", c_int32)]
+
+
+BN_CALIB_SAVE, BN_CALIB_ADD, BN_CALIB_WRITE = 0, 1, 2   # GS_BN_CALIB_*
+
+
 _P = c_void_p  # device pointers and the stream travel as plain addresses
 _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
 _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
@@ -199,6 +208,7 @@ PROTOTYPES = {
     "gs_bn_sync_merge": (_i32, [_P, _i32, _i32, _P, _P]),
     "gs_bn_stats_finalize": (_i32, [_P, _i64, _i32, _i32, _P, _P, _f32, _f32, _P, _P, _P, _P, _sz,
                                     _P]),
+    "gs_bn_calib_fold": (_i32, [_P, _i32, _P, _i64, _i32, _f32, _P]),
     "gs_bn_eval_coeffs": (_i32, [_P, _P, _i32, _P, _P, _f32, _P, _P]),
     "gs_bn_apply": (_i32, [_P, _i64, _i32, _i32, _P, _P, _i32, _i32, _P, _i32, _P]),
     "gs_bn_apply_mask": (_i32, [_P, _i64, _i32, _i32, _P, _P, _i32, _P, _i32, _P, _P]),

@@ -183,6 +183,32 @@ int gs_bn_bwd_apply(const float* dy, int32_t ld_dy, const float* x, int32_t ldx,
                     int32_t use_batch_stats, float* dx, int32_t ld_dx, float* dgamma,
                     float* dbeta, void* stream);
 
+/* Per-subnet BatchNorm re-calibration (core/bn_calibration.py): one table-driven launch that
+ * moves the leading `channels` running statistics of every listed BatchNorm between its buffers
+ * and a flat fp32 bank, layer i at bank[offset_i .. offset_i + 2*channels_i) = [mean[c] | var[c]].
+ *   GS_BN_CALIB_SAVE  : bank  = running            (snapshot; first batch of an accumulation)
+ *   GS_BN_CALIB_ADD   : bank += running            (further batches; momentum-1 forwards leave
+ *                                                   the batch's own statistics in the buffers)
+ *   GS_BN_CALIB_WRITE : running = bank * scale     (scale 1/K commits the average of K batches,
+ *                                                   scale 1 from a SAVE bank restores bit for bit)
+ * `scale` is read by WRITE only, which multiplies (it never divides).  One fp32 operation per
+ * element in a fixed order: results are bit-reproducible.  `layers` and `bank` are device memory;
+ * channels beyond a layer's `channels` and bank floats outside the layers' ranges are never
+ * touched.  GS_E_NULL (layers or bank) / GS_E_BADARG (n_layers <= 0, bank_floats <= 0, op outside
+ * 0..2) before any launch.  An entry with channels < 0, offset < 0, offset + 2*channels >
+ * bank_floats or a null buffer pointer is skipped by the kernel, not followed. */
+typedef struct GsBnCalibLayer {
+  float* running_mean; /* device pointers of one BatchNorm's buffers */
+  float* running_var;
+  int32_t channels;    /* active leading channels c */
+  int32_t offset;      /* first float of this layer's [mean[c] | var[c]] in the bank */
+} GsBnCalibLayer;
+#define GS_BN_CALIB_SAVE 0
+#define GS_BN_CALIB_ADD 1
+#define GS_BN_CALIB_WRITE 2
+int gs_bn_calib_fold(const GsBnCalibLayer* layers, int32_t n_layers, float* bank,
+                     int64_t bank_floats, int32_t op, float scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* conv -> BatchNorm (+ residual) (+ ReLU) issued by ONE host call per direction               */
 /* ------------------------------------------------------------------------------------------ */
