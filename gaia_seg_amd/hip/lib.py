@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class HipLibraryError(RuntimeError):
@@ -128,6 +128,13 @@ class PairwiseDesc(Structure):
                 [("T", c_float), ("reserved2", c_int32)])
 
 
+class CwdDesc(Structure):
+    """Mirror of ``gs_cwd_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("N", "C", "H", "W")] +
+                [(k, c_int64) for k in ("s_sn", "s_sc", "s_sh", "s_sw", "t_sn", "t_sc", "t_sh", "t_sw")] +
+                [("T", c_float), ("reserved", c_int32)])
+
+
 class SlideDesc(Structure):
     """Mirror of ``gs_slide_desc``."""
     _fields_ = [(k, c_int32) for k in ("N", "C", "ld", "hl", "wl", "hc", "wc", "H", "W", "Ho", "Wo",
@@ -187,7 +194,7 @@ BN_CALIB_SAVE, BN_CALIB_ADD, BN_CALIB_WRITE = 0, 1, 2   # GS_BN_CALIB_*
 _P = c_void_p  # device pointers and the stream travel as plain addresses
 _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
 _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
-_DD, _PW = POINTER(DistillDesc), POINTER(PairwiseDesc)
+_DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -254,6 +261,10 @@ PROTOTYPES = {
     "gs_pairwise_save_bytes": (_sz, [_PW]),
     "gs_pairwise_forward": (_i32, [_PW, _P, _P, _f32, _P, _P, _sz, _P]),
     "gs_pairwise_backward": (_i32, [_PW, _P, _P, _sz, _f32, _P, _i32, _P]),
+    "gs_cwd_workspace_bytes": (_sz, [_CW]),
+    "gs_cwd_forward": (_i32, [_CW, _P, _P, _P, _P, _f32, _P, _P, _sz, _P]),
+    "gs_cwd_backward": (_i32, [_CW, _P, _P, _P, _P, _f32, _P, _i32, _P]),
+    "gs_cwd_debug_partials": (_i32, [_CW]),
     "gs_slide_fuse": (_i32, [POINTER(SlideDesc), POINTER(_i32), POINTER(_i32), _P, _P, _P, _P, _P]),
     "gs_debug_set_slide_strip": (_i32, [_i32]),
     "gs_seg_augment": (_i32, [POINTER(AugmentDesc), _P, _P, _P, _P, _P]),

@@ -243,3 +243,74 @@ def pairwise_loss(student_feat, teacher_feat, window, T=1, weight=1):
     scale = float(weight) / (student_feat.shape[0] * step_h * step_w)
     return _Pairwise.apply(student_feat, teacher_feat.detach(), tuple(int(v) for v in window[:4]),
                            float(T), scale)
+
+
+# ---- channel-wise distillation (Shu et al., ICCV 2021; mmrazor's ChannelWiseDivergence) ----
+def _cwd_check_shapes(student, teacher):
+    if student.dim() != 4 or tuple(teacher.shape) != tuple(student.shape):
+        raise ValueError("channel-wise distillation needs student logits %s and teacher logits %s of one "
+                         "shape (a teacher at another output stride is not supported)"
+                         % (tuple(student.shape), tuple(teacher.shape)))
+
+
+def cwd_desc(student, teacher, T):
+    _cwd_check_shapes(student, teacher)
+    d = _lib.CwdDesc()
+    d.N, d.C, d.H, d.W = student.shape
+    d.s_sn, d.s_sc, d.s_sh, d.s_sw = student.stride()
+    d.t_sn, d.t_sc, d.t_sh, d.t_sw = teacher.stride()
+    d.T = float(T)
+    return d
+
+
+class _ChannelDistill(torch.autograd.Function):
+    """scale * T^2 * sum_{n,c} KL(softmax_pixels(t/T) || softmax_pixels(s/T)) as one fp32 scalar
+    (gs_cwd_*); gradient to the student's logits only."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, T, scale):
+        require_gpu_tensor(student, "seg_logit")
+        require_gpu_tensor(teacher, "teacher_logits")
+        L = _lib.load()
+        dev = student.device
+        d = cwd_desc(student, teacher, T)
+        lse_s = torch.empty((d.N, d.C), dtype=torch.float32, device=dev)
+        lse_t = torch.empty_like(lse_s)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = WORKSPACE.get(L.gs_cwd_workspace_bytes(ctypes.byref(d)), dev)
+        _lib.check(L.gs_cwd_forward(ctypes.byref(d), student.data_ptr(), teacher.data_ptr(),
+                                    lse_s.data_ptr(), lse_t.data_ptr(), float(scale), out.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), current_stream_ptr()), "gs_cwd_forward")
+        ctx.desc, ctx.scale = d, float(scale)
+        ctx.save_for_backward(student, teacher, lse_s, lse_t)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        from ...hip import ops as _ops
+        prev_slot = _ops.adopt_current_stream()
+        try:
+            student, teacher, lse_s, lse_t = ctx.saved_tensors
+            L = _lib.load()
+            n, c, h, w = student.shape
+            ld = round_up(c, 4)
+            buf = torch.empty((n, h, w, ld), dtype=torch.float32, device=student.device)
+            _lib.check(L.gs_cwd_backward(ctypes.byref(ctx.desc), student.data_ptr(), teacher.data_ptr(),
+                                         lse_s.data_ptr(), lse_t.data_ptr(), ctx.scale, buf.data_ptr(),
+                                         ld, current_stream_ptr()), "gs_cwd_backward")
+            buf.mul_(grad_loss)   # the upstream scalar, on the device (no host sync)
+            return buf[..., :c].permute(0, 3, 1, 2), None, None, None
+        finally:
+            _ops.restore_stream_slot(prev_slot)
+
+
+def channel_distill_loss(student, teacher, T=1, weight=1):
+    """Channel-wise distillation of two logit maps of one shape [N, C, H, W]: every class map becomes a
+    distribution over its H * W pixels (softmax of x / T), and the loss is
+    weight * T^2 / (N * C) * sum_{n,c} KL(phi(teacher) || phi(student)) -- mmrazor's
+    ChannelWiseDivergence.  No labels, no resize; ``teacher`` is detached."""
+    require_gpu_tensor(student, "seg_logit")
+    require_gpu_tensor(teacher, "teacher_logits")
+    _cwd_check_shapes(student, teacher)
+    scale = float(weight) / (student.shape[0] * student.shape[1])
+    return _ChannelDistill.apply(student, teacher.detach(), float(T), scale)

@@ -4,7 +4,9 @@ Host-side mirror of gaiaseg/models/segmentors/dynamic_distiller.py:152-413, quir
 student's decode-head losses come without the 'decode.' prefix, both logit maps are resized with the
 STUDENT's align_corners, the logit loss has no T^2 factor, and the pairwise loss is taken on the
 single column the reference's slice selects (:329-330).  The two distillation losses run on the HIP
-kernels of csrc/distill.hip (models/losses/distill_loss.py).
+kernels of csrc/distill.hip (models/losses/distill_loss.py).  Not in the reference: the opt-in
+channel-wise distillation loss ``channel_loss_seg`` of csrc/cwd.hip on the two low-resolution logit maps
+(DESIGN.md section 24), the structural term the one-column pairwise loss does not provide.
 
 Deliberate deviation: the teacher is held OUTSIDE module registration.  It is
 absent from parameters(), modules(), state_dict() and active_parameters(), so the parameter arena,
@@ -17,7 +19,8 @@ import torch
 
 from ...hip import ops
 from ..builder import SEGMENTORS, build_segmentor
-from ..losses.distill_loss import draw_pairwise_window, pairwise_loss, teacher_distill_loss
+from ..losses.distill_loss import (channel_distill_loss, draw_pairwise_window, pairwise_loss,
+                                   teacher_distill_loss)
 from .dynamic_encoder_decoder import DynamicEncoderDecoder
 
 @SEGMENTORS.register_module()
@@ -29,7 +32,8 @@ class DynamicDistiller(DynamicEncoderDecoder):
     def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, teacher_segmentor=None,
                  train_cfg=None, test_cfg=None, pretrained=None, teacher_ckpt=None,
                  has_distill_loss=True, distill_loss_temperature=1, has_pairwise_loss=True,
-                 pairwise_loss_temperature=1, distill_loss_weight=1, pairwise_loss_weight=1):
+                 pairwise_loss_temperature=1, distill_loss_weight=1, pairwise_loss_weight=1,
+                 has_channel_loss=False, channel_loss_temperature=1, channel_loss_weight=1):
         super().__init__(backbone=backbone, decode_head=decode_head, neck=neck,
                          auxiliary_head=auxiliary_head, train_cfg=train_cfg, test_cfg=test_cfg,
                          pretrained=pretrained)
@@ -39,8 +43,12 @@ class DynamicDistiller(DynamicEncoderDecoder):
         self.distill_loss_weight = distill_loss_weight
         self.pairwise_loss_temperature = pairwise_loss_temperature
         self.pairwise_loss_weight = pairwise_loss_weight
+        self.has_channel_loss = bool(has_channel_loss)
+        self.channel_loss_temperature = channel_loss_temperature
+        self.channel_loss_weight = channel_loss_weight
         teacher = None
-        if self.has_distill_loss or self.has_pairwise_loss:   # (:190-206; both off: "debug mode")
+        # (:190-206; all off: "debug mode")
+        if self.has_distill_loss or self.has_pairwise_loss or self.has_channel_loss:
             if teacher_segmentor is None:
                 raise ValueError("DynamicDistiller: teacher_segmentor (the teacher's model config) is "
                                  "missing")
@@ -81,7 +89,8 @@ class DynamicDistiller(DynamicEncoderDecoder):
 
     def forward_train(self, img, img_metas, gt_semantic_seg):
         """(:370-413)"""
-        distill = (self.has_distill_loss or self.has_pairwise_loss) and self.teacher_segmentor is not None
+        distill = ((self.has_distill_loss or self.has_pairwise_loss or self.has_channel_loss)
+                   and self.teacher_segmentor is not None)
         if distill:
             teacher_x, teacher_logits = self.prepare_distill_feature(img, img_metas)
         x = self.extract_feat(img)
@@ -101,6 +110,11 @@ class DynamicDistiller(DynamicEncoderDecoder):
             losses["pairwise_loss_seg"] = pairwise_loss(
                 feat, teacher_x[-1], window, T=self.pairwise_loss_temperature,
                 weight=self.pairwise_loss_weight)
+        if distill and self.has_channel_loss:
+            # at logit resolution: a teacher at another output stride is refused (ValueError, both shapes)
+            losses["channel_loss_seg"] = channel_distill_loss(
+                seg_logits, teacher_logits, T=self.channel_loss_temperature,
+                weight=self.channel_loss_weight)
         if self.with_auxiliary_head:
             with ops.branch_scope(dev, branch, forked=True):
                 loss_aux = self._auxiliary_head_forward_train(x, img_metas, gt_semantic_seg)

@@ -547,6 +547,43 @@ int gs_pairwise_forward(const gs_pairwise_desc* d, const float* student, const f
 int gs_pairwise_backward(const gs_pairwise_desc* d, const float* student, void* save,
                          size_t save_bytes, float grad_scale, float* ds, int32_t ld_d, void* stream);
 
+/* Channel-wise distillation (Shu et al., ICCV 2021; mmrazor's ChannelWiseDivergence) of two logit maps
+ * of one shape [N, C, H, W], each with element strides of its own.  With phi(x)[n,c,:] the softmax of
+ * x[n,c,:] / T over the P = H * W PIXELS of one class map,
+ *   out[0] = scale * T^2 * sum_{n,c} sum_p phi(t) * (log phi(t) - log phi(s))
+ * with the host's scale = weight / (N * C).  One pass: every logit is read once, no [N, C, H, W]
+ * temporary is written.  A column (n, c) is five running numbers (the two maxima, Z_s, Z_t and
+ * A = sum e_t (t - s) / T; KL = A / Z_t + (m_s - m_t) / T + log Z_s - log Z_t) whose partial states
+ * combine associatively; a map is split over gs_cwd_debug_partials(d) workgroups by pixel range, a
+ * second launch (one wave per class map) rescales the partials to the map's maxima and sums them in
+ * double in a fixed order, and a third sums the N * C column losses in double in a fixed order:
+ * bit-reproducible, no float atomics.  The split depends on the descriptor alone.  Channels-last maps
+ * (c stride 1; the other strides and the base addresses multiples of 4 floats) are read as float4s,
+ * the partial last quad by scalars: the pad columns C .. ld-1 are never read.  Any other layout is
+ * read by scalars.
+ * lse_s / lse_t: float [N, C], written by the forward: m / T + log Z of each class map.
+ * workspace: gs_cwd_workspace_bytes(d) bytes, 8-byte aligned (GS_E_WORKSPACE when smaller).
+ * GS_E_NULL / GS_E_BADARG (a size <= 0, N > 65535, T <= 0 or infinite) before any launch. */
+typedef struct gs_cwd_desc {
+  int32_t N, C, H, W;
+  int64_t s_sn, s_sc, s_sh, s_sw;   /* student strides (elements)                               */
+  int64_t t_sn, t_sc, t_sh, t_sw;   /* teacher strides                                          */
+  float T;                     /* temperature (> 0)                                             */
+  int32_t reserved;
+} gs_cwd_desc;
+size_t gs_cwd_workspace_bytes(const gs_cwd_desc* d);
+int gs_cwd_forward(const gs_cwd_desc* d, const float* student, const float* teacher, float* lse_s,
+                   float* lse_t, float scale, float* out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* ds[n,y,x,c] = scale * T * (exp(s / T - lse_s[n,c]) - exp(t / T - lse_t[n,c])), elementwise, written
+ * densely at pixel stride ld_d (>= C; columns C..ld_d-1 zeroed).  The teacher receives no gradient. */
+int gs_cwd_backward(const gs_cwd_desc* d, const float* student, const float* teacher,
+                    const float* lse_s, const float* lse_t, float scale, float* ds, int32_t ld_d,
+                    void* stream);
+/* The number of pixel ranges (workgroups) one class map is split into for d's sizes and strides
+ * (>= 1; host arithmetic, no device needed), or a negative GS_E_* for a bad descriptor. */
+int gs_cwd_debug_partials(const gs_cwd_desc* d);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Inference epilogue — K17                                                                    */
 /* ------------------------------------------------------------------------------------------ */
