@@ -205,3 +205,84 @@ def _stream_all_shapes(L, STREAM_CASES, q, widths):
         d = lib.conv_desc(n, h, w, ci, co, k)
         assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_FORWARD, ctypes.byref(q)) == 0
         assert q.kloop != lib.KLOOP_STREAM
+
+
+def test_wgrad_cases_make_their_coverage_claims_without_gpu():
+    """tests/test_wgrad_gpu.py states per case which weight-gradient kernel, tile, split count (hence
+    form of the reduce launch) and loader it is there for.  gs_debug_query_conv_launch is host
+    arithmetic, so every claim is checked here already, and so is what the table covers as a whole (the
+    GPU test re-checks each claim against the launch that really happened)."""
+    import test_wgrad_gpu as T
+    L = lib.load()
+    seen_kloop, seen_bn = set(), {64: set(), 128: set()}
+    seen_reduce, seen_walign, seen_aff = set(), set(), set()
+    for c in T.ALL_CASES:
+        d = T.make_desc(lib, c)
+        if c.aff:
+            d.in_affine = 4096          # any aligned address: the query does not read it
+            assert L.gs_conv2d_in_affine_supported(ctypes.byref(d)) == (0 if T.NO_FAST else 1), c
+        q = lib.DebugLaunch()
+        with T.forced_plan(L, c):
+            assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_WGRAD, ctypes.byref(q)) == 0
+            need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+        T.check_claim(c, d, q)
+        m = d.KH * d.KW * c.ci
+        assert need >= (q.splits * m * c.co * 4 if q.splits > 1 else 0)
+        # the exact leg's integers stay exact in fp32: |x|, |dy| <= 3 (in_affine: activation <= 11)
+        assert c.n * d.Ho * d.Wo * 3 * (11 if c.aff else 3) < 2 ** 22
+        seen_kloop.add(q.kloop)
+        seen_bn[q.bm].add(q.bn)
+        seen_reduce.add((T.reduce_form(q.splits, m, c.co), q.splits >= 48))
+        if c.walign and q.kloop != lib.KLOOP_GENERIC:
+            seen_walign.add((c.stride, q.bm, q.kloop))
+        if c.aff:
+            seen_aff.add((q.kloop, c.walign))
+    if T.NO_FAST:
+        assert seen_kloop == {lib.KLOOP_GENERIC}
+        return
+    assert seen_bn[128] == {128, 96, 80, 64, 48, 32}
+    assert seen_bn[64] >= {80, 64, 48, 32}
+    assert {s for s, _, _ in seen_walign} >= {1, 2} and {b for _, b, _ in seen_walign} == {64, 128}
+    if T.PLAN_ENV:
+        return
+    assert seen_kloop == {lib.KLOOP_GENERIC, lib.KLOOP_FP32, lib.KLOOP_FP32_PAIRS}
+    # the reduce launch: none; sequential; WIDE for >= 48 splits; WIDE for 16..47 splits of few outputs
+    assert seen_reduce >= {("none", False), ("seq", False), ("wide", True), ("wide", False)}
+    assert {k for _, _, k in seen_walign} == {lib.KLOOP_FP32, lib.KLOOP_FP32_PAIRS}
+    assert seen_aff >= {(lib.KLOOP_FP32, True), (lib.KLOOP_FP32, False), (lib.KLOOP_FP32_PAIRS, True)}
+
+
+def test_wgrad_argument_checks_need_no_gpu():
+    """gs_conv2d_wgrad refuses bad arguments before any launch.  (The addresses are never read.)"""
+    L = lib.load()
+    OK_PTR, ODD_PTR = 1 << 20, (1 << 20) + 4
+
+    def call(d, x=OK_PTR, dy=OK_PTR, dw=OK_PTR, ws=OK_PTR, ws_bytes=None):
+        need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+        return L.gs_conv2d_wgrad(ctypes.byref(d), x, dy, dw, ws, need if ws_bytes is None else ws_bytes, None)
+
+    d = lib.conv_desc(2, 13, 17, 48, 48, 3)          # 7 splits: needs a slab
+    q = lib.DebugLaunch()
+    assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_WGRAD, ctypes.byref(q)) == 0
+    assert q.splits > 1
+    slab = q.splits * 9 * 48 * 48 * 4                 # what the weight gradient itself needs
+    assert 0 < slab <= L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+    assert L.gs_conv2d_wgrad(None, OK_PTR, OK_PTR, OK_PTR, OK_PTR, slab, None) == -4
+    assert call(d, x=None) == -4 and call(d, dy=None) == -4 and call(d, dw=None) == -4      # GS_E_NULL
+    assert call(d, dy=ODD_PTR) == -2 and call(d, dw=ODD_PTR) == -2                            # GS_E_ALIGN
+    assert call(d, x=ODD_PTR) == -2                   # a vector source is read as float4
+    assert call(d, ws_bytes=slab - 1) == -3 and call(d, ws=None) == -3                         # GS_E_WORKSPACE
+    assert call(d, ws=None, ws_bytes=0) == -3
+    bad = lib.conv_desc(2, 13, 17, 48, 48, 3)
+    bad.Ho += 1
+    assert call(bad) == -1
+    # in_affine: at most kAffMaxC = 640 channels, a vector source, a 1x1 or 3x3
+    for shape in [(2, 9, 9, 656, 64, 1), (2, 17, 19, 6, 24, 3), (1, 20, 24, 16, 32, 5)]:
+        d = lib.conv_desc(*shape)
+        d.in_affine = OK_PTR
+        assert L.gs_conv2d_in_affine_supported(ctypes.byref(d)) == 0
+        assert call(d) == -1, shape                                                            # GS_E_BADARG
+    d = lib.conv_desc(2, 9, 9, 640, 64, 1)
+    d.in_affine = ODD_PTR
+    if L.gs_conv2d_in_affine_supported(ctypes.byref(d)) == 1:      # (not under GS_NO_FAST)
+        assert call(d) == -2
