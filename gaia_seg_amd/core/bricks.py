@@ -99,17 +99,24 @@ class DynamicConv2d(nn.Module, DynamicMixin):
     """Conv2d over the leading slice of a max-size weight: ``F.conv2d(x, W[:width, :x.size(1)])``.
 
     ``width_state`` is the active number of output channels; the active number of input channels
-    is taken from the input tensor."""
+    is taken from the input tensor.
+
+    ``groups == in_channels == out_channels`` with a 3x3 kernel and stride 1 is the depthwise form
+    (mmcv's DepthwiseSeparableConvModule.depthwise_conv): the logical weight is [C, 1, 3, 3], both
+    active widths are the input's channel count, and it runs on the depthwise kernels
+    (ops.dwconv2d).  Every other grouping is refused."""
     search_space = {"width"}
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
                  groups=1, bias=True, padding_mode="zeros"):
         super().__init__()
-        if groups != 1:
+        kh, kw = _pair(kernel_size)
+        depthwise = (groups != 1 and groups == in_channels == out_channels and (kh, kw) == (3, 3)
+                     and _pair(stride) == (1, 1))
+        if groups != 1 and not depthwise:
             raise NotImplementedError("DynConv2d: groups != 1 is not used on the supernet hot path")
         if padding_mode != "zeros":
             raise NotImplementedError("DynConv2d: only zero padding is supported")
-        kh, kw = _pair(kernel_size)
         sh, sw = _pair(stride)
         ph, pw = _pair(padding)
         dh, dw = _pair(dilation)
@@ -117,9 +124,10 @@ class DynamicConv2d(nn.Module, DynamicMixin):
             raise NotImplementedError("DynConv2d: anisotropic stride/padding/dilation unsupported")
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding, self.dilation = (kh, kw), sh, ph, dh
-        self.groups = 1
+        self.groups = groups
+        self.depthwise = depthwise
         co_ld = round_up(out_channels, 4)
-        phys = torch.zeros(kh, kw, in_channels, co_ld)
+        phys = torch.zeros(kh, kw, 1 if depthwise else in_channels, co_ld)
         self.weight = nn.Parameter(hwio_logical_view(phys, out_channels))
         if bias:
             self.bias = nn.Parameter(torch.zeros(co_ld)[:out_channels])
@@ -132,14 +140,15 @@ class DynamicConv2d(nn.Module, DynamicMixin):
     def reset_parameters(self):
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
         if self.bias is not None:
-            fan_in = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
+            fan_in = self.weight.shape[1] * self.kernel_size[0] * self.kernel_size[1]
             bound = 1 / math.sqrt(fan_in) if fan_in > 0 else 0
             nn.init.uniform_(self.bias, -bound, bound)
 
     def extra_repr(self):
-        return "%d, %d, kernel_size=%s, stride=%d, padding=%d, dilation=%d, bias=%s, width=%s" % (
+        return "%d, %d, kernel_size=%s, stride=%d, padding=%d, dilation=%d, %sbias=%s, width=%s" % (
             self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
-            self.dilation, self.bias is not None, self.width_state)
+            self.dilation, "groups=%d, " % self.groups if self.depthwise else "",
+            self.bias is not None, self.width_state)
 
     # ---- dynamic interface ----
     def manipulate_width(self, width):
@@ -166,6 +175,9 @@ class DynamicConv2d(nn.Module, DynamicMixin):
         self._check_layout()
         if getattr(self, "_deploying", False):
             self._deploy_slice(x.t.shape[1] if x.nchw_image else x.C)
+        if self.depthwise:
+            return ops.dwconv2d(tape, x, self.weight, self.padding, self.dilation, out=out,
+                                bias=self.bias)
         return ops.conv2d(tape, x, self.weight, self.bias, self.width_state, self.stride,
                           self.padding, self.dilation, out=out, tag=tag)
 
@@ -176,11 +188,14 @@ class DynamicConv2d(nn.Module, DynamicMixin):
     def _deploy_slice(self, ci):
         """Physically prune to [:width, :ci] (tools/extract_subnet.py semantics)."""
         co = self.width_state
+        if self.depthwise:   # one filter per channel: both widths are the input's
+            co, ci, self.groups = ci, 1, ci
         if self.weight.shape[0] == co and self.weight.shape[1] == ci:
             return
         w = self.weight.data[:co, :ci].clone()
         b = self.bias.data[:co].clone() if self.bias is not None else None
-        self.in_channels, self.out_channels = ci, co
+        self.in_channels, self.out_channels = (co, co) if self.depthwise else (ci, co)
+        self.width_state = co
         kh, kw = self.kernel_size
         phys = torch.zeros((kh, kw, ci, round_up(co, 4)), dtype=w.dtype, device=w.device)
         view = hwio_logical_view(phys, co)
@@ -365,7 +380,7 @@ _NO_FUSED_CALLS = os.environ.get("GS_NO_FUSED_CALLS") is not None
 def fused_call_ok(conv, norm):
     """conv -> norm can go through the one-call-per-direction entry (ops.conv_bn): a bias-free conv of a
     width that is a multiple of 4 followed by a rank-local BatchNorm, not while extracting a subnet."""
-    return (conv._parameters["bias"] is None and conv.width_state % 4 == 0
+    return (conv._parameters["bias"] is None and conv.width_state % 4 == 0 and not conv.depthwise
             and not conv.__dict__.get("_deploying", False)
             and not norm.__dict__.get("_deploying", False) and not _NO_FUSED_CALLS
             and not (norm.training and norm.sync is not None and norm._process_group() is not None))
@@ -377,11 +392,13 @@ def conv_bn_act(tape, conv, norm, x, relu=False, residual=None, out=None, tag=No
     loaders where the fused path allows it (ops.conv_bn).  Rank-local BatchNorm after a bias-free conv goes through
     the one-call-per-direction library entry (ops.conv_bn); SyncBN with a process group, a conv
     bias, widths that are not multiples of 4 and subnet extraction take the module-by-module path.
-    Both paths launch the same kernels."""
+    Both paths launch the same kernels.  A depthwise conv takes the module-by-module path too: its
+    kernels (ops.dwconv2d) are followed by ops.batchnorm."""
     c = conv.width_state
     cd = conv.__dict__
     weight = conv._parameters["weight"]
     fused = (conv._parameters["bias"] is None and c % 4 == 0 and not cd.get("_deploying", False)
+             and not cd["depthwise"]
              and not norm.__dict__.get("_deploying", False) and not _NO_FUSED_CALLS)
     if fused:
         bnp = norm.bn_params(c)
@@ -460,6 +477,38 @@ class DynamicConvModule(nn.Module, DynamicMixin):
         needs = any(p.requires_grad for p in self.parameters())
         return tape_function(
             lambda tape, acts: [self.forward_act(tape, acts[0], activate, norm)], [x], needs)[0]
+
+
+class DynamicDepthwiseSeparableConvModule(nn.Module, DynamicMixin):
+    """mmcv's DepthwiseSeparableConvModule with dynamic widths: a depthwise 3x3 ConvModule
+    (in -> in, groups = in) followed by a pointwise 1x1 ConvModule (in -> out), each conv -> norm ->
+    ReLU.  ``dw_*`` / ``pw_*`` default to ``norm_cfg`` / ``act_cfg`` as in mmcv."""
+    search_space = {"width"}
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
+                 conv_cfg=None, norm_cfg=None, act_cfg=dict(type="ReLU"), dw_norm_cfg="default",
+                 dw_act_cfg="default", pw_norm_cfg="default", pw_act_cfg="default"):
+        super().__init__()
+        dw_norm_cfg = norm_cfg if dw_norm_cfg == "default" else dw_norm_cfg
+        dw_act_cfg = act_cfg if dw_act_cfg == "default" else dw_act_cfg
+        pw_norm_cfg = norm_cfg if pw_norm_cfg == "default" else pw_norm_cfg
+        pw_act_cfg = act_cfg if pw_act_cfg == "default" else pw_act_cfg
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.depthwise_conv = DynamicConvModule(
+            in_channels, in_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
+            groups=in_channels, conv_cfg=conv_cfg, norm_cfg=dw_norm_cfg, act_cfg=dw_act_cfg)
+        self.pointwise_conv = DynamicConvModule(in_channels, out_channels, 1, conv_cfg=conv_cfg,
+                                                norm_cfg=pw_norm_cfg, act_cfg=pw_act_cfg)
+
+    def manipulate_width(self, width):
+        self.pointwise_conv.manipulate_width(width)
+
+    def forward_act(self, tape, x, out=None):
+        return self.pointwise_conv.forward_act(tape, self.depthwise_conv.forward_act(tape, x), out=out)
+
+    def forward(self, x):
+        needs = any(p.requires_grad for p in self.parameters())
+        return tape_function(lambda tape, acts: [self.forward_act(tape, acts[0])], [x], needs)[0]
 
 
 # ------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@ from .bricks import DynamicConv2d
 def _conv(m, cin, h, w):
     co = m.width_state
     kh, kw = m.kernel_size
+    if m.depthwise:   # one filter per channel: the output width is the input's, one input channel each
+        co, cin = cin, 1
     ho = conv_out_size(h, kh, m.stride, m.padding, m.dilation)
     wo = conv_out_size(w, kw, m.stride, m.padding, m.dilation)
     flops = 2.0 * ho * wo * co * cin * kh * kw
@@ -81,6 +83,39 @@ def psp_head_flops(head, c, h, w):
     return total + f
 
 
+def _conv_module(m, c, h, w):
+    """(flops, output width) of a DynamicConvModule or DynamicDepthwiseSeparableConvModule."""
+    if hasattr(m, "depthwise_conv"):
+        fd, _, c, h, w = _conv(m.depthwise_conv.conv, c, h, w)
+        fp, _, c, _, _ = _conv(m.pointwise_conv.conv, c, h, w)
+        return fd + fp, c
+    f, _, c, _, _ = _conv(m.conv, c, h, w)
+    return f, c
+
+
+def aspp_head_flops(head, feats):
+    """DynamicASPPHead / DynamicDepthwiseSeparableASPPHead: the image-pool 1x1 conv on one pixel, one
+    branch per dilation and the 3x3 bottleneck at the input's size; for DeepLabV3+ also the 1x1
+    c1_bottleneck and the two separable convs at the first level's size, where the classifier then
+    runs."""
+    c, h, w = feats[head.in_index % len(feats)]
+    total = _conv_module(head.image_pool[1], c, 1, 1)[0]
+    for m in head.aspp_modules:
+        total += _conv_module(m, c, h, w)[0]
+    f, cb = _conv_module(head.bottleneck, (len(head.dilations) + 1) * head.channels, h, w)
+    total += f
+    if hasattr(head, "sep_bottleneck"):
+        if head.c1_bottleneck is not None:
+            c1, h, w = feats[0]
+            f, c1 = _conv_module(head.c1_bottleneck, c1, h, w)
+            total += f
+            cb += c1
+        for m in head.sep_bottleneck:
+            f, cb = _conv_module(m, cb, h, w)
+            total += f
+    return total + _conv(head.conv_seg, cb, h, w)[0]
+
+
 def uper_head_flops(head, feats):
     """DynamicUPerHead (gaiaseg/models/decode_heads/dynamic_uper_head.py:81-131): PPM + bottleneck on
     the last level, one 1x1 lateral and one 3x3 fpn conv per other level at that level's size, the
@@ -116,6 +151,8 @@ def model_flops(model, h, w):
             out[key] = psp_head_flops(head, c, fh, fw)
         elif name == "DynamicUPerHead":
             out[key] = uper_head_flops(head, feats)
+        elif name in ("DynamicASPPHead", "DynamicDepthwiseSeparableASPPHead"):
+            out[key] = aspp_head_flops(head, feats)
         else:
             out[key] = float("nan")
     out["total"] = sum(v for k, v in out.items() if k in ("backbone", "decode", "aux") and v == v)

@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class HipLibraryError(RuntimeError):
@@ -56,6 +56,24 @@ def conv_desc(n, h, w, ci, co, k, stride=1, dil=1, pad=None, ci_max=None, co_ld=
     d.x_sn, d.x_sh, d.x_sw, d.x_sc = h * w * ldx, w * ldx, ldx, 1
     d.ldy, d.ld_add = co if ldy is None else ldy, ld_add
     d.role = role
+    return d
+
+
+class DwConvDesc(Structure):
+    """Mirror of ``gs_dwconv_desc``."""
+    _fields_ = [(k, c_int32) for k in ("N", "H", "W", "C", "C_ld", "KH", "KW", "stride", "pad", "dil",
+                                       "ldx", "ldy")]
+
+
+def dwconv_desc(n, h, w, c, pad, dil=1, c_ld=None, ldx=None, ldy=None, k=3, stride=1):
+    """A ``DwConvDesc`` for a packed-NHWC input [n, h, w, c] (row pitch ``ldx``, default c), a weight of
+    tap pitch ``c_ld`` (default c) and output row pitch ``ldy`` (default c)."""
+    d = DwConvDesc()
+    d.N, d.H, d.W, d.C = n, h, w, c
+    d.C_ld = c if c_ld is None else c_ld
+    d.KH = d.KW = k
+    d.stride, d.pad, d.dil = stride, pad, dil
+    d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
     return d
 
 
@@ -195,6 +213,7 @@ _P = c_void_p  # device pointers and the stream travel as plain addresses
 _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
 _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
 _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
+_DW = POINTER(DwConvDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -206,6 +225,10 @@ PROTOTYPES = {
     "gs_conv2d_forward": (_i32, [_CD, _P, _P, _P, _P, _P, _P, _sz, _P]),
     "gs_conv2d_dgrad": (_i32, [_CD, _P, _P, _P, _i32, _P, _sz, _P]),
     "gs_conv2d_wgrad": (_i32, [_CD, _P, _P, _P, _P, _sz, _P]),
+    "gs_dwconv2d_workspace_bytes": (_sz, [_DW]),
+    "gs_dwconv2d_forward": (_i32, [_DW, _P, _P, _P, _P, _P]),
+    "gs_dwconv2d_dgrad": (_i32, [_DW, _P, _P, _P, _i32, _P]),
+    "gs_dwconv2d_wgrad": (_i32, [_DW, _P, _P, _P, _P, _sz, _P]),
     "gs_colsum_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_colsum": (_i32, [_P, _i64, _i32, _i32, _P, _P, _sz, _P]),
     "gs_bn_stats_workspace_bytes": (_sz, [_i64, _i32]),

@@ -710,6 +710,61 @@ def conv2d(tape, x, weight, bias, co, stride=1, pad=0, dil=1, out=None, tag=None
     return out
 
 
+def dwconv2d(tape, x, weight, pad, dil=1, out=None, bias=None):
+    """Depthwise 3x3 DynConv2d forward (stride 1): y = conv(x, weight[:x.C], groups = x.C) (+ bias[:x.C]).
+
+    ``weight`` is the max-size Parameter, logical [C_max, 1, 3, 3], physical HWIO [3][3][1][C_ld]; the
+    active width is x.C.  fp32 in every precision mode (the kernels are bandwidth-bound); everything
+    runs on the current stream, the weight gradient included."""
+    _check_precision(tape)
+    L = _L()
+    x = materialize(tape, x)
+    c_max, ci, kh, kw = weight.shape
+    c = x.C
+    if ci != 1 or (kh, kw) != (3, 3):
+        raise ValueError("dwconv2d needs a [C, 1, 3, 3] weight, got %s" % (tuple(weight.shape),))
+    if c > c_max:
+        raise ValueError("input has %d channels, conv supports at most %d" % (c, c_max))
+    if c % 4:
+        raise ValueError("dwconv2d needs a channel count that is a multiple of 4, got %d" % c)
+    dev = x.t.device
+    ho, wo = conv_out_size(x.H, 3, 1, pad, dil), conv_out_size(x.W, 3, 1, pad, dil)
+    if out is None:
+        out = Act.empty(x.N, ho, wo, c, dev)
+    d = _lib.dwconv_desc(x.N, x.H, x.W, c, pad, dil, c_ld=weight.stride(1), ldx=x.ld, ldy=out.ld)
+    _lib.check(L.gs_dwconv2d_forward(ctypes.byref(d), x.ptr, weight.data_ptr(),
+                                     bias.data_ptr() if bias is not None else None, out.ptr,
+                                     current_stream_ptr()), "gs_dwconv2d_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None:
+            return
+        s = current_stream_ptr()
+        db = ctypes.byref(d)
+        if weight.requires_grad:
+            gw = ensure_grad(weight)
+            need = L.gs_dwconv2d_workspace_bytes(db)
+            ws = _ws.get(need, dev)
+            _lib.check(L.gs_dwconv2d_wgrad(db, x.ptr, dy.data_ptr(), gw.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), s), "gs_dwconv2d_wgrad")
+            _notify(weight)
+        if bias is not None and bias.requires_grad:
+            gb = ensure_grad(bias)
+            nb = L.gs_colsum_workspace_bytes(out.rows, c)
+            wsb = _ws.get(nb, dev)
+            _lib.check(L.gs_colsum(dy.data_ptr(), out.rows, c, out.ld, gb.data_ptr(), wsb.data_ptr(),
+                                   wsb.numel(), s), "gs_colsum")
+            _notify(bias)
+        if x.requires_grad:
+            acc = _input_grad(x)
+            _lib.check(L.gs_dwconv2d_dgrad(db, dy.data_ptr(), weight.data_ptr(), x.g.data_ptr(), acc,
+                                           s), "gs_dwconv2d_dgrad")
+
+    tape.record(backward)
+    return out
+
+
 def _input_grad(x):
     """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
     x.g already held a contribution, else 0 after allocating it (a channel slice's storage is

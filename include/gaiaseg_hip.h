@@ -110,6 +110,45 @@ int gs_colsum(const float* src, int64_t rows, int32_t C, int32_t ld, float* out,
               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Depthwise 3x3 convolution (DeepLabV3+ separable convolutions)                               */
+/* ------------------------------------------------------------------------------------------ */
+/* F.conv2d(x, w[:C], bias[:C], stride 1, padding, dilation, groups = C) of a depthwise DynConv2d
+ * (mmcv DepthwiseSeparableConvModule.depthwise_conv as used by mmseg's DepthwiseSeparableASPPHead):
+ *   y[n,h,w,c] = sum_{kh,kw} x[n, h + kh*dil - pad, w + kw*dil - pad, c] * w[kh,kw,0,c]  (+ bias[c])
+ * with zero padding; Ho = H + 2*pad - 2*dil, Wo likewise.  x is NHWC with pixel stride ldx, y / dy NHWC
+ * with pixel stride ldy (a channel slice of a concat buffer is a legal source or destination).  The
+ * weight is the physical HWIO tensor with I = 1, [3][3][1][C_ld]: channel-contiguous, and only its
+ * leading C channels are read (width-dynamic like gs_conv2d_*).  fp32 throughout, whatever
+ * gs_set_forward_precision / gs_set_train_precision say.  The kernels are bandwidth-bound: one thread
+ * per float4 channel quad over a strip of pixels, the nine weight quads in registers.
+ * Supported: KH = KW = 3, stride = 1, dil >= 1, pad >= 0 with Ho, Wo >= 1 (GS_E_BADARG otherwise, also
+ * for sizes <= 0 and pitches below C); C, C_ld, ldx, ldy multiples of 4 and 16-byte aligned pointers
+ * (GS_E_ALIGN); GS_E_NULL for a missing descriptor or pointer.  The descriptor is checked first, on the
+ * host, before any launch. */
+typedef struct gs_dwconv_desc {
+  int32_t N, H, W;        /* input batch and spatial size                                    */
+  int32_t C, C_ld;        /* ACTIVE channels; channel pitch of the weight's taps (>= C)      */
+  int32_t KH, KW;         /* 3, 3                                                            */
+  int32_t stride, pad, dil;
+  int32_t ldx, ldy;       /* pixel strides of x / dx and of y / dy                           */
+} gs_dwconv_desc;
+/* bytes of scratch gs_dwconv2d_wgrad needs (0 for a descriptor it would refuse): one [9][C] partial
+ * per run of 256 output pixels; non-decreasing in N * Ho * Wo. */
+size_t gs_dwconv2d_workspace_bytes(const gs_dwconv_desc* d);
+/* bias may be NULL. */
+int gs_dwconv2d_forward(const gs_dwconv_desc* d, const float* x, const float* w, const float* bias,
+                        float* y, void* stream);
+/* dx[n,h,w,:C] (= or +=) the same stencil over dy with mirrored taps; accumulate != 0 adds to dx. */
+int gs_dwconv2d_dgrad(const gs_dwconv_desc* d, const float* dy, const float* w, float* dx,
+                      int accumulate, void* stream);
+/* dw[kh,kw,0,:C] = sum_{n,h,w} x[n, h + kh*dil - pad, w + kw*dil - pad, :C] * dy[n,h,w,:C], written into
+ * the max-size gradient tensor [3][3][1][C_ld]; channels C..C_ld-1 are never written.  Two launches:
+ * per-run partials in the workspace, then their sum in a fixed order -- no float atomics, the result
+ * is bit-identical from run to run.  GS_E_WORKSPACE when workspace_bytes is below the query. */
+int gs_dwconv2d_wgrad(const gs_dwconv_desc* d, const float* x, const float* dy, float* dw,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Dynamic BatchNorm (+ residual add, + ReLU) — K4, K8                                         */
 /* ------------------------------------------------------------------------------------------ */
 /* Replaces F.batch_norm on the leading C-slice of max-size parameters (gaiavision DynBN /
