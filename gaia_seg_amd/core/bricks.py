@@ -35,6 +35,32 @@ ACTIVATION_LAYERS = Registry("activation layer")
 ACTIVATION_LAYERS.register_module("ReLU", module=nn.ReLU)
 
 
+def _nhwc_tape_call(run, x):
+    """run(tape, act) as one autograd node on a [N, H, W, C] tensor; returns [N, H, W, C]"""
+    if x.dim() != 4:
+        raise ValueError("expected a [N, H, W, C] tensor (got %dD input)" % x.dim())
+    return tape_function(lambda tape, acts: [run(tape, acts[0])], [x.permute(0, 3, 1, 2)],
+                         True)[0].permute(0, 2, 3, 1)
+
+
+@ACTIVATION_LAYERS.register_module("GELU")
+class GELU(nn.Module):
+    """nn.GELU() (exact erf form) on the gs_gelu_* kernels.  Inside a tape: forward_act on an NHWC
+    activation; as a module it takes and returns a channels-last [N, H, W, C] tensor, the layout the
+    ConvNeXt block applies it in."""
+
+    def __init__(self, approximate="none"):
+        super().__init__()
+        if approximate != "none":
+            raise NotImplementedError("GELU: only the exact erf form is implemented")
+
+    def forward_act(self, tape, x, out=None):
+        return ops.gelu(tape, x, out=out)
+
+    def forward(self, x):
+        return _nhwc_tape_call(self.forward_act, x)
+
+
 def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
@@ -101,18 +127,18 @@ class DynamicConv2d(nn.Module, DynamicMixin):
     ``width_state`` is the active number of output channels; the active number of input channels
     is taken from the input tensor.
 
-    ``groups == in_channels == out_channels`` with a 3x3 kernel and stride 1 is the depthwise form
-    (mmcv's DepthwiseSeparableConvModule.depthwise_conv): the logical weight is [C, 1, 3, 3], both
-    active widths are the input's channel count, and it runs on the depthwise kernels
-    (ops.dwconv2d).  Every other grouping is refused."""
+    ``groups == in_channels == out_channels`` with a 3x3 or 7x7 kernel and stride 1 is the depthwise
+    form (mmcv's DepthwiseSeparableConvModule.depthwise_conv, ConvNeXt's dwconv): the logical weight is
+    [C, 1, K, K], both active widths are the input's channel count, and it runs on the depthwise
+    kernels (ops.dwconv2d).  Every other grouping is refused."""
     search_space = {"width"}
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
                  groups=1, bias=True, padding_mode="zeros"):
         super().__init__()
         kh, kw = _pair(kernel_size)
-        depthwise = (groups != 1 and groups == in_channels == out_channels and (kh, kw) == (3, 3)
-                     and _pair(stride) == (1, 1))
+        depthwise = (groups != 1 and groups == in_channels == out_channels
+                     and (kh, kw) in ((3, 3), (7, 7)) and _pair(stride) == (1, 1))
         if groups != 1 and not depthwise:
             raise NotImplementedError("DynConv2d: groups != 1 is not used on the supernet hot path")
         if padding_mode != "zeros":
@@ -206,6 +232,37 @@ class DynamicConv2d(nn.Module, DynamicMixin):
             pb[:co].copy_(b)
             self.bias = nn.Parameter(pb[:co], requires_grad=self.bias.requires_grad)
         relayout_conv_params(self)
+
+
+class DynamicLinear(DynamicConv2d):
+    """gaiavision's DynamicLinear (ConvNeXt's pwconv1 / pwconv2): ``F.linear(x, W[:width, :x.size(-1)],
+    b[:width])`` over the last dimension of a channels-last tensor.  On NHWC storage that is a 1x1
+    convolution, so it IS a 1x1 DynamicConv2d (physical weight HWIO [1][1][in][out_ld], gs_conv2d_*
+    kernels); only its state-dict weight is the 2-D [out, in] of nn.Linear, so reference checkpoints
+    load and save unchanged."""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__(in_features, out_features, 1, bias=bias)
+        self.in_features, self.out_features = in_features, out_features
+
+    def manipulate_out_channels(self, width):
+        self.manipulate_width(width)
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        destination[prefix + "weight"] = destination[prefix + "weight"][:, :, 0, 0]
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        w = state_dict.get(prefix + "weight")
+        if w is not None and w.dim() == 2:
+            if w.untyped_storage().data_ptr() == self.weight.untyped_storage().data_ptr():
+                w = w.clone()   # the module's own live state_dict: a view of the destination
+            state_dict = dict(state_dict)
+            state_dict[prefix + "weight"] = w[:, :, None, None]
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, x):
+        return _nhwc_tape_call(self.forward_act, x)
 
 
 def build_conv_layer(cfg, *args, **kwargs):
@@ -353,8 +410,61 @@ _register_norm(["SyncBN"], "world")
 _register_norm(["DynSyncBN"], "group")
 
 
+# ------------------------------------------------------------------------------------------
+# DynLN / LN
+# ------------------------------------------------------------------------------------------
+class DynamicLayerNorm(nn.LayerNorm, DynamicMixin):
+    """gaiavision's DynamicLayerNorm as ConvNeXt uses it: LayerNorm over the channels of every pixel,
+    on the leading ``C`` active channels with ``weight[:C]`` / ``bias[:C]``.
+
+    ``data_format`` says where the channels are in the tensors ``forward`` takes and returns:
+    'channels_first' [N, C, H, W] or 'channels_last' [N, H, W, C].  Activations are stored NHWC either
+    way, so both formats run the same kernel (ops.layernorm); inside a tape (``forward_act``) the format
+    plays no part at all."""
+    search_space = set()
+    _abbr_ = "ln"
+
+    def __init__(self, num_features, eps=1e-6, data_format="channels_last", elementwise_affine=True):
+        if data_format not in ("channels_last", "channels_first"):
+            raise NotImplementedError("DynLN: data_format %r" % (data_format,))
+        if not elementwise_affine:
+            raise NotImplementedError("DynLN without affine parameters is not used by ConvNeXt")
+        super().__init__(num_features, eps=eps, elementwise_affine=True)
+        self.num_features = num_features
+        self.data_format = data_format
+
+    def extra_repr(self):
+        return "%d, eps=%g, data_format=%s" % (self.num_features, self.eps, self.data_format)
+
+    def forward_act(self, tape, x, out=None):
+        if getattr(self, "_deploying", False):
+            self._deploy_slice(x.C)
+        return ops.layernorm(tape, x, self.weight, self.bias, self.eps, out=out)
+
+    def forward(self, x):
+        if self.data_format == "channels_last":
+            return _nhwc_tape_call(self.forward_act, x)
+        return tape_function(lambda tape, acts: [self.forward_act(tape, acts[0])], [x], True)[0]
+
+    def _deploy_slice(self, c):
+        if self.num_features == c:
+            return
+        self.num_features, self.normalized_shape = c, (c,)
+        self.weight = nn.Parameter(self.weight.data[:c].clone(), self.weight.requires_grad)
+        self.bias = nn.Parameter(self.bias.data[:c].clone(), self.bias.requires_grad)
+
+
+def _layernorm_factory(num_features, eps=1e-6, data_format="channels_last", **unused):
+    return DynamicLayerNorm(num_features, eps, data_format)
+
+
+for _n in ("DynLN", "LN"):
+    NORM_LAYERS.register_module(_n, module=_layernorm_factory)
+
+
 def build_norm_layer(cfg, num_features, postfix=""):
-    """mmcv.cnn.build_norm_layer: returns (name, layer); BN-family abbreviation is 'bn'."""
+    """mmcv.cnn.build_norm_layer: returns (name, layer); the abbreviation is 'bn' for the BN family and
+    'ln' for DynLN / LN."""
     if not isinstance(cfg, dict) or "type" not in cfg:
         raise KeyError('the cfg dict must contain the key "type"')
     cfg_ = dict(cfg)
@@ -367,7 +477,7 @@ def build_norm_layer(cfg, num_features, postfix=""):
     layer = factory(num_features, **cfg_)
     for p in layer.parameters():
         p.requires_grad = requires_grad
-    return "bn%s" % postfix, layer
+    return "%s%s" % (getattr(layer, "_abbr_", "bn"), postfix), layer
 
 
 def build_activation_layer(cfg):

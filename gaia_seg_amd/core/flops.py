@@ -3,7 +3,10 @@ reference's tools/count_flops.py:118-179 obtains from gaiavision's get_model_com
 
 forward FLOPs of a conv = 2 * N * Ho * Wo * Cout_act * Cin_act * kh * kw,
 Ho = floor((H + 2p - d(k-1) - 1)/s) + 1.  Only convolutions are counted (BN / ReLU / pooling are
-O(activations) and excluded)."""
+O(activations) and excluded).  For ConvNeXt a depthwise conv counts
+2 * K * K * C * Ho * Wo and a DynamicLinear counts as the 1x1 conv it is; LayerNorm, GELU and the layer
+scale count 0: the reference's counter lives in gaiavision, which is absent, so there is no count of
+theirs to reproduce, and they are O(activations) like BN / ReLU above."""
 from ..hip.ops import conv_out_size
 from .bricks import DynamicConv2d
 
@@ -20,8 +23,36 @@ def _conv(m, cin, h, w):
     return flops, params, co, ho, wo
 
 
+def convnext_backbone_flops(backbone, h, w, in_channels=3):
+    """backbone_flops for a DynamicConvNeXt: (flops per image, params, 0.0, feature shapes).  Params are
+    those of the extracted subnet: active slices, active blocks, LayerNorm affines and layer scales."""
+    total, params, c = 0.0, 0.0, in_channels
+    f, p, c, h, w = _conv(backbone.stem, c, h, w)
+    total += f
+    params += p + 2 * c                                   # + the stem LayerNorm
+    feats = []
+    for i, name in enumerate(backbone.blocks):
+        for blk in getattr(backbone, name).active_blocks():
+            fd, pd, _, _, _ = _conv(blk.dwconv, c, h, w)
+            f1, p1, c1, _, _ = _conv(blk.pwconv1, c, h, w)
+            f2, p2, _, _, _ = _conv(blk.pwconv2, c1, h, w)
+            total += fd + f1 + f2
+            params += pd + p1 + p2 + 2 * c + (c if blk.gamma is not None else 0)
+        feats.append((c, h, w))
+        if i in backbone.out_indices:
+            params += 2 * c                               # norm{i}
+        if i < 3:
+            params += 2 * c                               # the downsample layer's LayerNorm
+            f, p, c, h, w = _conv(getattr(backbone, "ds%d_conv" % (i + 1)), c, h, w)
+            total += f
+            params += p
+    return total, params, 0.0, feats
+
+
 def backbone_flops(backbone, h, w, in_channels=3):
     """(flops per image, params, flops of the 3x3 bottleneck convs, feature shapes)."""
+    if type(backbone).__name__ == "DynamicConvNeXt":
+        return convnext_backbone_flops(backbone, h, w, in_channels)
     total = params = k3 = 0.0
     c = in_channels
     if backbone.deep_stem:

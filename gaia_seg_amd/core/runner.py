@@ -60,6 +60,9 @@ class ManipulateArchHook(Hook):
 def full_arch_meta(model):
     """The supernet's largest architecture in fold_dict form ({'backbone': {'stem': .., 'body': ..}})."""
     bb = model.backbone
+    own = getattr(bb, "full_arch_meta", None)   # a backbone with another search space states its own
+    if own is not None:
+        return {"backbone": own()}
     stem = bb.stem_width
     return {"backbone": {"stem": {"width": list(stem) if isinstance(stem, (list, tuple)) else stem},
                          "body": {"width": list(bb.body_width), "depth": list(bb.body_depth)}}}

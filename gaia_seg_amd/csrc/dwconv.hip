@@ -1,5 +1,6 @@
-// Depthwise 3x3 convolution (stride 1, any dilation and padding) on NHWC fp32: forward, data gradient
-// and a two-stage weight gradient (gs_dwconv2d_* in include/gaiaseg_hip.h).
+// Depthwise 3x3 and 7x7 convolution (stride 1, any dilation and padding) on NHWC fp32: forward, data
+// gradient and a two-stage weight gradient (gs_dwconv2d_* in include/gaiaseg_hip.h).  The text below
+// describes the 3x3 kernels; the 7x7 ones (ConvNeXt) follow them further down with their own structure.
 //
 // A depthwise conv has no channel reduction: 9 multiply-adds per output element against 8 bytes moved,
 // so all three kernels are bandwidth-bound and there is nothing for the matrix cores to do.  One thread
@@ -94,6 +95,7 @@ struct DwWgrad {
   int32_t dil, pad;
   int64_t pixels;            // N * Ho * Wo
   int32_t runs;              // ceil(pixels / kWgPixels)
+  int32_t taps;              // KH * KW
 };
 
 // stage 1: grid (runs, quad groups).  part[(run * 9 + tap) * C + c]
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_partial_kernel(const DwWgrad a, 
   }
 }
 
-// stage 2: grid (quad groups, 9 taps).  Lane l sums runs l, l + 16, ... in order, then the 16 lane
+// stage 2: grid (quad groups, taps).  Lane l sums runs l, l + 16, ... in order, then the 16 lane
 // sums are added in order.
 __global__ __launch_bounds__(256) void dw_wgrad_sum_kernel(const DwWgrad a, const float* __restrict__ part,
                                                            float* __restrict__ dw) {
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(256) void dw_wgrad_sum_kernel(const DwWgrad a, cons
   const int k = blockIdx.y;
   f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
   if (cq < a.C4)
-    for (int r = pl; r < a.runs; r += kWgLanes) s += ld4(part + ((int64_t)r * 9 + k) * a.C + cq * 4);
+    for (int r = pl; r < a.runs; r += kWgLanes) s += ld4(part + ((int64_t)r * a.taps + k) * a.C + cq * 4);
   sh[pl][ql] = s;
   __syncthreads();
   if (pl == 0 && cq < a.C4) {
@@ -164,17 +166,127 @@ __global__ __launch_bounds__(256) void dw_wgrad_sum_kernel(const DwWgrad a, cons
   }
 }
 
+// ---- 7x7 ----------------------------------------------------------------------------------------
+// 49 weight quads do not fit in registers beside the accumulators, so the 7x7 stencil walks the tap
+// COLUMNS: for one kw it holds the 7 weight quads of that column and the kStrip7 + 6 input rows the
+// strip touches (one load each, reused by all 7 vertical taps), and adds 7 * kStrip7 products into the
+// strip's accumulators.  Per output quad that is (kStrip7 + 6) * 7 / kStrip7 = 12.25 input loads and
+// 6.1 weight loads, all but the first touch of a line from L1 / L2: the HBM traffic stays one read of
+// x and one write of y.  Summation order per output: kw outermost, then kh, like the 3x3 kernel.
+constexpr int kK7 = 7;
+constexpr int kStrip7 = 8;
+
+__global__ __launch_bounds__(256) void dw7_stencil_kernel(const DwStencil a, const float* __restrict__ in,
+                                                          const float* __restrict__ w,
+                                                          const float* __restrict__ bias,
+                                                          float* __restrict__ out, const int64_t items) {
+  const int dil = a.dil;
+  for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (int64_t)gridDim.x * 256) {
+    const int cq = (int)(it % a.C4);
+    int64_t r = it / a.C4;
+    const int wo = (int)(r % a.Wo);
+    r /= a.Wo;
+    const int s = (int)(r % a.strips);
+    const int n = (int)(r / a.strips);
+    const int h0 = s % dil + (s / dil) * kStrip7 * dil;
+    if (h0 >= a.Ho) continue;
+    f32x4 acc[kStrip7];
+    const f32x4 b = bias ? ld4(bias + cq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < kStrip7; ++j) acc[j] = b;
+#pragma unroll 1
+    for (int kw = 0; kw < kK7; ++kw) {
+      const int wi = wo + kw * dil - a.off;
+      if (wi < 0 || wi >= a.Wi) continue;
+      f32x4 wt[kK7];
+#pragma unroll
+      for (int kh = 0; kh < kK7; ++kh) {
+        const int k = kh * kK7 + kw;
+        wt[kh] = ld4(w + (int64_t)(a.flip ? kK7 * kK7 - 1 - k : k) * a.ldw + cq * 4);
+      }
+      const float* col = in + ((int64_t)n * a.Hi * a.Wi + wi) * a.ldi + cq * 4;
+      f32x4 win[kStrip7 + kK7 - 1];
+#pragma unroll
+      for (int j = 0; j < kStrip7 + kK7 - 1; ++j) {
+        const int hi = h0 + j * dil - a.off;
+        // row j feeds the outputs max(0, j - 6) .. j of the strip: skip it when all of them are beyond Ho
+        const bool ok = hi >= 0 && hi < a.Hi && h0 + (j > kK7 - 1 ? j - (kK7 - 1) : 0) * dil < a.Ho;
+        win[j] = ok ? ld4(col + (int64_t)hi * a.Wi * a.ldi) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int kh = 0; kh < kK7; ++kh)
+#pragma unroll
+        for (int j = 0; j < kStrip7; ++j) acc[j] += win[j + kh] * wt[kh];
+    }
+#pragma unroll
+    for (int j = 0; j < kStrip7; ++j) {
+      const int ho = h0 + j * dil;
+      if (ho >= a.Ho) break;
+      float* p = out + (((int64_t)n * a.Ho + ho) * a.Wo + wo) * a.ldo + cq * 4;
+      st4(p, a.accumulate ? ld4(p) + acc[j] : acc[j]);
+    }
+  }
+}
+
+// 7x7 stage 1: grid (runs, quad groups, 7 tap rows).  A workgroup owns ONE tap row kh of a run, so a
+// thread carries 7 accumulator quads (49 would leave two waves per SIMD); the seven workgroups of a run
+// read the same dy and overlapping rows of x, which the caches serve.  part[(run * 49 + tap) * C + c]
+__global__ __launch_bounds__(256) void dw7_wgrad_partial_kernel(const DwWgrad a, const float* __restrict__ x,
+                                                                const float* __restrict__ dy,
+                                                                float* __restrict__ part) {
+  __shared__ f32x4 sh[kK7][kWgLanes][kWgQuads];
+  const int ql = threadIdx.x % kWgQuads, pl = threadIdx.x / kWgQuads;
+  const int cq = blockIdx.y * kWgQuads + ql;
+  const int kh = blockIdx.z;
+  const int64_t p0 = (int64_t)blockIdx.x * kWgPixels;
+  f32x4 acc[kK7];
+#pragma unroll
+  for (int k = 0; k < kK7; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (cq < a.C4) {
+    for (int i = 0; i < kWgPixels / kWgLanes; ++i) {
+      const int64_t pix = p0 + i * kWgLanes + pl;
+      if (pix >= a.pixels) break;
+      const int wo = (int)(pix % a.Wo);
+      const int64_t t = pix / a.Wo;
+      const int ho = (int)(t % a.Ho);
+      const int64_t n = t / a.Ho;
+      const int hi = ho + kh * a.dil - a.pad;
+      if (hi < 0 || hi >= a.H) continue;
+      const f32x4 g = ld4(dy + pix * a.ldy + cq * 4);
+      const float* row = x + (n * a.H + hi) * a.W * a.ldx + cq * 4;
+#pragma unroll
+      for (int kw = 0; kw < kK7; ++kw) {
+        const int wi = wo + kw * a.dil - a.pad;
+        if (wi >= 0 && wi < a.W) acc[kw] += ld4(row + (int64_t)wi * a.ldx) * g;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kK7; ++k) sh[k][pl][ql] = acc[k];
+  __syncthreads();
+  if (threadIdx.x < kK7 * kWgQuads) {
+    const int k = threadIdx.x / kWgQuads;
+    if (cq < a.C4) {
+      f32x4 s = sh[k][0][ql];
+#pragma unroll
+      for (int l = 1; l < kWgLanes; ++l) s += sh[k][l][ql];
+      st4(part + ((int64_t)blockIdx.x * (kK7 * kK7) + kh * kK7 + k) * a.C + cq * 4, s);
+    }
+  }
+}
+
 // Everything a call can get wrong, checked on the host before any launch.
 int dw_check(const gs_dwconv_desc* d) {
   if (!d) return GS_E_NULL;
-  if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->dil < 1 || d->pad < 0) return GS_E_BADARG;
+  if ((d->KH != 3 && d->KH != 7) || d->KW != d->KH || d->stride != 1 || d->dil < 1 || d->pad < 0)
+    return GS_E_BADARG;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0) return GS_E_BADARG;
   if (d->C % 4 || d->C_ld % 4 || d->ldx % 4 || d->ldy % 4) return GS_E_ALIGN;
   if (d->C > d->C_ld || d->C > d->ldx || d->C > d->ldy) return GS_E_BADARG;
-  const int64_t ho = (int64_t)d->H + 2LL * d->pad - 2LL * d->dil;
-  const int64_t wo = (int64_t)d->W + 2LL * d->pad - 2LL * d->dil;
+  const int64_t ho = (int64_t)d->H + 2LL * d->pad - (d->KH - 1LL) * d->dil;
+  const int64_t wo = (int64_t)d->W + 2LL * d->pad - (d->KH - 1LL) * d->dil;
   if (ho < 1 || wo < 1 || ho > INT32_MAX || wo > INT32_MAX) return GS_E_BADARG;
-  // 2 * dil - pad (the data gradient's padding) and every coordinate o + k * dil - off stay in int32
+  // (K - 1) * dil - pad (the data gradient's padding) and every coordinate o + k * dil - off stay in int32
   if (d->dil > (1 << 24) || d->pad > (1 << 24)) return GS_E_BADARG;
   const int64_t runs = ceil_div((int64_t)d->N * ho * wo, kWgPixels);
   if (runs > INT32_MAX || ceil_div(d->C / 4, kWgQuads) > 65535) return GS_E_BADARG;
@@ -182,15 +294,19 @@ int dw_check(const gs_dwconv_desc* d) {
 }
 
 // strips of kStrip output rows `dil` apart that cover Ho rows: per residue class ceil(Ho / dil) rows
-inline int dw_strips(int ho, int dil) { return dil * (int)ceil_div(ceil_div(ho, dil), kStrip); }
+inline int dw_strips(int ho, int dil, int strip) { return dil * (int)ceil_div(ceil_div(ho, dil), strip); }
 
-inline int dw_out(const gs_dwconv_desc* d, int in) { return in + 2 * d->pad - 2 * d->dil; }
+inline int dw_out(const gs_dwconv_desc* d, int in) { return in + 2 * d->pad - (d->KH - 1) * d->dil; }
 
-int launch_stencil(const DwStencil& a, const float* in, const float* w, const float* bias, float* out,
+int launch_stencil(DwStencil a, int k, const float* in, const float* w, const float* bias, float* out,
                    void* stream) {
+  a.strips = dw_strips(a.Ho, a.dil, k == kK7 ? kStrip7 : kStrip);
   const int64_t items = (int64_t)a.N * a.strips * a.Wo * a.C4;
   const dim3 grid(stream_grid(items, 256));
-  hipLaunchKernelGGL(dw_stencil_kernel, grid, dim3(256), 0, as_stream(stream), a, in, w, bias, out, items);
+  if (k == kK7)
+    hipLaunchKernelGGL(dw7_stencil_kernel, grid, dim3(256), 0, as_stream(stream), a, in, w, bias, out, items);
+  else
+    hipLaunchKernelGGL(dw_stencil_kernel, grid, dim3(256), 0, as_stream(stream), a, in, w, bias, out, items);
   return launch_status();
 }
 
@@ -202,7 +318,7 @@ using namespace gs;
 extern "C" size_t gs_dwconv2d_workspace_bytes(const gs_dwconv_desc* d) {
   if (dw_check(d) != GS_OK) return 0;
   const int64_t runs = ceil_div((int64_t)d->N * dw_out(d, d->H) * dw_out(d, d->W), kWgPixels);
-  return (size_t)runs * 9 * d->C * sizeof(float);
+  return (size_t)runs * d->KH * d->KW * d->C * sizeof(float);
 }
 
 extern "C" int gs_dwconv2d_forward(const gs_dwconv_desc* d, const float* x, const float* w,
@@ -215,8 +331,7 @@ extern "C" int gs_dwconv2d_forward(const gs_dwconv_desc* d, const float* x, cons
   a.N = d->N; a.Hi = d->H; a.Wi = d->W; a.Ho = dw_out(d, d->H); a.Wo = dw_out(d, d->W);
   a.C4 = d->C / 4; a.ldi = d->ldx; a.ldo = d->ldy; a.ldw = d->C_ld;
   a.dil = d->dil; a.off = d->pad; a.flip = 0; a.accumulate = 0;
-  a.strips = dw_strips(a.Ho, a.dil);
-  return launch_stencil(a, x, w, bias, y, stream);
+  return launch_stencil(a, d->KH, x, w, bias, y, stream);
 }
 
 extern "C" int gs_dwconv2d_dgrad(const gs_dwconv_desc* d, const float* dy, const float* w, float* dx,
@@ -225,13 +340,12 @@ extern "C" int gs_dwconv2d_dgrad(const gs_dwconv_desc* d, const float* dy, const
   if (rc != GS_OK) return rc;
   if (!dy || !w || !dx) return GS_E_NULL;
   if (!aligned16(dy) || !aligned16(w) || !aligned16(dx)) return GS_E_ALIGN;
-  // dx[h] = sum_k dy[h + pad - k * dil] w[k] = sum_k' dy[h + k' * dil - (2 * dil - pad)] w[2 - k']
+  // dx[h] = sum_k dy[h + pad - k * dil] w[k] = sum_k' dy[h + k' * dil - ((K-1) * dil - pad)] w[K-1 - k']
   DwStencil a;
   a.N = d->N; a.Hi = dw_out(d, d->H); a.Wi = dw_out(d, d->W); a.Ho = d->H; a.Wo = d->W;
   a.C4 = d->C / 4; a.ldi = d->ldy; a.ldo = d->ldx; a.ldw = d->C_ld;
-  a.dil = d->dil; a.off = 2 * d->dil - d->pad; a.flip = 1; a.accumulate = accumulate ? 1 : 0;
-  a.strips = dw_strips(a.Ho, a.dil);
-  return launch_stencil(a, dy, w, nullptr, dx, stream);
+  a.dil = d->dil; a.off = (d->KH - 1) * d->dil - d->pad; a.flip = 1; a.accumulate = accumulate ? 1 : 0;
+  return launch_stencil(a, d->KH, dy, w, nullptr, dx, stream);
 }
 
 extern "C" int gs_dwconv2d_wgrad(const gs_dwconv_desc* d, const float* x, const float* dy, float* dw,
@@ -247,10 +361,16 @@ extern "C" int gs_dwconv2d_wgrad(const gs_dwconv_desc* d, const float* x, const 
   a.dil = d->dil; a.pad = d->pad;
   a.pixels = (int64_t)d->N * a.Ho * a.Wo;
   a.runs = (int32_t)ceil_div(a.pixels, kWgPixels);
+  a.taps = d->KH * d->KW;
   const unsigned groups = (unsigned)ceil_div(a.C4, kWgQuads);
   float* part = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(dw_wgrad_partial_kernel, dim3((unsigned)a.runs, groups), dim3(256), 0,
-                     as_stream(stream), a, x, dy, part);
-  hipLaunchKernelGGL(dw_wgrad_sum_kernel, dim3(groups, 9), dim3(256), 0, as_stream(stream), a, part, dw);
+  if (d->KH == kK7)
+    hipLaunchKernelGGL(dw7_wgrad_partial_kernel, dim3((unsigned)a.runs, groups, kK7), dim3(256), 0,
+                       as_stream(stream), a, x, dy, part);
+  else
+    hipLaunchKernelGGL(dw_wgrad_partial_kernel, dim3((unsigned)a.runs, groups), dim3(256), 0,
+                       as_stream(stream), a, x, dy, part);
+  hipLaunchKernelGGL(dw_wgrad_sum_kernel, dim3(groups, (unsigned)a.taps), dim3(256), 0, as_stream(stream), a,
+                     part, dw);
   return launch_status();
 }

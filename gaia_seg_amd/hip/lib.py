@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class HipLibraryError(RuntimeError):
@@ -73,6 +73,19 @@ def dwconv_desc(n, h, w, c, pad, dil=1, c_ld=None, ldx=None, ldy=None, k=3, stri
     d.C_ld = c if c_ld is None else c_ld
     d.KH = d.KW = k
     d.stride, d.pad, d.dil = stride, pad, dil
+    d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
+    return d
+
+
+class LayerNormDesc(Structure):
+    """Mirror of ``gs_layernorm_desc``."""
+    _fields_ = [("rows", c_int64), ("C", c_int32), ("ldx", c_int32), ("ldy", c_int32), ("eps", c_float)]
+
+
+def layernorm_desc(rows, c, eps=1e-6, ldx=None, ldy=None):
+    """A ``LayerNormDesc`` for ``rows`` pixels of ``c`` active channels; pitches default to c."""
+    d = LayerNormDesc()
+    d.rows, d.C, d.eps = rows, c, eps
     d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
     return d
 
@@ -214,6 +227,7 @@ _i32, _i64, _f32, _f64, _sz = c_int32, c_int64, c_float, c_double, c_size_t
 _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTER(KdDesc)
 _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 _DW = POINTER(DwConvDesc)
+_LN = POINTER(LayerNormDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -229,6 +243,14 @@ PROTOTYPES = {
     "gs_dwconv2d_forward": (_i32, [_DW, _P, _P, _P, _P, _P]),
     "gs_dwconv2d_dgrad": (_i32, [_DW, _P, _P, _P, _i32, _P]),
     "gs_dwconv2d_wgrad": (_i32, [_DW, _P, _P, _P, _P, _sz, _P]),
+    "gs_layernorm_forward": (_i32, [_LN, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_layernorm_workspace_bytes": (_sz, [_LN]),
+    "gs_layernorm_backward": (_i32, [_LN, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_gelu_forward": (_i32, [_P, _P, _i64, _i32, _i32, _i32, _P]),
+    "gs_gelu_backward": (_i32, [_P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P]),
+    "gs_layer_scale_add_forward": (_i32, [_P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P]),
+    "gs_layer_scale_workspace_bytes": (_sz, [_i64, _i32]),
+    "gs_layer_scale_backward": (_i32, [_P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P, _sz, _P]),
     "gs_colsum_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_colsum": (_i32, [_P, _i64, _i32, _i32, _P, _P, _sz, _P]),
     "gs_bn_stats_workspace_bytes": (_sz, [_i64, _i32]),

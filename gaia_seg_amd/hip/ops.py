@@ -711,9 +711,10 @@ def conv2d(tape, x, weight, bias, co, stride=1, pad=0, dil=1, out=None, tag=None
 
 
 def dwconv2d(tape, x, weight, pad, dil=1, out=None, bias=None):
-    """Depthwise 3x3 DynConv2d forward (stride 1): y = conv(x, weight[:x.C], groups = x.C) (+ bias[:x.C]).
+    """Depthwise 3x3 or 7x7 DynConv2d forward (stride 1): y = conv(x, weight[:x.C], groups = x.C)
+    (+ bias[:x.C]).
 
-    ``weight`` is the max-size Parameter, logical [C_max, 1, 3, 3], physical HWIO [3][3][1][C_ld]; the
+    ``weight`` is the max-size Parameter, logical [C_max, 1, K, K], physical HWIO [K][K][1][C_ld]; the
     active width is x.C.  fp32 in every precision mode (the kernels are bandwidth-bound); everything
     runs on the current stream, the weight gradient included."""
     _check_precision(tape)
@@ -721,17 +722,18 @@ def dwconv2d(tape, x, weight, pad, dil=1, out=None, bias=None):
     x = materialize(tape, x)
     c_max, ci, kh, kw = weight.shape
     c = x.C
-    if ci != 1 or (kh, kw) != (3, 3):
-        raise ValueError("dwconv2d needs a [C, 1, 3, 3] weight, got %s" % (tuple(weight.shape),))
+    if ci != 1 or (kh, kw) not in ((3, 3), (7, 7)):
+        raise ValueError("dwconv2d needs a [C, 1, 3, 3] or [C, 1, 7, 7] weight, got %s"
+                         % (tuple(weight.shape),))
     if c > c_max:
         raise ValueError("input has %d channels, conv supports at most %d" % (c, c_max))
     if c % 4:
         raise ValueError("dwconv2d needs a channel count that is a multiple of 4, got %d" % c)
     dev = x.t.device
-    ho, wo = conv_out_size(x.H, 3, 1, pad, dil), conv_out_size(x.W, 3, 1, pad, dil)
+    ho, wo = conv_out_size(x.H, kh, 1, pad, dil), conv_out_size(x.W, kw, 1, pad, dil)
     if out is None:
         out = Act.empty(x.N, ho, wo, c, dev)
-    d = _lib.dwconv_desc(x.N, x.H, x.W, c, pad, dil, c_ld=weight.stride(1), ldx=x.ld, ldy=out.ld)
+    d = _lib.dwconv_desc(x.N, x.H, x.W, c, pad, dil, c_ld=weight.stride(1), ldx=x.ld, ldy=out.ld, k=kh)
     _lib.check(L.gs_dwconv2d_forward(ctypes.byref(d), x.ptr, weight.data_ptr(),
                                      bias.data_ptr() if bias is not None else None, out.ptr,
                                      current_stream_ptr()), "gs_dwconv2d_forward")
@@ -760,6 +762,136 @@ def dwconv2d(tape, x, weight, pad, dil=1, out=None, bias=None):
             acc = _input_grad(x)
             _lib.check(L.gs_dwconv2d_dgrad(db, dy.data_ptr(), weight.data_ptr(), x.g.data_ptr(), acc,
                                            s), "gs_dwconv2d_dgrad")
+
+    tape.record(backward)
+    return out
+
+
+def _active_width(x, param, what):
+    c = x.C
+    if c > param.shape[0]:
+        raise ValueError("input has %d channels, %s supports at most %d" % (c, what, param.shape[0]))
+    if c % 4:
+        raise ValueError("%s needs a channel count that is a multiple of 4, got %d" % (what, c))
+    return c
+
+
+def _param_grad(param, c, dev):
+    """where a kernel writes the gradient of the leading ``c`` channels of ``param``: param.grad, or
+    scratch for a frozen parameter (the kernels always produce it)"""
+    if param.requires_grad:
+        return ensure_grad(param)
+    return torch.empty(c, dtype=torch.float32, device=dev)
+
+
+def layernorm(tape, x, weight, bias, eps=1e-6, out=None):
+    """DynLN forward: LayerNorm over the x.C active channels of every pixel with weight[:x.C], bias[:x.C]
+    (the reference's channels_first and channels_last forms are this one kernel on NHWC storage).
+    The per-pixel mean and 1/std are kept for the backward."""
+    L = _L()
+    x = materialize(tape, x)
+    c = _active_width(x, weight, "layernorm")
+    dev, rows = x.t.device, x.rows
+    if out is None:
+        out = Act.empty(x.N, x.H, x.W, c, dev)
+    stats = torch.empty(2 * rows, dtype=torch.float32, device=dev)
+    mean_ptr, rstd_ptr = stats.data_ptr(), stats.data_ptr() + 4 * rows
+    d = _lib.layernorm_desc(rows, c, eps, ldx=x.ld, ldy=out.ld)
+    _lib.check(L.gs_layernorm_forward(ctypes.byref(d), x.ptr, weight.data_ptr(), bias.data_ptr(), out.ptr,
+                                      mean_ptr, rstd_ptr, current_stream_ptr()), "gs_layernorm_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None:
+            return
+        keep = stats  # noqa: F841 -- the closure owns the storage behind mean_ptr / rstd_ptr
+        db = ctypes.byref(d)
+        gw, gb = _param_grad(weight, c, dev), _param_grad(bias, c, dev)
+        ws = _ws.get(L.gs_layernorm_workspace_bytes(db), dev)
+        if x.requires_grad:
+            acc = _input_grad(x)
+            dx = x.g
+        else:
+            acc, dx = 0, torch.empty_like(x.t)
+        _lib.check(L.gs_layernorm_backward(db, x.ptr, dy.data_ptr(), weight.data_ptr(), mean_ptr, rstd_ptr,
+                                           dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), acc, ws.data_ptr(),
+                                           ws.numel(), current_stream_ptr()), "gs_layernorm_backward")
+        if weight.requires_grad:
+            _notify(weight)
+        if bias.requires_grad:
+            _notify(bias)
+
+    tape.record(backward)
+    return out
+
+
+def gelu(tape, x, out=None):
+    """nn.GELU() (exact erf form).  The backward recomputes the derivative from x."""
+    L = _L()
+    x = materialize(tape, x)
+    if x.C % 4:
+        raise ValueError("gelu needs a channel count that is a multiple of 4, got %d" % x.C)
+    if out is None:
+        out = Act.empty(x.N, x.H, x.W, x.C, x.t.device)
+    _lib.check(L.gs_gelu_forward(x.ptr, out.ptr, x.rows, x.C, x.ld, out.ld, current_stream_ptr()),
+               "gs_gelu_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None or not x.requires_grad:
+            return
+        if _input_grad(x):
+            raise RuntimeError("GELU input has more than one consumer; unsupported")
+        _lib.check(L.gs_gelu_backward(x.ptr, dy.data_ptr(), x.g.data_ptr(), x.rows, x.C, x.ld, dy.stride(2),
+                                      x.g.stride(2), current_stream_ptr()), "gs_gelu_backward")
+
+    tape.record(backward)
+    return out
+
+
+def layer_scale_add(tape, identity, z, gamma, out=None):
+    """ConvNeXt's block output: identity + gamma[:C] * z, one kernel.  ``gamma`` None (no layer scale) is
+    the plain residual add.  The identity's gradient is the output's, handed on without a copy."""
+    L = _L()
+    identity, z = materialize(tape, identity), materialize(tape, z)
+    c, rows, dev = z.C, z.rows, z.t.device
+    if identity.C != c or identity.rows != rows:
+        raise ValueError("layer_scale_add: identity %s and branch %s differ" % (tuple(identity.t.shape),
+                                                                                  tuple(z.t.shape)))
+    if out is None:
+        out = Act.empty(z.N, z.H, z.W, c, dev)
+    st = current_stream_ptr()
+    if gamma is not None:
+        _active_width(z, gamma, "layer_scale_add")
+        _lib.check(L.gs_layer_scale_add_forward(identity.ptr, z.ptr, gamma.data_ptr(), out.ptr, rows, c,
+                                                identity.ld, z.ld, out.ld, st), "gs_layer_scale_add_forward")
+    else:
+        for src, acc in ((identity, 0), (z, 1)):
+            _lib.check(L.gs_copy2d(src.ptr, src.ld, out.ptr, out.ld, rows, c, 1.0, acc, st), "gs_copy2d")
+
+    def backward():
+        dout = out.g
+        if dout is None:
+            return
+        s = current_stream_ptr()
+        if gamma is None:
+            if z.requires_grad:
+                # (copied, not aliased: the identity below may alias dout and later add to it)
+                acc = _input_grad(z)
+                _lib.check(L.gs_copy2d(dout.data_ptr(), dout.stride(2), z.g.data_ptr(), z.g.stride(2), rows, c,
+                                       1.0, acc, s), "gs_copy2d")
+        else:
+            if _input_grad(z):
+                raise RuntimeError("layer-scaled branch has more than one consumer; unsupported")
+            gg = _param_grad(gamma, c, dev)
+            ws = _ws.get(L.gs_layer_scale_workspace_bytes(rows, c), dev)
+            _lib.check(L.gs_layer_scale_backward(dout.data_ptr(), z.ptr, gamma.data_ptr(), z.g.data_ptr(),
+                                                 gg.data_ptr(), rows, c, dout.stride(2), z.ld, z.g.stride(2),
+                                                 ws.data_ptr(), ws.numel(), s), "gs_layer_scale_backward")
+            if gamma.requires_grad:
+                _notify(gamma)
+        if identity.requires_grad:
+            _pass_residual_grad(L, identity, dout, rows, c, s)
 
     tape.record(backward)
     return out

@@ -1,1 +1,2 @@
 from .dynamic_resnet import DynamicResNet  # noqa: F401
+from .dynamic_convnext import DynamicConvNeXt  # noqa: F401

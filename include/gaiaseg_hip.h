@@ -110,29 +110,30 @@ int gs_colsum(const float* src, int64_t rows, int32_t C, int32_t ld, float* out,
               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
-/* Depthwise 3x3 convolution (DeepLabV3+ separable convolutions)                               */
+/* Depthwise 3x3 / 7x7 convolution (DeepLabV3+ separable convolutions, ConvNeXt blocks)        */
 /* ------------------------------------------------------------------------------------------ */
 /* F.conv2d(x, w[:C], bias[:C], stride 1, padding, dilation, groups = C) of a depthwise DynConv2d
  * (mmcv DepthwiseSeparableConvModule.depthwise_conv as used by mmseg's DepthwiseSeparableASPPHead):
  *   y[n,h,w,c] = sum_{kh,kw} x[n, h + kh*dil - pad, w + kw*dil - pad, c] * w[kh,kw,0,c]  (+ bias[c])
- * with zero padding; Ho = H + 2*pad - 2*dil, Wo likewise.  x is NHWC with pixel stride ldx, y / dy NHWC
+ * with zero padding; Ho = H + 2*pad - (KH-1)*dil, Wo likewise.  x is NHWC with pixel stride ldx, y / dy NHWC
  * with pixel stride ldy (a channel slice of a concat buffer is a legal source or destination).  The
- * weight is the physical HWIO tensor with I = 1, [3][3][1][C_ld]: channel-contiguous, and only its
+ * weight is the physical HWIO tensor with I = 1, [KH][KW][1][C_ld]: channel-contiguous, and only its
  * leading C channels are read (width-dynamic like gs_conv2d_*).  fp32 throughout, whatever
  * gs_set_forward_precision / gs_set_train_precision say.  The kernels are bandwidth-bound: one thread
- * per float4 channel quad over a strip of pixels, the nine weight quads in registers.
- * Supported: KH = KW = 3, stride = 1, dil >= 1, pad >= 0 with Ho, Wo >= 1 (GS_E_BADARG otherwise, also
+ * per float4 channel quad over a strip of pixels; the 3x3 kernel keeps its nine weight quads in
+ * registers, the 7x7 kernel (ConvNeXt's dwconv) walks the tap columns with seven at a time.
+ * Supported: KH = KW = 3 or KH = KW = 7, stride = 1, dil >= 1, pad >= 0 with Ho, Wo >= 1 (GS_E_BADARG otherwise, also
  * for sizes <= 0 and pitches below C); C, C_ld, ldx, ldy multiples of 4 and 16-byte aligned pointers
  * (GS_E_ALIGN); GS_E_NULL for a missing descriptor or pointer.  The descriptor is checked first, on the
  * host, before any launch. */
 typedef struct gs_dwconv_desc {
   int32_t N, H, W;        /* input batch and spatial size                                    */
   int32_t C, C_ld;        /* ACTIVE channels; channel pitch of the weight's taps (>= C)      */
-  int32_t KH, KW;         /* 3, 3                                                            */
+  int32_t KH, KW;         /* 3, 3 or 7, 7                                                    */
   int32_t stride, pad, dil;
   int32_t ldx, ldy;       /* pixel strides of x / dx and of y / dy                           */
 } gs_dwconv_desc;
-/* bytes of scratch gs_dwconv2d_wgrad needs (0 for a descriptor it would refuse): one [9][C] partial
+/* bytes of scratch gs_dwconv2d_wgrad needs (0 for a descriptor it would refuse): one [KH*KW][C] partial
  * per run of 256 output pixels; non-decreasing in N * Ho * Wo. */
 size_t gs_dwconv2d_workspace_bytes(const gs_dwconv_desc* d);
 /* bias may be NULL. */
@@ -142,11 +143,63 @@ int gs_dwconv2d_forward(const gs_dwconv_desc* d, const float* x, const float* w,
 int gs_dwconv2d_dgrad(const gs_dwconv_desc* d, const float* dy, const float* w, float* dx,
                       int accumulate, void* stream);
 /* dw[kh,kw,0,:C] = sum_{n,h,w} x[n, h + kh*dil - pad, w + kw*dil - pad, :C] * dy[n,h,w,:C], written into
- * the max-size gradient tensor [3][3][1][C_ld]; channels C..C_ld-1 are never written.  Two launches:
+ * the max-size gradient tensor [KH][KW][1][C_ld]; channels C..C_ld-1 are never written.  Two launches:
  * per-run partials in the workspace, then their sum in a fixed order -- no float atomics, the result
  * is bit-identical from run to run.  GS_E_WORKSPACE when workspace_bytes is below the query. */
 int gs_dwconv2d_wgrad(const gs_dwconv_desc* d, const float* x, const float* dy, float* dw,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* ConvNeXt block operators: LayerNorm over channels, GELU, layer scale + residual              */
+/* ------------------------------------------------------------------------------------------ */
+/* All on NHWC fp32 "rows x C" views: rows = N*H*W pixels, C ACTIVE channels, a pixel pitch ld >= C per
+ * operand (a channel slice of a wider buffer is a legal operand), parameters sliced to their leading C
+ * channels.  fp32 in every precision mode.  Arguments are checked on the host before any launch:
+ * GS_E_NULL (descriptor or pointer), GS_E_BADARG (rows or C <= 0, a pitch below C, eps <= 0),
+ * GS_E_ALIGN (C or a pitch no multiple of 4, a tensor pointer not 16-byte aligned), GS_E_WORKSPACE.
+ * No float atomics: every reduction has a fixed order and is bit-identical from run to run.
+ *
+ * LayerNorm (nn.LayerNorm(C) on channels_last data == the ConvNeXt channels_first LayerNorm on NCHW):
+ *   y[r,c] = (x[r,c] - mean[r]) * rstd[r] * weight[c] + bias[c],   rstd = 1 / sqrt(var + eps),
+ * var the biased variance of the row.  mean and rstd are [rows] and are saved for the backward.  Any C
+ * that is a multiple of 4 (a row is walked by up to one wave in as many steps as it needs). */
+typedef struct gs_layernorm_desc {
+  int64_t rows;           /* N*H*W                                                           */
+  int32_t C;              /* ACTIVE channels                                                 */
+  int32_t ldx, ldy;       /* pixel strides of x / dx and of y / dy                           */
+  float eps;
+} gs_layernorm_desc;
+int gs_layernorm_forward(const gs_layernorm_desc* d, const float* x, const float* weight,
+                         const float* bias, float* y, float* mean, float* rstd, void* stream);
+/* bytes of scratch gs_layernorm_backward needs (0 for a descriptor it would refuse): one [2][C] partial
+ * per run of 256 rows. */
+size_t gs_layernorm_workspace_bytes(const gs_layernorm_desc* d);
+/* dx[r,:C] (= or +=, accumulate != 0 adds) the LayerNorm data gradient; dweight[:C] = sum_r dy * xhat and
+ * dbias[:C] = sum_r dy through per-run partials in the workspace and their ordered sum.  Channels C..
+ * of dweight / dbias are never written.  dx may be dy's buffer when ldx == ldy. */
+int gs_layernorm_backward(const gs_layernorm_desc* d, const float* x, const float* dy,
+                          const float* weight, const float* mean, const float* rstd, float* dx,
+                          float* dweight, float* dbias, int accumulate, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* nn.GELU() (exact erf form): y = x * 0.5 * (1 + erf(x / sqrt 2)). */
+int gs_gelu_forward(const float* x, float* y, int64_t rows, int32_t C, int32_t ldx, int32_t ldy,
+                    void* stream);
+/* dx = dy * (Phi(x) + x * phi(x)), recomputed from the saved pre-activation x.  dx may be dy's buffer. */
+int gs_gelu_backward(const float* x, const float* dy, float* dx, int64_t rows, int32_t C, int32_t ldx,
+                     int32_t lddy, int32_t lddx, void* stream);
+/* out[r,c] = identity[r,c] + gamma[c] * z[r,c]  (ConvNeXt: x = input + gamma * branch).  out may be
+ * identity's buffer. */
+int gs_layer_scale_add_forward(const float* identity, const float* z, const float* gamma, float* out,
+                               int64_t rows, int32_t C, int32_t ldi, int32_t ldz, int32_t ldo,
+                               void* stream);
+/* one [C] partial per run of 256 rows (0 for arguments gs_layer_scale_backward would refuse). */
+size_t gs_layer_scale_workspace_bytes(int64_t rows, int32_t C);
+/* dz[r,:C] = gamma * dout and dgamma[:C] = sum_r dout * z (per-run partials, then their ordered sum);
+ * channels C.. of dgamma are never written.  The identity's gradient is dout itself.  dz may be dout's
+ * or z's buffer. */
+int gs_layer_scale_backward(const float* dout, const float* z, const float* gamma, float* dz,
+                            float* dgamma, int64_t rows, int32_t C, int32_t lddo, int32_t ldz,
+                            int32_t lddz, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Dynamic BatchNorm (+ residual add, + ReLU) — K4, K8                                         */
