@@ -120,7 +120,7 @@ def _storage_room(t):
 # ------------------------------------------------------------------------------------------
 # DynConv2d
 # ------------------------------------------------------------------------------------------
-@CONV_LAYERS.register_module(["DynConv2d", "Conv2d", "Conv"])
+@CONV_LAYERS.register_module(["DynConv2d", "ElasticConv2d", "Conv2d", "Conv"])
 class DynamicConv2d(nn.Module, DynamicMixin):
     """Conv2d over the leading slice of a max-size weight: ``F.conv2d(x, W[:width, :x.size(1)])``.
 
@@ -458,7 +458,7 @@ def _layernorm_factory(num_features, eps=1e-6, data_format="channels_last", **un
     return DynamicLayerNorm(num_features, eps, data_format)
 
 
-for _n in ("DynLN", "LN"):
+for _n in ("DynLN", "ElaLN", "LN"):
     NORM_LAYERS.register_module(_n, module=_layernorm_factory)
 
 

@@ -6,7 +6,13 @@ Ho = floor((H + 2p - d(k-1) - 1)/s) + 1.  Only convolutions are counted (BN / Re
 O(activations) and excluded).  For ConvNeXt a depthwise conv counts
 2 * K * K * C * Ho * Wo and a DynamicLinear counts as the 1x1 conv it is; LayerNorm, GELU and the layer
 scale count 0: the reference's counter lives in gaiavision, which is absent, so there is no count of
-theirs to reproduce, and they are O(activations) like BN / ReLU above."""
+theirs to reproduce, and they are O(activations) like BN / ReLU above.
+
+For the ElasticTransformer the patch embedding is a conv, every linear counts as the 1x1 conv it is on the N
+tokens of an image (cls row included), and self-attention counts 4 * N^2 * 64 * heads per layer and image:
+the two matrix products Q K^T and P V at 2 * N^2 * 64 FLOPs per head each.  The softmax (O(N^2) exponentials,
+no multiply-add pairs), LayerNorm, GELU and the residual adds count 0.  A DynamicMultiLevelNeck counts its
+1x1 and 3x3 convs at the resolutions they run at (key 'neck' of model_flops); the resizes count 0."""
 from ..hip.ops import conv_out_size
 from .bricks import DynamicConv2d
 
@@ -49,10 +55,62 @@ def convnext_backbone_flops(backbone, h, w, in_channels=3):
     return total, params, 0.0, feats
 
 
+def attention_flops(n_tokens, heads, head_dim=64):
+    """Q K^T and P V of one image: 2 products x 2 * N^2 * head_dim FLOPs per head"""
+    return 4.0 * n_tokens * n_tokens * head_dim * heads
+
+
+def vit_backbone_flops(backbone, h, w, in_channels=3):
+    """backbone_flops for an ElasticTransformer: (flops per image, params, 0.0, feature shapes).  Params are
+    those of the active subnet's used parameters: patch embedding, tokens, active layers' norms and
+    linears (not the relative-position tables or the final norm, which nothing reads)."""
+    f, p, d, hp, wp = _conv(backbone.elastic_patch_embed.projection, in_channels, h, w)
+    n = hp * wp + 1
+    total, params = f, p + d + n * d                      # + cls_token and pos_embed
+    feats = []
+    for i, name in enumerate(backbone.layers):
+        enc = getattr(backbone, name)
+        layers = enc.active_layers()
+        for layer in layers:
+            heads = layer.attn.num_heads
+            hw, hidden = 64 * heads, layer.mlp.layer1.width_state
+            for cin, cout, count in ((d, hw, 3), (hw, d, 1), (d, hidden, 1), (hidden, d, 1)):
+                total += count * 2.0 * n * cin * cout
+                params += count * (cin * cout + cout)
+            total += attention_flops(n, heads)
+            params += 4 * d                               # ln1, ln2
+        if i in backbone.out_stages:
+            extra = backbone.out_indices[i]
+            n_out = 1 if extra is None else 1 + sum(1 for j in extra if j < len(layers))
+            feats.extend([(d, hp, wp)] * n_out)
+    return total, params, 0.0, feats
+
+
+def neck_flops(neck, feats):
+    """DynamicMultiLevelNeck: (flops per image, feature shapes after the neck)"""
+    from ..models.necks.dynamic_multilevel_neck import scaled_size
+    total, laterals = 0.0, []
+    for (c, h, w), lat in zip(feats, neck.lateral_convs):
+        f, _, co, _, _ = _conv(lat.conv, c, h, w)
+        total += f
+        laterals.append((co, h, w))
+    if len(laterals) == 1:
+        laterals = laterals * neck.num_outs
+    out = []
+    for (c, h, w), scale, conv in zip(laterals, neck.scales, neck.convs):
+        h, w = scaled_size(h, scale), scaled_size(w, scale)
+        f, _, co, _, _ = _conv(conv.conv, c, h, w)
+        total += f
+        out.append((co, h, w))
+    return total, out
+
+
 def backbone_flops(backbone, h, w, in_channels=3):
     """(flops per image, params, flops of the 3x3 bottleneck convs, feature shapes)."""
     if type(backbone).__name__ == "DynamicConvNeXt":
         return convnext_backbone_flops(backbone, h, w, in_channels)
+    if type(backbone).__name__ == "ElasticTransformer":
+        return vit_backbone_flops(backbone, h, w, in_channels)
     total = params = k3 = 0.0
     c = in_channels
     if backbone.deep_stem:
@@ -167,9 +225,11 @@ def uper_head_flops(head, feats):
 
 
 def model_flops(model, h, w):
-    """dict(backbone, backbone_3x3, decode, aux, total) in FLOPs per image for the current arch."""
+    """dict(backbone, backbone_3x3, [neck,] decode, aux, total) in FLOPs per image for the current arch."""
     b, params, k3, feats = backbone_flops(model.backbone, h, w)
     out = dict(backbone=b, backbone_3x3=k3, backbone_params=params)
+    if getattr(model, "neck", None) is not None:
+        out["neck"], feats = neck_flops(model.neck, feats)
     for key, head in (("decode", model.decode_head), ("aux", getattr(model, "auxiliary_head", None))):
         if head is None:
             continue
@@ -186,5 +246,5 @@ def model_flops(model, h, w):
             out[key] = aspp_head_flops(head, feats)
         else:
             out[key] = float("nan")
-    out["total"] = sum(v for k, v in out.items() if k in ("backbone", "decode", "aux") and v == v)
+    out["total"] = sum(v for k, v in out.items() if k in ("backbone", "neck", "decode", "aux") and v == v)
     return out

@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 class HipLibraryError(RuntimeError):
@@ -87,6 +87,28 @@ def layernorm_desc(rows, c, eps=1e-6, ldx=None, ldy=None):
     d = LayerNormDesc()
     d.rows, d.C, d.eps = rows, c, eps
     d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
+    return d
+
+
+class AttentionDesc(Structure):
+    """Mirror of ``gs_attention_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("B", "N", "heads", "ldq", "ldk", "ldv", "ldo", "lddq", "lddk", "lddv",
+                                        "lddo")] + [("scale", c_float)])
+
+
+ATTENTION_HEAD_DIM = 64
+
+
+def attention_desc(b, n, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=None, ldk=None, ldv=None, ldo=None,
+                   lddq=None, lddk=None, lddv=None, lddo=None):
+    """An ``AttentionDesc`` for ``b`` images of ``n`` tokens and ``heads`` active heads; a forward pitch
+    defaults to 64 * heads, a gradient's pitch to the pitch of its forward operand."""
+    d = AttentionDesc()
+    d.B, d.N, d.heads, d.scale = b, n, heads, scale
+    c = ATTENTION_HEAD_DIM * heads
+    d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
+    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
+                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
     return d
 
 
@@ -228,6 +250,7 @@ _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTE
 _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 _DW = POINTER(DwConvDesc)
 _LN = POINTER(LayerNormDesc)
+_AT = POINTER(AttentionDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -251,6 +274,11 @@ PROTOTYPES = {
     "gs_layer_scale_add_forward": (_i32, [_P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P]),
     "gs_layer_scale_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_layer_scale_backward": (_i32, [_P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P, _sz, _P]),
+    "gs_attention_forward": (_i32, [_AT, _P, _P, _P, _P, _P, _P]),
+    "gs_attention_workspace_bytes": (_sz, [_AT]),
+    "gs_attention_backward": (_i32, [_AT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_vit_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _P]),
+    "gs_vit_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_colsum_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_colsum": (_i32, [_P, _i64, _i32, _i32, _P, _P, _sz, _P]),
     "gs_bn_stats_workspace_bytes": (_sz, [_i64, _i32]),

@@ -897,6 +897,120 @@ def layer_scale_add(tape, identity, z, gamma, out=None):
     return out
 
 
+def attention(tape, q, k, v, heads, scale, out=None):
+    """Multi-head softmax self-attention, head dimension 64: ``heads`` active heads in the leading
+    64 * heads columns of q, k and v (token activations [B, 1, N, 64 * heads], each with its own pitch: three
+    column slices of one buffer are fine).  No N x N matrix is stored; the log-sum-exp of every query row is
+    kept for the backward, which recomputes the probabilities."""
+    L = _L()
+    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
+    c = _lib.ATTENTION_HEAD_DIM * heads
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.C != c or t.rows != q.rows or t.H != 1:
+            raise ValueError("attention: %s is %s, expected [B, 1, N, %d] for %d heads"
+                             % (name, tuple(t.t.shape), c, heads))
+    b, n, dev = q.N, q.W, q.t.device
+    if out is None:
+        out = Act.empty(b, 1, n, c, dev)
+    lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
+    d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    _lib.check(L.gs_attention_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(),
+                                      current_stream_ptr()), "gs_attention_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad):
+            return
+        accs = [_input_grad(t) for t in (q, k, v)]
+        if any(accs) and not all(accs):   # one flag for the three: start the fresh ones from zero
+            for t, acc in zip((q, k, v), accs):
+                if not acc:
+                    t.g.zero_()
+        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        db = ctypes.byref(d)
+        ws = _ws.get(L.gs_attention_workspace_bytes(db), dev)
+        _lib.check(L.gs_attention_backward(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(),
+                                           q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(), 1 if any(accs) else 0,
+                                           ws.data_ptr(), ws.numel(), current_stream_ptr()),
+                   "gs_attention_backward")
+
+    tape.record(backward)
+    return out
+
+
+def vit_tokens(tape, patches, cls_token, pos_embed):
+    """ElasticTransformer's token assembly: from the patch embedding [B, Hp, Wp, D] and the max-size
+    ``cls_token`` [1, 1, D_max] / ``pos_embed`` [1, N_max, D_max] Parameters, the token activation
+    [B, 1, 1 + Hp*Wp, D] with x[b, 0] = cls + pos[0] and x[b, 1 + t] = patch[b, t] + pos[1 + t], on the
+    leading D columns and 1 + Hp*Wp rows of the parameters."""
+    L = _L()
+    patches = materialize(tape, patches)
+    b, t, dch, dev = patches.N, patches.H * patches.W, patches.C, patches.t.device
+    if dch % 4:
+        raise ValueError("vit_tokens needs an embedding width that is a multiple of 4, got %d" % dch)
+    if dch > cls_token.shape[-1] or dch > pos_embed.shape[-1] or t + 1 > pos_embed.shape[1]:
+        raise ValueError("vit_tokens: %d tokens of width %d exceed pos_embed %s"
+                         % (t + 1, dch, tuple(pos_embed.shape)))
+    ldpos = pos_embed.stride(1)
+    out = Act.empty(b, 1, t + 1, dch, dev)
+    _lib.check(L.gs_vit_tokens_forward(patches.ptr, patches.ld, cls_token.data_ptr(), pos_embed.data_ptr(),
+                                       ldpos, out.ptr, out.ld, b, t, dch, current_stream_ptr()),
+               "gs_vit_tokens_forward")
+
+    def backward():
+        dx = out.g
+        if dx is None:
+            return
+        gc = _param_grad(cls_token, dch, dev)
+        gp = ensure_grad(pos_embed) if pos_embed.requires_grad else torch.empty_like(pos_embed)
+        if patches.requires_grad:
+            if _input_grad(patches):
+                raise RuntimeError("patch embedding has more than one consumer; unsupported")
+            dp = patches.g
+        else:
+            dp = torch.empty_like(patches.t)
+        _lib.check(L.gs_vit_tokens_backward(dx.data_ptr(), dx.stride(2), dp.data_ptr(), dp.stride(2),
+                                            gc.data_ptr(), gp.data_ptr(), ldpos, b, t, dch,
+                                            current_stream_ptr()), "gs_vit_tokens_backward")
+        if cls_token.requires_grad:
+            _notify(cls_token)
+        if pos_embed.requires_grad:
+            _notify(pos_embed)
+
+    tape.record(backward)
+    return out
+
+
+def vit_feature_map(tape, x, hp, wp):
+    """The tokens [B, 1, 1 + hp*wp, D] without their cls row as an NHWC feature map [B, hp, wp, D].  An
+    activation cannot express the per-image row offset, so the rows are copied (one gs_copy2d per image)."""
+    L = _L()
+    b, n, c, dev = x.N, x.W, x.C, x.t.device
+    if n != 1 + hp * wp:
+        raise ValueError("vit_feature_map: %d tokens are not 1 + %d x %d" % (n, hp, wp))
+    out = Act.empty(b, hp, wp, c, dev)
+    st = current_stream_ptr()
+    for i in range(b):
+        _lib.check(L.gs_copy2d(x.ptr + 4 * (i * n + 1) * x.ld, x.ld, out.ptr + 4 * i * (n - 1) * out.ld, out.ld,
+                               n - 1, c, 1.0, 0, st), "gs_copy2d")
+
+    def backward():
+        dy = out.g
+        if dy is None or not x.requires_grad:
+            return
+        acc = _input_grad(x)
+        if not acc:
+            x.g.zero_()   # the cls rows receive nothing from this edge
+        s = current_stream_ptr()
+        g, ldg = x.g, x.g.stride(2)
+        for i in range(b):
+            _lib.check(L.gs_copy2d(dy.data_ptr() + 4 * i * (n - 1) * dy.stride(2), dy.stride(2),
+                                   g.data_ptr() + 4 * (i * n + 1) * ldg, ldg, n - 1, c, 1.0, 1, s), "gs_copy2d")
+
+    tape.record(backward)
+    return out
+
+
 def _input_grad(x):
     """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
     x.g already held a contribution, else 0 after allocating it (a channel slice's storage is

@@ -1,2 +1,3 @@
 from .dynamic_resnet import DynamicResNet  # noqa: F401
 from .dynamic_convnext import DynamicConvNeXt  # noqa: F401
+from .elastic_transformer import ElasticTransformer  # noqa: F401

@@ -202,6 +202,49 @@ int gs_layer_scale_backward(const float* dout, const float* z, const float* gamm
                             int32_t lddz, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Multi-head softmax self-attention (head dimension 64) and the ViT token assembly             */
+/* ------------------------------------------------------------------------------------------ */
+/* ElasticMHA.forward with relative_position=False (gaiaseg/models/backbones/elastic_transformer.py):
+ *   O[b,i,h,:] = sum_j softmax_j(scale * <Q[b,i,h,:], K[b,j,h,:]>) V[b,j,h,:],   no mask, no dropout.
+ * Q, K, V, O and their gradients are fp32 "rows x C" views as above: rows = B*N tokens, head h in columns
+ * [64 h, 64 h + 64), one pitch >= 64 * heads per operand; a column slice of a wider buffer is a legal
+ * operand (Q, K, V as three slices of one buffer).  `heads` is the ACTIVE head count.  fp32-accurate in
+ * every precision mode (exact fp32 MFMA); no N x N matrix is stored (online softmax over key tiles of 32
+ * rows; a workgroup owns 128 query rows).  lse[b,h,i] = log sum_j exp(scale * <q_i, k_j>) is [B][heads][N]
+ * and is saved for the backward.  No float atomics; bit-identical from run to run.
+ * Checked on the host before any launch: GS_E_NULL (descriptor or pointer), GS_E_BADARG (B, N or heads
+ * <= 0, B or heads > 65535, a pitch below 64 * heads, scale <= 0), GS_E_ALIGN (a pitch no multiple of 4, a
+ * pointer not 16-byte aligned), GS_E_WORKSPACE.  Nothing outside the active columns of O / dQ / dK / dV
+ * is written. */
+typedef struct gs_attention_desc {
+  int32_t B, N, heads;              /* batch, tokens per image, ACTIVE heads                     */
+  int32_t ldq, ldk, ldv, ldo;       /* token pitches of Q, K, V, O                               */
+  int32_t lddq, lddk, lddv, lddo;   /* token pitches of dQ, dK, dV, dO (all eight are checked)   */
+  float scale;                      /* 64^-0.5 in ElasticMHA                                     */
+} gs_attention_desc;
+int gs_attention_forward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+                         float* o, float* lse, void* stream);
+/* bytes of scratch gs_attention_backward needs (0 for a descriptor it would refuse): delta[B][heads][N]. */
+size_t gs_attention_workspace_bytes(const gs_attention_desc* d);
+/* dQ, dK, dV (each = or +=, accumulate != 0 adds) from Q, K, V, O, lse and dO.  P is recomputed from Q, K
+ * and lse; delta = <dO, O> goes through the workspace.  Two kernels: one workgroup per 128 keys owns dK /
+ * dV and sweeps the queries, one per 128 queries owns dQ and sweeps the keys. */
+int gs_attention_backward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+                          const float* o, const float* lse, const float* d_o, float* dq, float* dk,
+                          float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* ElasticTransformer's token assembly on the leading D columns: from patches [B*T][D] (pitch ldp),
+ * cls_token[:D] and pos_embed[:T+1, :D] (pitch ldpos, the max-size embedding width),
+ *   x[b,0,:] = cls_token + pos_embed[0],   x[b,1+t,:] = patches[b,t] + pos_embed[1+t]      (x: [B*(T+1)][D]).
+ * GS_E_BADARG for B, T or D <= 0 or a pitch below D, GS_E_ALIGN for D or a pitch no multiple of 4 or a
+ * pointer not 16-byte aligned, GS_E_NULL. */
+int gs_vit_tokens_forward(const float* patches, int32_t ldp, const float* cls_token, const float* pos_embed,
+                          int32_t ldpos, float* x, int32_t ldx, int32_t B, int32_t T, int32_t D, void* stream);
+/* dpatches[b,t,:D] = dx[b,1+t]; dpos_embed[n,:D] = sum_b dx[b,n] and dcls_token[:D] = sum_b dx[b,0], summed
+ * in the order of b.  Columns D.. and rows T+1.. are never written. */
+int gs_vit_tokens_backward(const float* dx, int32_t lddx, float* dpatches, int32_t lddp, float* dcls_token,
+                           float* dpos_embed, int32_t ldpos, int32_t B, int32_t T, int32_t D, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Dynamic BatchNorm (+ residual add, + ReLU) — K4, K8                                         */
 /* ------------------------------------------------------------------------------------------ */
 /* Replaces F.batch_norm on the leading C-slice of max-size parameters (gaiavision DynBN /

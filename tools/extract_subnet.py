@@ -46,13 +46,16 @@ def meta_hash(meta):
 
 
 def extract(model, meta, input_size=64):
-    """One pruned copy of ``model`` (already in deploy mode) for ``meta``."""
+    """One pruned copy of ``model`` (already in deploy mode) for ``meta``.  A backbone with a fixed
+    ``img_size`` (ElasticTransformer) gets its dummy input at that size."""
     model.manipulate_arch(fold_dict(meta)["arch"])
     sub = copy.deepcopy(model)
     sub.deploy()
     dev = next(sub.parameters()).device
+    size = getattr(sub.backbone, "img_size", input_size)
+    h, w = (size, size) if isinstance(size, int) else size
     with torch.no_grad():
-        sub.forward_dummy(torch.zeros(1, 3, input_size, input_size, device=dev))
+        sub.forward_dummy(torch.zeros(1, 3, h, w, device=dev))
     sub.deploy(False)
     return sub
 
