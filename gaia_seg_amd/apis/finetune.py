@@ -94,7 +94,7 @@ class SupernetSnapshot:
             a.flat_param.copy_(self.flat_param)
             for b, saved in self.buffers:
                 b.copy_(saved)
-            a.flat_mom.zero_()
+            a.reset_optimizer_state()    # (momentum; AdamW: both moments and the step counters)
             a.flat_grad.zero_()
             if a.flat_acc is not None:
                 a.flat_acc.zero_()

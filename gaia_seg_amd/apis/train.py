@@ -6,8 +6,8 @@ lr_scaler :103-113, resume_from / load_from :172-175).  What differs by design:
   * the model is not wrapped in MMDistributedDataParallel: parameters and gradients live in flat
     arenas and a bucketed RCCL all-reduce over slices of the gradient arena is driven by the
     backward tape (core/dist.py);
-  * the optimizer is the fused flat-arena SGD kernel (cfg.optimizer must be SGD, as in the
-    in-tree config);
+  * the optimizer is a fused flat-arena kernel: SGD (the in-tree ResNet configs) or AdamW
+    (cfg.optimizer.type, core/optimizer.py; anything else is refused);
   * datasets: the reference's CityscapesDataset19 is not defined anywhere and
     no dataset exists offline, so ``type='SyntheticSegDataset'`` (seeded tensors of the pipeline's
     output shapes) is the built-in loader; any iterable of
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ..core import dist as gdist
-from ..core.optimizer import build_param_groups
+from ..core.optimizer import build_param_groups, check_optimizer_cfg
 from ..core.param_arena import ParamArena
 from ..core.runner import (ArenaOptimizerHook, CheckpointHook, FixedLrUpdaterHook,
                            Fp16ArenaOptimizerHook, IterBasedRunner, ManipulateArchHook,
@@ -162,6 +162,9 @@ def prepare_training(model, cfg):
                                 bucket_bytes=cfg.get("bucket_bytes", 64 << 20))
     # optimizer keys the arena SGD does not implement are errors, and paramwise_cfg becomes parameter
     # groups (core/optimizer.py; None = the one-group path)
+    opt = check_optimizer_cfg(cfg.optimizer)
+    if opt.get("type", "SGD") == "AdamW":    # second moment + per-parameter counters, per-parameter tables
+        arena.set_optimizer("AdamW", opt["betas"], opt["eps"])
     param_groups = build_param_groups(model, cfg.optimizer)
     return model, arena, reducer, param_groups
 
@@ -179,7 +182,7 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
     ``runner.run``."""
     device = arena.device
     apply_input_shape = check_input_shape_cfg(cfg)
-    opt = dict(cfg.optimizer)
+    opt = check_optimizer_cfg(cfg.optimizer)      # (AdamW: torch's defaults filled in)
     lr = opt["lr"]
     lr_scaler = cfg.get("lr_scaler")      # gaiaseg/apis/train.py:103-113
     if lr_scaler is not None:

@@ -2,8 +2,9 @@
 whose state_dict holds the MAX-size parameters as contiguous OIHW tensors under the reference's
 module names (tools/train_supernet.py:197-202; gaiaseg/apis/train.py:172-175;
 gaiaseg/models/backbones/dynamic_resnet.py:343-345).  The HWIO physical
-layout of this implementation never leaks into a file: `optimizer` holds the SGD momentum per
-parameter NAME in the same logical layout (ParamArena.state_dict)."""
+layout of this implementation never leaks into a file: `optimizer` holds the SGD momentum (or
+AdamW's step count and two moments) per parameter NAME in the same logical layout
+(ParamArena.state_dict)."""
 import os
 
 import torch

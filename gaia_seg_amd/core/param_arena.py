@@ -1,4 +1,5 @@
-"""Flat fp32 arenas for parameters, gradients and SGD momentum (laid out for 288 GB of HBM3E).
+"""Flat fp32 arenas for parameters, gradients and optimizer state -- SGD momentum, or AdamW's two moments and
+per-parameter step counters (laid out for 288 GB of HBM3E).
 
 Every parameter of the supernet becomes a view into ONE contiguous buffer (and its gradient a view
 into a second one with identical offsets), in forward order.  This gives
@@ -82,6 +83,45 @@ class ParamArena:
         # while a list: every device tensor a gs_sgd_step_groups launch names is appended (the runner
         # sets it around a graph capture and keeps the list with the graph)
         self.capture_refs = None
+        # the optimizer kind (set_optimizer): 'SGD' keeps flat_mom alone; 'AdamW' adds the second
+        # moment, one int32 step counter per parameter and an fp64 hyper table
+        self.optimizer = "SGD"
+        self.flat_var = None          # AdamW exp_avg_sq (flat_mom is its exp_avg)
+        self.steps = None             # AdamW: int32 [number of parameters], torch's state['step']
+        self.betas, self.eps = None, None
+        self.adamw_hyper = None       # device doubles, GS_ADAMW_HYPER_DOUBLES (gaiaseg_hip.h)
+        self._adamw_hyper_vals = None
+        self._group_of_param, self._chunk_floats = None, None
+
+    # ---- optimizer kind ----
+    def set_optimizer(self, kind, betas=(0.9, 0.999), eps=1e-8):
+        """'SGD' (the state the arena is built in) or 'AdamW': allocates ``flat_var`` and ``steps``
+        (zero) and from here on the chunk tables are per parameter (every chunk carries its
+        parameter's slot in ``steps``).  An SGD arena allocates nothing for AdamW."""
+        if kind not in ("SGD", "AdamW"):
+            raise NotImplementedError("optimizer %r: only SGD and AdamW" % (kind,))
+        if kind == "AdamW":
+            b1, b2 = (float(b) for b in betas)
+            if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or not float(eps) > 0.0:
+                raise ValueError("AdamW needs betas in [0, 1) and eps > 0, got %r, %r" % (betas, eps))
+            self.betas, self.eps = (b1, b2), float(eps)
+            if self.flat_var is None:
+                self.flat_var = torch.zeros_like(self.flat_mom)
+                self.steps = torch.zeros(len(self._layout), dtype=torch.int32, device=self.device)
+        else:
+            self.flat_var = self.steps = self.betas = self.eps = None
+        changed, self.optimizer = kind != self.optimizer, kind
+        self._adamw_hyper_vals = None
+        if changed and self._group_of_param is not None:      # tables of the other mode are void
+            self.set_param_groups(self._group_of_param, self.groups, self._chunk_floats)
+
+    def reset_optimizer_state(self):
+        """Momentum / first moment, second moment and step counters back to zero."""
+        with torch.no_grad():
+            self.flat_mom.zero_()
+            if self.flat_var is not None:
+                self.flat_var.zero_()
+                self.steps.zero_()
 
     # ---- parameter groups (paramwise_cfg, core/optimizer.py) ----
     def set_param_groups(self, group_of_param, n_groups=1, chunk_floats=None):
@@ -94,6 +134,8 @@ class ParamArena:
         self.group_epoch += 1
         self._group_hyper_vals = None
         self._tables = None
+        self._adamw_hyper_vals = None
+        self._group_of_param, self._chunk_floats = group_of_param, chunk_floats
         if group_of_param is None:
             self.groups = None
             return
@@ -106,10 +148,14 @@ class ParamArena:
             raise ValueError("set_param_groups: group index outside [0, %d)" % n_groups)
         self.groups = n_groups
         self._tables = _opt.ChunkTableCache(
-            _opt.segment_groups(self._layout, group_of_param, _ALIGN), chunk_floats or _opt.CHUNK_FLOATS,
-            upload=lambda tab: torch.from_numpy(tab).to(self.device), numel=self.numel)
+            _opt.segment_groups(self._layout, group_of_param, _ALIGN, per_param=self.optimizer == "AdamW"),
+            chunk_floats or _opt.CHUNK_FLOATS,
+            upload=lambda tab: torch.from_numpy(tab).to(self.device), numel=self.numel,
+            n_slots=len(self._layout))
         # a fresh table per grouping: a graph of an earlier grouping keeps (and reads) its own
         self.group_hyper = torch.zeros(4 + 2 * _lib.SGD_MAX_GROUPS, dtype=torch.float32, device=self.device)
+        if self.optimizer == "AdamW":
+            self.adamw_hyper = torch.zeros(_lib.ADAMW_HYPER_DOUBLES, dtype=torch.float64, device=self.device)
 
     def chunk_table(self, ranges):
         """(device table, chunks, fragments) of ``ranges`` under the current grouping, built once per
@@ -138,6 +184,25 @@ class ParamArena:
                                                       self.groups, g, current_stream_ptr()),
                    "gs_sgd_set_group_hyper")
         self._group_hyper_vals = vals
+
+    def write_adamw_hyper(self, lrs, weight_decays, grad_scale):
+        """{betas, eps, grad_scale, n_groups, per-group lr / wd} -> the fp64 device table in stream
+        order (one tiny launch; skipped while the table already holds exactly these values).  The
+        values stay Python doubles all the way into the kernel's arguments."""
+        vals = (tuple(float(x) for x in lrs), tuple(float(x) for x in weight_decays), float(grad_scale))
+        if len(vals[0]) != self.groups or len(vals[1]) != self.groups:
+            raise ValueError("%d parameter groups need %d learning rates and weight decays, got %d / %d"
+                             % (self.groups, self.groups, len(vals[0]), len(vals[1])))
+        if vals == self._adamw_hyper_vals:
+            return
+        g = _lib.AdamwGroups()
+        for i, (lr, wd) in enumerate(zip(vals[0], vals[1])):
+            g.lr_wd[2 * i], g.lr_wd[2 * i + 1] = lr, wd
+        _lib.check(_lib.load().gs_adamw_set_group_hyper(self.adamw_hyper.data_ptr(), self.betas[0],
+                                                        self.betas[1], self.eps, vals[2], self.groups,
+                                                        g, current_stream_ptr()),
+                   "gs_adamw_set_group_hyper")
+        self._adamw_hyper_vals = vals
 
     @staticmethod
     def _view(flat, p, phys, off, n):
@@ -219,6 +284,31 @@ class ParamArena:
                                      weight_decay, grad_scale, 1 if zero_grad else 0, st),
                        "gs_sgd_step")
 
+    def adamw_step(self, ranges, lr, weight_decay, grad_scale=1.0, zero_grad=False, hyper=None):
+        """torch.optim.AdamW(betas, eps, amsgrad=False) on the ranges: ONE gs_adamw_step_groups call
+        over the per-parameter chunk table of ``ranges`` (the step kernel, then the launch that
+        advances the counters of the parameters it stepped).  ``lr`` / ``weight_decay``: one value
+        per parameter group.  A non-None ``hyper`` means the caller has written the hyper table
+        itself (write_adamw_hyper, outside a captured graph)."""
+        if self.optimizer != "AdamW":
+            raise RuntimeError("adamw_step on an arena in %s mode (set_optimizer('AdamW', ...))" % self.optimizer)
+        if self.groups is None:
+            raise RuntimeError("adamw_step needs parameter groups (set_param_groups; one group is fine)")
+        table, n_chunks, _ = self.chunk_table(ranges)
+        if n_chunks == 0:
+            return
+        if hyper is None:
+            self.write_adamw_hyper(lr, weight_decay, grad_scale)
+        elif self._adamw_hyper_vals is None:
+            raise RuntimeError("adamw_step(hyper=...) before write_adamw_hyper")
+        if self.capture_refs is not None:
+            self.capture_refs += [table, self.adamw_hyper]
+        _lib.check(_lib.load().gs_adamw_step_groups(
+            self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.flat_mom.data_ptr(),
+            self.flat_var.data_ptr(), self.steps.data_ptr(), self.steps.numel(), table.data_ptr(),
+            n_chunks, self.adamw_hyper.data_ptr(), 1 if zero_grad else 0, current_stream_ptr()),
+            "gs_adamw_step_groups")
+
     def accumulate(self, ranges, into="buffer"):
         """Move gradients between the gradient arena and the accumulation buffer over ``ranges``
         (one gs_grad_accumulate launch per merged range):
@@ -241,18 +331,63 @@ class ParamArena:
         """{parameter name: momentum buffer as a LOGICAL (OIHW / plain) view of the flat arena}."""
         return {name: self._view(self.flat_mom, p, phys, o, n) for name, p, phys, o, n in self._layout}
 
+    def variance_views(self):
+        """{parameter name: exp_avg_sq as a LOGICAL view of the flat arena} (AdamW mode)."""
+        return {name: self._view(self.flat_var, p, phys, o, n) for name, p, phys, o, n in self._layout}
+
+    SGD_FORMAT, ADAMW_FORMAT = "gaia_seg_amd.sgd_momentum.v1", "gaia_seg_amd.adamw.v1"
+
     def state_dict(self):
         """Optimizer state keyed by parameter name in the logical layout (contiguous OIHW for conv
         weights), so that neither the arena offsets nor the physical HWIO layout leak into a
-        checkpoint (tools/train_supernet.py:197-202 stores `optimizer` next to `state_dict`)."""
-        return {"format": "gaia_seg_amd.sgd_momentum.v1",
+        checkpoint (tools/train_supernet.py:197-202 stores `optimizer` next to `state_dict`).
+        AdamW mode: per name {step, exp_avg, exp_avg_sq}, with the betas and eps alongside."""
+        if self.optimizer == "AdamW":
+            steps = self.steps.cpu().tolist()
+            mom, var = self.momentum_views(), self.variance_views()
+            return {"format": self.ADAMW_FORMAT, "betas": tuple(self.betas), "eps": self.eps,
+                    "state": {name: {"step": int(steps[i]),
+                                     "exp_avg": mom[name].detach().clone().contiguous(),
+                                     "exp_avg_sq": var[name].detach().clone().contiguous()}
+                              for i, (name, *_r) in enumerate(self._layout)}}
+        return {"format": self.SGD_FORMAT,
                 "state": {k: v.detach().clone().contiguous() for k, v in self.momentum_views().items()}}
+
+    def _load_adamw_state(self, sd, warn):
+        state = sd.get("state") if isinstance(sd, dict) else None
+        if not isinstance(sd, dict) or sd.get("format") != self.ADAMW_FORMAT or not isinstance(state, dict):
+            warn("optimizer state of a foreign format (not %s): AdamW moments and step counters "
+                 "restart from zero" % self.ADAMW_FORMAT)
+            self.reset_optimizer_state()
+            return False
+        self.reset_optimizer_state()
+        mom, var = self.momentum_views(), self.variance_views()
+        steps = self.steps.cpu()
+        missing = [k for k in mom if k not in state]
+        with torch.no_grad():
+            for i, (name, *_r) in enumerate(self._layout):
+                ent = state.get(name)
+                if ent is None:
+                    continue
+                for key, views in (("exp_avg", mom), ("exp_avg_sq", var)):
+                    if tuple(views[name].shape) != tuple(ent[key].shape):
+                        raise RuntimeError("%s of %s: checkpoint %s vs model %s"
+                                           % (key, name, tuple(ent[key].shape), tuple(views[name].shape)))
+                    views[name].copy_(ent[key])
+                steps[i] = int(ent["step"])
+            self.steps.copy_(steps)
+        if missing:
+            warn("optimizer state lacks %d parameters (e.g. %s): their AdamW state is zero"
+                 % (len(missing), missing[0]))
+        return True
 
     def load_state_dict(self, sd, logger=None):
         """Accepts this build's format; any other optimizer state (e.g. a torch.optim.SGD state_dict
         of an mmcv checkpoint, whose integer keys carry no parameter names) is skipped with a warning
         and the momentum restarts from zero."""
         import warnings
+        if self.optimizer == "AdamW":
+            return self._load_adamw_state(sd, logger.warning if logger is not None else warnings.warn)
         state = sd.get("state") if isinstance(sd, dict) else None
         if not isinstance(sd, dict) or sd.get("format") != "gaia_seg_amd.sgd_momentum.v1" \
                 or not isinstance(state, dict):

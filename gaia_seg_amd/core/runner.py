@@ -397,6 +397,13 @@ class IterBasedRunner:
         # group_lr follows the schedule (LrUpdaterHook), group_wd is fixed here
         self.param_groups = param_groups
         self.group_base_lr = self.group_lr = self.group_wd = None
+        # the optimizer kind is the arena's (ParamArena.set_optimizer, from cfg.optimizer.type in
+        # apis.train.prepare_training); AdamW has the table-driven path only, so it always has groups
+        self.optimizer = arena.optimizer
+        if self.optimizer == "AdamW" and param_groups is None:
+            from .optimizer import ParamGroups
+            param_groups = self.param_groups = ParamGroups(
+                [(1., 1.)], {n: 0 for n, p in model.named_parameters() if p.requires_grad})
         if param_groups is not None:
             arena.set_param_groups(param_groups.index, len(param_groups))
             self.group_base_lr = param_groups.lrs(base_lr)
@@ -607,6 +614,9 @@ class IterBasedRunner:
         from ..hip.runtime import current_stream_ptr
         if self.hyper is None:
             self.hyper = torch.zeros(4, dtype=torch.float32, device=self.arena.flat_param.device)
+        if self.optimizer == "AdamW":      # (its own fp64 table; ``hyper`` only says "written")
+            self.arena.write_adamw_hyper(self.group_lr, self.group_wd, self.grad_scale())
+            return
         _lib.check(_lib.load().gs_sgd_set_hyper(self.hyper.data_ptr(), self.lr, self.momentum,
                                                 self.weight_decay, self.grad_scale(),
                                                 current_stream_ptr()), "gs_sgd_set_hyper")
@@ -654,7 +664,10 @@ class IterBasedRunner:
         return dj.checkpoint
 
     def _sgd(self, ranges, grad_scale, hyper=None):
-        """One fused SGD step on ``ranges`` that clears the gradients it consumed."""
+        """One fused optimizer step on ``ranges`` that clears the gradients it consumed."""
+        if self.optimizer == "AdamW":
+            self.arena.adamw_step(ranges, self.opt_lr, self.opt_wd, grad_scale, True, hyper=hyper)
+            return
         self.arena.sgd_step(ranges, self.opt_lr, self.momentum, self.opt_wd, grad_scale, True,
                             hyper=hyper)
 

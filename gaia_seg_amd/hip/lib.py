@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class HipLibraryError(RuntimeError):
@@ -230,6 +230,14 @@ class SgdGroups(Structure):
     _fields_ = [("lr_wd", c_float * (2 * SGD_MAX_GROUPS))]
 
 
+class AdamwGroups(Structure):
+    """Mirror of ``GsAdamwGroups`` (passed by value): per-group {lr, wd} in fp64."""
+    _fields_ = [("lr_wd", c_double * (2 * SGD_MAX_GROUPS))]
+
+
+ADAMW_HYPER_DOUBLES = 8 + 2 * SGD_MAX_GROUPS   # GS_ADAMW_HYPER_DOUBLES
+
+
 class SgdChunk(Structure):
     """Mirror of ``GsSgdChunk``: {begin, length, group, reserved} in units of 4 floats."""
     _fields_ = [(k, c_int32) for k in ("begin", "length", "group", "reserved")]
@@ -352,6 +360,8 @@ PROTOTYPES = {
     "gs_sgd_set_hyper": (_i32, [_P, _f32, _f32, _f32, _f32, _P]),
     "gs_sgd_set_group_hyper": (_i32, [_P, _f32, _f32, _i32, SgdGroups, _P]),
     "gs_sgd_step_groups": (_i32, [_P, _P, _P, _P, _i32, _P, _i32, _P]),
+    "gs_adamw_set_group_hyper": (_i32, [_P, _f64, _f64, _f64, _f64, _i32, AdamwGroups, _P]),
+    "gs_adamw_step_groups": (_i32, [_P, _P, _P, _P, _P, _i32, _P, _i32, _P, _i32, _P]),
     "gs_grad_accumulate": (_i32, [_P, _P, _i64, _P]),
     "gs_debug_force_plan": (_i32, [_i32, _i32, _i32]),
     "gs_debug_query_plan": (_i32, [_i32, _i32, _i32, _i32, POINTER(_i32), POINTER(_i32), POINTER(_i32),

@@ -828,6 +828,41 @@ int gs_sgd_set_group_hyper(float* hyper, float momentum, float grad_scale, int32
                            GsSgdGroups lr_wd, void* stream);
 int gs_sgd_step_groups(float* param, float* grad, float* momentum_buf, const GsSgdChunk* chunks,
                        int32_t n_chunks, const float* hyper, int32_t zero_grad, void* stream);
+/* Fused AdamW (torch.optim.AdamW, single-tensor form, amsgrad=False, maximize=False) over a chunk
+ * table, with a step counter PER PARAMETER in device memory (torch keeps state['step'] per parameter
+ * and advances it only when the parameter has a gradient; a depth-skipped block of a supernet has
+ * none).  For every element of every chunk, with t = steps[slot] + 1 of the chunk's parameter:
+ *   g = grad * grad_scale
+ *   p *= (float)(1 - lr*wd)
+ *   m += (g - m) * (float)(1 - beta1)
+ *   v  = v * (float)beta2 + g*g * (float)(1 - beta2)
+ *   p -= (float)(lr / (1 - beta1^t)) * m / (sqrt(v) / (float)sqrt(1 - beta2^t) + (float)eps)
+ *   grad = 0 when zero_grad != 0
+ * Every scalar is formed in fp64 and rounded to fp32 once, as torch forms them in Python doubles;
+ * 1 - beta^t is -expm1(t log beta), evaluated in fp64 once per chunk.
+ *   chunks: GsSgdChunk entries whose `reserved` field is the SLOT of the chunk's parameter in
+ *           `steps`.  A chunk never spans two parameters and one parameter's chunks are contiguous
+ *           in the table.  An entry naming a group >= n_groups, a slot outside [0, n_slots), a
+ *           negative begin or a length <= 0 is skipped, not followed.
+ *   steps:  n_slots int32 counters of device memory.  The step kernel only reads them; a second
+ *           small launch of the same call advances, in stream order and without atomics, the counter
+ *           of every parameter the table stepped, by one.  No host read: a captured step graph
+ *           replays both launches.
+ *   hyper:  GS_ADAMW_HYPER_DOUBLES doubles of device memory, 16-byte aligned: {beta1, beta2, eps,
+ *           grad_scale, n_groups, log beta1, log beta2, 0, lr_0, wd_0, lr_1, wd_1, ...}, written by
+ *           gs_adamw_set_group_hyper in stream order (the values travel as kernel arguments).
+ * Elements outside the table are never read or written in param, grad, exp_avg or exp_avg_sq.
+ * GS_E_NULL / GS_E_BADARG (n_chunks <= 0, n_slots <= 0, n_groups outside [1, GS_SGD_MAX_GROUPS], a
+ * beta outside [0, 1), eps <= 0) / GS_E_ALIGN before any launch. */
+#define GS_ADAMW_HYPER_DOUBLES (8 + 2 * GS_SGD_MAX_GROUPS)
+typedef struct GsAdamwGroups {
+  double lr_wd[2 * GS_SGD_MAX_GROUPS]; /* {lr_0, wd_0, lr_1, wd_1, ...}; entries >= n_groups ignored */
+} GsAdamwGroups;
+int gs_adamw_set_group_hyper(double* hyper, double beta1, double beta2, double eps, double grad_scale,
+                             int32_t n_groups, GsAdamwGroups lr_wd, void* stream);
+int gs_adamw_step_groups(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int32_t* steps,
+                         int32_t n_slots, const GsSgdChunk* chunks, int32_t n_chunks,
+                         const double* hyper, int32_t zero_grad, void* stream);
 /* Gradient accumulation of a sandwich iteration (one SGD step over several subnets, US-Nets): the
  * weight-gradient kernels overwrite their gradient, so each member's gradients are moved into an
  * accumulation arena:  dst[i] += src[i]; src[i] = 0  for i in [0, n).  One launch per range; float4
