@@ -636,8 +636,11 @@ static bool ce_rowtile_ok(const gs_ce_desc* d) {
 }
 
 extern "C" size_t gs_ce_backward_workspace_bytes(const gs_ce_desc* d, int32_t ld_d) {
+  CeArgs a;
   int sy, sx;
-  if (!d || !(ce_tile_scales(d, sy, sx) || ce_rowtile_ok(d))) return 0;
+  // a refused descriptor needs no workspace (and ce_tile_scales divides by h and w)
+  if (check_ce(d, a) || ld_d < d->Cls) return 0;
+  if (!(ce_tile_scales(d, sy, sx) || ce_rowtile_ok(d))) return 0;
   return (size_t)d->N * (d->h + 1) * (d->w + 1) * 4 * ld_d * sizeof(float);
 }
 
