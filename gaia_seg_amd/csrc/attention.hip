@@ -16,6 +16,12 @@
 //              lane: the row maximum and sum are 16 register steps and one exchange between the lane
 //              halves.  O^T += V^T P^T keeps the query on the lane, so the online rescale is per lane.
 //              A key past N gets the score -inf, hence p = exp(-inf) = 0 exactly.
+//   relpos   : the same kernel with BEiT's relative-position bias added to the scaled score (template
+//              parameter; the bias-free instantiation is the code above, unchanged).  The N x N bias is
+//              never formed: the head's column of the table (at most 8192 floats) is staged in LDS once
+//              per workgroup and gathered per score.  Lanes of a half wave hold consecutive queries, so
+//              their table rows are consecutive except where the window row wraps: few bank conflicts,
+//              and no gather traffic beside the K / V stream in L2.  Forward only.
 //   backward : delta[b,h,i] = <dO, O> by a pre-pass, as the same d-ordered fma chain the MFMA forms (a
 //              single token gives dP == delta bit for bit, so dQ = dK = 0 exactly).  Then two kernels:
 //              dK / dV : a workgroup owns 128 keys (32 per wave, K and V in registers) and sweeps query
@@ -102,13 +108,24 @@ __device__ __forceinline__ void store_row(float* row, const f32x16& a0, const f3
   }
 }
 
-// grid (ceil(N / 128), heads, B)
+// BEiT's relative-position bias: one fp32 table [(2 Wh - 1)(2 Ww - 1) + 3][heads] (row pitch ld)
+struct AttnBias {
+  const float* table;
+  int32_t ld, Wh, Ww, R;   // R = (2 Wh - 1)(2 Ww - 1): rows R, R + 1, R + 2 are the three cls entries
+};
+
+// grid (ceil(N / 128), heads, B).  kBias: the score of (query i, key j) gets table[idx(i, j)][head] added
+// before the softmax.  The head's column of the table is staged once in (dynamic) LDS; idx(i, j) for
+// i, j >= 1 is qterm(i) + koff(j), qterm on the lane and koff computed once per key tile by 32 threads.
+template <bool kBias>
 __global__ __launch_bounds__(256) void attn_forward_kernel(const AttnArgs a, const float* __restrict__ Q,
                                                            const float* __restrict__ K,
                                                            const float* __restrict__ V, float* __restrict__ O,
-                                                           float* __restrict__ lse) {
+                                                           float* __restrict__ lse, const AttnBias rb) {
   __shared__ float sK[kTK * kPitch];
   __shared__ float sV[kTK * kPitch];
+  __shared__ int sKoff[kBias ? kTK : 1];
+  extern __shared__ float sTab[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ql = lane & 31, h = lane >> 5;
   const int hd = blockIdx.y, b = blockIdx.z;
@@ -121,10 +138,32 @@ __global__ __launch_bounds__(256) void attn_forward_kernel(const AttnArgs a, con
   const float* Vb = V + tok0 * a.ldv + hd * kD;
   f32x16 o0 = zero16(), o1 = zero16();
   float m = -INFINITY, l = 0.f;   // l: the sum over this lane half's keys
+  // the cls query (and a lane past N, whose result is dropped) reads row R whatever the key
+  int qterm = rb.R, qand = 0, key0 = rb.R + 2;
+  if constexpr (kBias) {
+    for (int t = threadIdx.x; t < rb.R + 3; t += 256) sTab[t] = rb.table[(int64_t)t * rb.ld + hd];
+    if (qok && q > 0) {
+      const int iy = (q - 1) / rb.Ww, ix = (q - 1) - iy * rb.Ww;
+      qterm = iy * (2 * rb.Ww - 1) + ix;
+      qand = -1;
+      key0 = rb.R + 1;
+    }
+  }
   for (int k0 = 0; k0 < a.N; k0 += kTK) {
     __syncthreads();
     stage_tile(sK, Kb, k0, a.N, a.ldk);
     stage_tile(sV, Vb, k0, a.N, a.ldv);
+    if constexpr (kBias) {
+      if (threadIdx.x < kTK) {   // key j = 1 + jy Ww + jx: (Wh - 1 - jy)(2 Ww - 1) + (Ww - 1 - jx)
+        const int j = k0 + threadIdx.x;
+        int off = 0;             // the cls key (replaced by key0 below) and keys past N (score -inf)
+        if (j >= 1 && j < a.N) {
+          const int jy = (j - 1) / rb.Ww, jx = (j - 1) - jy * rb.Ww;
+          off = (rb.Wh - 1 - jy) * (2 * rb.Ww - 1) + (rb.Ww - 1 - jx);
+        }
+        sKoff[threadIdx.x] = off;
+      }
+    }
     __syncthreads();
     f32x16 s = zero16();   // S^T[key][query]
 #pragma unroll
@@ -132,7 +171,12 @@ __global__ __launch_bounds__(256) void attn_forward_kernel(const AttnArgs a, con
     float tmax = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      s[r] = (k0 + acc_row(r, h) < a.N) ? __fmul_rn(s[r], a.scale) : -INFINITY;
+      float sc = __fmul_rn(s[r], a.scale);
+      if constexpr (kBias) {
+        const int kr = acc_row(r, h);
+        sc += sTab[k0 + kr == 0 ? key0 : qterm + (sKoff[kr] & qand)];
+      }
+      s[r] = (k0 + acc_row(r, h) < a.N) ? sc : -INFINITY;
       tmax = fmaxf(tmax, s[r]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -392,7 +436,28 @@ extern "C" int gs_attention_forward(const gs_attention_desc* d, const float* q, 
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(lse)) return GS_E_ALIGN;
   const AttnArgs a = attn_args(d, 0);
   const dim3 grid((unsigned)ceil_div(d->N, kTQ), (unsigned)d->heads, (unsigned)d->B);
-  hipLaunchKernelGGL(attn_forward_kernel, grid, dim3(256), 0, as_stream(stream), a, q, k, v, o, lse);
+  hipLaunchKernelGGL(attn_forward_kernel<false>, grid, dim3(256), 0, as_stream(stream), a, q, k, v, o, lse,
+                     AttnBias{nullptr, 0, 0, 0, 0});
+  return launch_status();
+}
+
+extern "C" int gs_attention_relpos_forward(const gs_attention_desc* d, const float* q, const float* k,
+                                           const float* v, const float* table, int32_t ld_table, int32_t Wh,
+                                           int32_t Ww, float* o, float* lse, void* stream) {
+  const int rc = attn_check(d);
+  if (rc != GS_OK) return rc;
+  if (Wh < 1 || Ww < 1 || (int64_t)Wh * Ww + 1 != d->N || ld_table < d->heads) return GS_E_BADARG;
+  const int64_t R = (2 * (int64_t)Wh - 1) * (2 * (int64_t)Ww - 1);
+  if (R + 3 > GS_ATTENTION_RELPOS_MAX_ROWS) return GS_E_BADARG;
+  if (!q || !k || !v || !table || !o || !lse) return GS_E_NULL;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(lse) ||
+      (reinterpret_cast<uintptr_t>(table) & 3u))
+    return GS_E_ALIGN;
+  const AttnArgs a = attn_args(d, 0);
+  const AttnBias rb = {table, ld_table, Wh, Ww, (int32_t)R};
+  const dim3 grid((unsigned)ceil_div(d->N, kTQ), (unsigned)d->heads, (unsigned)d->B);
+  const size_t lds = (size_t)ceil_div((R + 3) * (int64_t)sizeof(float), 16) * 16;
+  hipLaunchKernelGGL(attn_forward_kernel<true>, grid, dim3(256), lds, as_stream(stream), a, q, k, v, o, lse, rb);
   return launch_status();
 }
 

@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 class HipLibraryError(RuntimeError):
@@ -97,6 +97,7 @@ class AttentionDesc(Structure):
 
 
 ATTENTION_HEAD_DIM = 64
+ATTENTION_RELPOS_MAX_ROWS = 8192   # GS_ATTENTION_RELPOS_MAX_ROWS
 
 
 def attention_desc(b, n, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=None, ldk=None, ldv=None, ldo=None,
@@ -274,6 +275,8 @@ PROTOTYPES = {
     "gs_dwconv2d_forward": (_i32, [_DW, _P, _P, _P, _P, _P]),
     "gs_dwconv2d_dgrad": (_i32, [_DW, _P, _P, _P, _i32, _P]),
     "gs_dwconv2d_wgrad": (_i32, [_DW, _P, _P, _P, _P, _sz, _P]),
+    "gs_deconv2x2_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "gs_deconv2x2_forward": (_i32, [_P, _i32, _i32, _i32, _i32, _i32, _P, _i32, _P, _P, _i32, _P, _sz, _P]),
     "gs_layernorm_forward": (_i32, [_LN, _P, _P, _P, _P, _P, _P, _P]),
     "gs_layernorm_workspace_bytes": (_sz, [_LN]),
     "gs_layernorm_backward": (_i32, [_LN, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
@@ -283,6 +286,7 @@ PROTOTYPES = {
     "gs_layer_scale_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_layer_scale_backward": (_i32, [_P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P, _sz, _P]),
     "gs_attention_forward": (_i32, [_AT, _P, _P, _P, _P, _P, _P]),
+    "gs_attention_relpos_forward": (_i32, [_AT, _P, _P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
     "gs_attention_workspace_bytes": (_sz, [_AT]),
     "gs_attention_backward": (_i32, [_AT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
     "gs_vit_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _P]),

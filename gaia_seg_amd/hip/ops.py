@@ -938,6 +938,78 @@ def attention(tape, q, k, v, heads, scale, out=None):
     return out
 
 
+def _forward_only(tape, what, *inputs):
+    if tape.enabled and any(t.requires_grad for t in inputs):
+        raise NotImplementedError("%s: forward only (no backward kernel); called with a recording tape and an "
+                                  "input that requires grad" % what)
+
+
+def attention_relpos(tape, q, k, v, heads, scale, table, window, out=None):
+    """BEiT's attention, forward only: ``attention`` with table[idx(i, j), h] added to the scaled score of
+    (query i, key j) in head h.  ``table`` is a relative_position_bias_table [(2 Wh - 1)(2 Ww - 1) + 3, heads]
+    (fp32, any row pitch), ``window`` = (Wh, Ww), N = Wh * Ww + 1 tokens with the cls token first.  The
+    kernel gathers from the table: no N x N bias exists."""
+    L = _L()
+    _forward_only(tape, "attention_relpos", q, k, v, table)
+    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
+    c = _lib.ATTENTION_HEAD_DIM * heads
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.C != c or t.rows != q.rows or t.H != 1:
+            raise ValueError("attention_relpos: %s is %s, expected [B, 1, N, %d] for %d heads"
+                             % (name, tuple(t.t.shape), c, heads))
+    wh, ww = window
+    rows = (2 * wh - 1) * (2 * ww - 1) + 3
+    if table.dim() != 2 or table.shape[0] != rows or table.shape[1] < heads or table.stride(1) != 1:
+        raise ValueError("attention_relpos: the table is %s, expected [%d, >= %d] for a %d x %d window"
+                         % (tuple(table.shape), rows, heads, wh, ww))
+    if rows > _lib.ATTENTION_RELPOS_MAX_ROWS:
+        raise ValueError("attention_relpos: a %d x %d window needs %d table rows, the kernel stages at most "
+                         "%d in LDS" % (wh, ww, rows, _lib.ATTENTION_RELPOS_MAX_ROWS))
+    b, n, dev = q.N, q.W, q.t.device
+    if out is None:
+        out = Act.empty(b, 1, n, c, dev)
+    lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
+    d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    _lib.check(L.gs_attention_relpos_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, table.data_ptr(),
+                                             table.stride(0), wh, ww, out.ptr, lse.data_ptr(),
+                                             current_stream_ptr()), "gs_attention_relpos_forward")
+    return out
+
+
+def _deconv_packed(weight):
+    """torch's ConvTranspose2d weight [Cin, Cout, 2, 2] as the GEMM operand [Cin][2][2][Cout] of
+    gs_deconv2x2_forward: made on first use, again when the parameter has been written to (``_version``)
+    or moved."""
+    key = (weight._version, weight.data_ptr(), weight.device)
+    cached = weight.__dict__.get("_gs_deconv_packed")
+    if cached is None or cached[0] != key:
+        cached = weight._gs_deconv_packed = (key, weight.detach().permute(0, 2, 3, 1).contiguous())
+    return cached[1]
+
+
+def deconv2x2(tape, x, weight, bias, out=None):
+    """nn.ConvTranspose2d(Cin, Cout, kernel_size=2, stride=2) forward on an NHWC activation; ``weight`` is
+    the Parameter in torch's [Cin, Cout, 2, 2] layout.  Forward only."""
+    L = _L()
+    _forward_only(tape, "deconv2x2", x, weight, *([bias] if bias is not None else []))
+    x = materialize(tape, x)
+    cin, cout = weight.shape[0], weight.shape[1]
+    if tuple(weight.shape[2:]) != (2, 2) or x.C != cin:
+        raise ValueError("deconv2x2: weight %s does not fit an input of %d channels (expected [%d, Cout, 2, 2])"
+                         % (tuple(weight.shape), x.C, x.C))
+    if cin % 4 or cout % 4:
+        raise ValueError("deconv2x2 needs channel counts that are multiples of 4, got %d -> %d" % (cin, cout))
+    dev = x.t.device
+    if out is None:
+        out = Act.empty(x.N, 2 * x.H, 2 * x.W, cout, dev)
+    w4 = _deconv_packed(weight)
+    ws = _ws.get(L.gs_deconv2x2_workspace_bytes(x.N, x.H, x.W, cin, cout), dev)
+    _lib.check(L.gs_deconv2x2_forward(x.ptr, x.N, x.H, x.W, cin, x.ld, w4.data_ptr(), cout,
+                                      bias.data_ptr() if bias is not None else None, out.ptr, out.ld,
+                                      ws.data_ptr(), ws.numel(), current_stream_ptr()), "gs_deconv2x2_forward")
+    return out
+
+
 def vit_tokens(tape, patches, cls_token, pos_embed):
     """ElasticTransformer's token assembly: from the patch embedding [B, Hp, Wp, D] and the max-size
     ``cls_token`` [1, 1, D_max] / ``pos_embed`` [1, N_max, D_max] Parameters, the token activation

@@ -22,6 +22,7 @@ def add_prefix(inputs, prefix):
     return {"%s.%s" % (prefix, name): value for name, value in inputs.items()}
 
 
+@builder.SEGMENTORS.register_module()   # (a fixed model, e.g. a distiller's BEiT teacher, by its mmseg name)
 class EncoderDecoder(nn.Module):
     def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None,
                  test_cfg=None, pretrained=None):

@@ -202,6 +202,24 @@ int gs_layer_scale_backward(const float* dout, const float* z, const float* gamm
                             int32_t lddz, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* ConvTranspose2d(kernel_size = 2, stride = 2), forward only (BEiT's fpn1 / fpn2)              */
+/* ------------------------------------------------------------------------------------------ */
+/* y[n, 2 h + dy, 2 w + dx, :Cout] = sum_ci x[n, h, w, ci] * w4[ci][(2 dy + dx) * Cout + co] (+ bias[co]):
+ * kernel == stride, so the four taps are four independent 1x1 convolutions.  They run as ONE
+ * gs_conv2d_forward GEMM Cin -> 4 Cout (the MFMA implicit-GEMM kernels, in the library's forward
+ * precision) into scratch, and a depth-to-space kernel moves the rows to their output pixels and adds the
+ * bias.  x: NHWC fp32 [N][H][W] with pixel pitch ldx >= Cin; w4: [Cin][4 Cout] packed, i.e. torch's
+ * ConvTranspose2d weight [Cin][Cout][2][2] permuted to [Cin][2][2][Cout]; bias: [Cout] or NULL;
+ * y: NHWC [N][2 H][2 W] with pixel pitch ldy >= Cout, columns Cout.. are not written.
+ * GS_E_BADARG (a size <= 0, a pitch below its width, more than 2^31 - 1 output pixels), GS_E_ALIGN (Cin,
+ * Cout or a pitch no multiple of 4, a pointer not 16-byte aligned), GS_E_NULL, GS_E_WORKSPACE (below
+ * gs_deconv2x2_workspace_bytes, which is 0 for sizes the forward refuses). */
+size_t gs_deconv2x2_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+int gs_deconv2x2_forward(const float* x, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldx,
+                         const float* w4, int32_t Cout, const float* bias, float* y, int32_t ldy,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Multi-head softmax self-attention (head dimension 64) and the ViT token assembly             */
 /* ------------------------------------------------------------------------------------------ */
 /* ElasticMHA.forward with relative_position=False (gaiaseg/models/backbones/elastic_transformer.py):
@@ -224,6 +242,27 @@ typedef struct gs_attention_desc {
 } gs_attention_desc;
 int gs_attention_forward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
                          float* o, float* lse, void* stream);
+/* BEiT's attention (forward only: the frozen teacher of DynamicDistiller): gs_attention_forward with an
+ * additive per-head relative-position bias,
+ *   O[b,i,h,:] = sum_j softmax_j(scale * <q_i, k_j> + table[idx(i,j)][h]) v_j,
+ * for N = Wh * Ww + 1 tokens, token 0 the cls token and token t >= 1 at (ty, tx) = divmod(t - 1, Ww) of the
+ * Wh x Ww patch window.  With R = (2 Wh - 1)(2 Ww - 1):
+ *   idx(i, j) = (iy - jy + Wh - 1) * (2 Ww - 1) + (ix - jx + Ww - 1)   for i, j >= 1,
+ *   idx(0, j >= 1) = R,   idx(i >= 1, 0) = R + 1,   idx(0, 0) = R + 2.
+ * table is fp32 [R + 3][heads] with row pitch ld_table >= heads: a checkpoint's
+ * relative_position_bias_table as it stands.  q, k, v, o, lse and d as for gs_attention_forward (same
+ * kernel, same exact-fp32 products, online softmax, fixed summation order, no atomics); lse includes the
+ * bias.  No N x N tensor exists anywhere: a workgroup stages its head's column of the table in LDS and
+ * gathers from it, which caps the table at GS_ATTENTION_RELPOS_MAX_ROWS rows (32 KiB beside the 16.5 KiB
+ * of key / value tiles; windows 32 x 64 and 40 x 40 fit).  A zero table gives the bits of
+ * gs_attention_forward.
+ * Checked before any launch: what gs_attention_forward checks, then GS_E_BADARG for Wh or Ww < 1,
+ * N != Wh * Ww + 1, ld_table < heads or R + 3 > GS_ATTENTION_RELPOS_MAX_ROWS; GS_E_NULL (table too);
+ * GS_E_ALIGN (table: 4-byte aligned). */
+#define GS_ATTENTION_RELPOS_MAX_ROWS 8192
+int gs_attention_relpos_forward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+                                const float* table, int32_t ld_table, int32_t Wh, int32_t Ww, float* o,
+                                float* lse, void* stream);
 /* bytes of scratch gs_attention_backward needs (0 for a descriptor it would refuse): delta[B][heads][N]. */
 size_t gs_attention_workspace_bytes(const gs_attention_desc* d);
 /* dQ, dK, dV (each = or +=, accumulate != 0 adds) from Q, K, V, O, lse and dO.  P is recomputed from Q, K
