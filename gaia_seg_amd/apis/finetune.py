@@ -55,7 +55,8 @@ def check_finetune_cfg(cfg, metas):
                          "tools/test_supernet.py")
     if not metas:
         raise ValueError("fast-finetune: no subnet to finetune (empty metas)")
-    optimizer_hook(cfg.get("optimizer_config"))   # grad_clip / dynamic loss scale: refused here
+    # grad_clip / dynamic loss scale / a non-bool fp16.attention: refused here
+    optimizer_hook(cfg.get("optimizer_config"), cfg.get("fp16"))
     if cfg.get("apply_input_shape", False):          # a scale no batch can take: refused here
         for meta in metas:
             if meta.get(INPUT_SHAPE_KEY) is not None:
@@ -65,8 +66,8 @@ def check_finetune_cfg(cfg, metas):
 
 class SupernetSnapshot:
     """S0: a device-side copy of the parameter arena and of every module buffer, and the host-side
-    state a run changes (arch, training mode, fp16_enabled flags).  ``restore`` is device copies
-    only."""
+    state a run changes (arch, training mode, fp16_enabled and fp16_attention flags).  ``restore`` is
+    device copies only."""
 
     def __init__(self, model, arena):
         self.model, self.arena = model, arena
@@ -78,6 +79,7 @@ class SupernetSnapshot:
                                   if v is not None}}
         self.training = model.training
         self.fp16 = [(m, m.fp16_enabled) for m in model.modules() if hasattr(m, "fp16_enabled")]
+        self.fp16_attention = [(m, m.fp16_attention) for m in model.modules() if hasattr(m, "fp16_attention")]
 
     @staticmethod
     def _flush(model):
@@ -88,7 +90,8 @@ class SupernetSnapshot:
     def restore(self, host_state=False):
         """Parameters and buffers back to S0 bit for bit, momentum / gradient / accumulation arenas
         zero (``grads_clean`` truthful), per-module caches of old buffers dropped.  ``host_state``:
-        also the arch, the training mode and the fp16_enabled flags found at snapshot time."""
+        also the arch and the training mode found at snapshot time.  The fp16_enabled and fp16_attention
+        flags (set by the fp16 hook of a run) go back either way."""
         a = self.arena
         with torch.no_grad():
             a.flat_param.copy_(self.flat_param)
@@ -106,6 +109,8 @@ class SupernetSnapshot:
                 d["_nbt_pending"] = 0
         for m, flag in self.fp16:
             m.fp16_enabled = flag
+        for m, flag in self.fp16_attention:
+            m.fp16_attention = flag
         if host_state:
             self.model.manipulate_arch(self.arch)
             self.model.train(self.training)
@@ -160,7 +165,7 @@ def finetune_model_space(model, metas, cfg, train_data, val_loader, num_batches,
             _restart(train_loader)
             sampler_cfg = anchor_sampler_cfg(meta, i)
             anchor = sampler_cfg["anchors"][0]
-            opt_hook = optimizer_hook(cfg.get("optimizer_config"))   # (a fresh loss-scaler state)
+            opt_hook = optimizer_hook(cfg.get("optimizer_config"), cfg.get("fp16"))   # (a fresh loss-scaler state)
             timing = {}
 
             def before_run(runner, timing=timing):

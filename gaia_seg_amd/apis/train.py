@@ -117,16 +117,21 @@ def wants_tta(pipeline):
     return False
 
 
-def optimizer_hook(optimizer_config):
+def optimizer_hook(optimizer_config, fp16=None):
     """``cfg.optimizer_config`` -> the arena optimizer hook (mmcv's register_training_hooks builds
     the hook it names).  ``type='Fp16OptimizerHook'`` turns on fp16 training with its ``loss_scale``
     (core/runner.py Fp16ArenaOptimizerHook); any other (or no) type is the fp32 OptimizerHook.  A
-    top-level ``fp16`` key alone means fp16 evaluation (tools/test_supernet.py), not training."""
+    top-level ``fp16`` key alone means fp16 evaluation (tools/test_supernet.py), not training.
+    ``fp16`` is that key's value: with the fp16 hook, ``fp16 = dict(attention=True)`` makes the hook wrap
+    the model for fp16 attention as well; without the hook it changes nothing
+    here.  Its type is checked either way."""
+    from ..core.fp16_utils import check_fp16_cfg
+    attention = check_fp16_cfg(fp16)
     oc = dict(optimizer_config or {})
     if oc.get("grad_clip"):
         raise NotImplementedError("grad_clip")
     if oc.pop("type", None) == "Fp16OptimizerHook":
-        return Fp16ArenaOptimizerHook(**oc)
+        return Fp16ArenaOptimizerHook(attention=attention, **oc)
     return ArenaOptimizerHook()
 
 
@@ -250,7 +255,7 @@ def run_training(model, arena, reducer, param_groups, train_sampler, val_sampler
 
 def train_segmentor(model, train_sampler, val_sampler, dataset, cfg, distributed=False,
                     validate=False, timestamp=None, meta=None, logger=None):
-    opt_hook = optimizer_hook(cfg.get("optimizer_config"))
+    opt_hook = optimizer_hook(cfg.get("optimizer_config"), cfg.get("fp16"))
     check_input_shape_cfg(cfg)
     if cfg.get("use_distillation", False) and isinstance(opt_hook, Fp16ArenaOptimizerHook):
         raise ValueError("use_distillation with fp16 training (optimizer_config type "

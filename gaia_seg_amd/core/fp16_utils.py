@@ -14,10 +14,30 @@ sets around every step when ``optimizer_config = dict(type='Fp16OptimizerHook', 
 in mmcv's state_dict form, the form checkpoints carry under ``meta['fp16']['loss_scaler']``."""
 
 
-def wrap_fp16_model(model):
+def check_fp16_cfg(fp16):
+    """A config's ``fp16`` value (None or a dict) -> whether it asks for fp16 attention:
+    ``fp16 = dict(attention=True)``.  The key must be a bool."""
+    attention = (fp16 or {}).get("attention", False)
+    if not isinstance(attention, bool):
+        raise ValueError("fp16.attention must be a bool, got %r" % (attention,))
+    return attention
+
+
+def wrap_fp16_model(model, attention=None):
     """Set ``fp16_enabled`` on every module that has the attribute (the segmentor: its simple_test,
     simple_test_device and aug_test then run inside ops.forward_precision('fp16')).  Returns the
-    model.  A wrapper (DistributedDataParallel) is looked through by ``modules()``."""
+    model.  A wrapper (DistributedDataParallel) is looked through by ``modules()``.
+
+    ``attention=True`` also sets ``fp16_attention`` on every module that has it (ElasticTransformer, BEiT
+    and their attention modules): inside an fp16 mode their attention then runs on the fp16-operand
+    kernels.  A model without such a module raises ValueError: the switch would
+    do nothing.  ``attention=None`` (the default, what tools/test_supernet.py's ``wrap_fp16_model(model)``
+    gives) takes ``fp16 = dict(attention=...)`` of the config the model was built from
+    (``model.top_cfg``, models/builder.py); a model built from a plain dict has no such config, and the
+    switch stays off."""
+    if attention is None:
+        tops = [m.top_cfg for m in model.modules() if getattr(m, "top_cfg", None) is not None]
+        attention = check_fp16_cfg(tops[0].get("fp16")) if tops else False
     n = 0
     for m in model.modules():
         if hasattr(m, "fp16_enabled"):
@@ -26,6 +46,14 @@ def wrap_fp16_model(model):
     if n == 0:
         raise ValueError("wrap_fp16_model: no module of %s has an fp16_enabled attribute"
                          % type(model).__name__)
+    if attention:
+        mods = [m for m in model.modules() if hasattr(m, "fp16_attention")]
+        if not mods:
+            raise ValueError("wrap_fp16_model(attention=True): no module of %s has an fp16_attention "
+                             "attribute (fp16 attention needs an ElasticTransformer or BEiT backbone)"
+                             % type(model).__name__)
+        for m in mods:
+            m.fp16_attention = True
     return model
 
 

@@ -291,19 +291,21 @@ class Fp16ArenaOptimizerHook(ArenaOptimizerHook):
     backward is seeded with S and SGD's gradient scale becomes 1 / (world_size * S).  As mmcv's hook
     does in before_run, the model is wrapped for fp16 (its evaluation then runs in fp16 as well) and
     a scaler state found in ``runner.meta['fp16']['loss_scaler']`` (a resumed checkpoint) is restored.
-    Only the static form: ``loss_scale='dynamic'`` or a dict are refused (not implemented)."""
+    Only the static form: ``loss_scale='dynamic'`` or a dict are refused (not implemented).
+    ``attention``: the model is wrapped for fp16 attention too."""
 
     def __init__(self, grad_clip=None, loss_scale=512., coalesce=True, bucket_size_mb=-1,
-                 distributed=True):
+                 distributed=True, attention=False):
         super().__init__(grad_clip)
         from .fp16_utils import LossScaler
         self.loss_scaler = LossScaler(**parse_loss_scale(loss_scale))
+        self.attention = attention   # ``fp16 = dict(attention=True)`` of the config (apis.train.optimizer_hook)
 
     def before_run(self, runner):
         from .fp16_utils import wrap_fp16_model
         if any(isinstance(h, SandwichHook) for h in runner.hooks):
             raise ValueError("fp16 training with use_distillation (sandwich) is not supported")
-        wrap_fp16_model(runner.model)
+        wrap_fp16_model(runner.model, attention=self.attention)
         saved = ((runner.meta or {}).get("fp16") or {}).get("loss_scaler")
         if saved is not None:
             self.loss_scaler.load_state_dict(saved)
@@ -583,7 +585,9 @@ class IterBasedRunner:
         # (a step captured in fp32 must never be replayed in fp16, nor one scaled by another S)
         # (nor a step captured under another grouping: the arena counts its set_param_groups calls)
         grouping = None if self.arena.groups is None else (self.arena.group_epoch, self.arena.groups)
-        return (self.arch_key, tuple(sig), self.model.training, grouping, self.train_precision,
+        # (nor one captured with the fp32 attention kernels under the fp16 ones, or the reverse)
+        attention = tuple(bool(m.fp16_attention) for m in self.model.modules() if hasattr(m, "fp16_attention"))
+        return (self.arch_key, tuple(sig), self.model.training, grouping, attention, self.train_precision,
                 self.loss_scale)
 
     def _apply_input_shape(self, data_batch):

@@ -35,37 +35,16 @@
 //              column]) for the second ones.
 #include <math.h>
 
-#include "common.h"
+#include "attention_common.h"
 
 namespace gs {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kD = 64;        // head dimension
-constexpr int kTK = 32;       // rows of a tile that is swept through LDS
-constexpr int kTQ = 128;      // rows a workgroup owns (32 per wave)
 constexpr int kPitch = 66;    // floats per LDS tile row
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.f;
-  return z;
-}
-
-struct AttnArgs {
-  int32_t B, N, heads;
-  int32_t ldq, ldk, ldv, ldo, lddq, lddk, lddv, lddo;
-  float scale;
-  int32_t accumulate;
-};
 
 // rows [row0, row0 + 32) of one (batch, head) block `src` (pitch ld) into an LDS tile; rows >= N are 0
 __device__ __forceinline__ void stage_tile(float* tile, const float* src, int row0, int N, int ld) {
@@ -89,30 +68,6 @@ __device__ __forceinline__ void load_row_regs(float (&reg)[32], const float* row
     reg[2 * c + 1] = h ? v.w : v.z;
   }
 }
-
-// an accumulator pair (columns d 0..31 and 32..63 of a row this lane owns, transposed) to memory
-__device__ __forceinline__ void store_row(float* row, const f32x16& a0, const f32x16& a1, int h, float mul,
-                                          int accumulate) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    f32x4 v0 = f32x4{a0[4 * g], a0[4 * g + 1], a0[4 * g + 2], a0[4 * g + 3]} * mul;
-    f32x4 v1 = f32x4{a1[4 * g], a1[4 * g + 1], a1[4 * g + 2], a1[4 * g + 3]} * mul;
-    float* p0 = row + 8 * g + 4 * h;
-    float* p1 = p0 + 32;
-    if (accumulate) {
-      v0 += ld4(p0);
-      v1 += ld4(p1);
-    }
-    st4(p0, v0);
-    st4(p1, v1);
-  }
-}
-
-// BEiT's relative-position bias: one fp32 table [(2 Wh - 1)(2 Ww - 1) + 3][heads] (row pitch ld)
-struct AttnBias {
-  const float* table;
-  int32_t ld, Wh, Ww, R;   // R = (2 Wh - 1)(2 Ww - 1): rows R, R + 1, R + 2 are the three cls entries
-};
 
 // grid (ceil(N / 128), heads, B).  kBias: the score of (query i, key j) gets table[idx(i, j)][head] added
 // before the softmax.  The head's column of the table is staged once in (dynamic) LDS; idx(i, j) for
@@ -383,28 +338,6 @@ __global__ __launch_bounds__(256) void vit_tokens_backward_kernel(const float* _
   }
 }
 
-int attn_check(const gs_attention_desc* d) {
-  if (!d) return GS_E_NULL;
-  if (d->B <= 0 || d->N <= 0 || d->heads <= 0 || !(d->scale > 0.f)) return GS_E_BADARG;
-  if (d->B > 65535 || d->heads > 65535 || d->heads > INT32_MAX / kD) return GS_E_BADARG;
-  const int32_t ld[8] = {d->ldq, d->ldk, d->ldv, d->ldo, d->lddq, d->lddk, d->lddv, d->lddo};
-  for (int i = 0; i < 8; ++i)
-    if (ld[i] % 4) return GS_E_ALIGN;
-  for (int i = 0; i < 8; ++i)
-    if (ld[i] < kD * d->heads) return GS_E_BADARG;
-  return GS_OK;
-}
-
-AttnArgs attn_args(const gs_attention_desc* d, int accumulate) {
-  AttnArgs a;
-  a.B = d->B; a.N = d->N; a.heads = d->heads;
-  a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv; a.ldo = d->ldo;
-  a.lddq = d->lddq; a.lddk = d->lddk; a.lddv = d->lddv; a.lddo = d->lddo;
-  a.scale = d->scale;
-  a.accumulate = accumulate ? 1 : 0;
-  return a;
-}
-
 inline size_t attn_ws_bytes(const gs_attention_desc* d) {
   return (size_t)ceil_div((int64_t)d->B * d->heads * d->N * (int64_t)sizeof(float), 16) * 16;
 }
@@ -446,9 +379,9 @@ extern "C" int gs_attention_relpos_forward(const gs_attention_desc* d, const flo
                                            int32_t Ww, float* o, float* lse, void* stream) {
   const int rc = attn_check(d);
   if (rc != GS_OK) return rc;
-  if (Wh < 1 || Ww < 1 || (int64_t)Wh * Ww + 1 != d->N || ld_table < d->heads) return GS_E_BADARG;
+  const int rb_rc = attn_relpos_check(d, ld_table, Wh, Ww);
+  if (rb_rc != GS_OK) return rb_rc;
   const int64_t R = (2 * (int64_t)Wh - 1) * (2 * (int64_t)Ww - 1);
-  if (R + 3 > GS_ATTENTION_RELPOS_MAX_ROWS) return GS_E_BADARG;
   if (!q || !k || !v || !table || !o || !lse) return GS_E_NULL;
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(lse) ||
       (reinterpret_cast<uintptr_t>(table) & 3u))

@@ -289,6 +289,10 @@ PROTOTYPES = {
     "gs_attention_relpos_forward": (_i32, [_AT, _P, _P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
     "gs_attention_workspace_bytes": (_sz, [_AT]),
     "gs_attention_backward": (_i32, [_AT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_attention_forward_f16": (_i32, [_AT, _P, _P, _P, _P, _P, _P]),
+    "gs_attention_relpos_forward_f16": (_i32, [_AT, _P, _P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
+    "gs_attention_workspace_bytes_f16": (_sz, [_AT]),
+    "gs_attention_backward_f16": (_i32, [_AT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
     "gs_vit_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_vit_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_colsum_workspace_bytes": (_sz, [_i64, _i32]),

@@ -897,12 +897,23 @@ def layer_scale_add(tape, identity, z, gamma, out=None):
     return out
 
 
-def attention(tape, q, k, v, heads, scale, out=None):
+def _attention_f16(f16):
+    """Whether an attention op called with ``f16`` takes the fp16-operand entries: only inside an fp16 mode
+    (the forward switch, or the library's train precision).  In fp32 modes the flag does nothing."""
+    return bool(f16) and (FORWARD_PRECISION == _lib.PRECISION_FP16
+                          or _L().gs_get_train_precision() == _lib.PRECISION_FP16)
+
+
+def attention(tape, q, k, v, heads, scale, out=None, f16=False):
     """Multi-head softmax self-attention, head dimension 64: ``heads`` active heads in the leading
     64 * heads columns of q, k and v (token activations [B, 1, N, 64 * heads], each with its own pitch: three
     column slices of one buffer are fine).  No N x N matrix is stored; the log-sum-exp of every query row is
-    kept for the backward, which recomputes the probabilities."""
+    kept for the backward, which recomputes the probabilities.  ``f16`` (opt-in, honoured only in an fp16
+    mode): fp16 MFMA operands with fp32 accumulation, forward and backward."""
     L = _L()
+    sfx = "_f16" if _attention_f16(f16) else ""
+    fwd, bwd = getattr(L, "gs_attention_forward" + sfx), getattr(L, "gs_attention_backward" + sfx)
+    ws_bytes = getattr(L, "gs_attention_workspace_bytes" + sfx)
     q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
     c = _lib.ATTENTION_HEAD_DIM * heads
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -914,8 +925,8 @@ def attention(tape, q, k, v, heads, scale, out=None):
         out = Act.empty(b, 1, n, c, dev)
     lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
     d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
-    _lib.check(L.gs_attention_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(),
-                                      current_stream_ptr()), "gs_attention_forward")
+    _lib.check(fwd(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), current_stream_ptr()),
+               "gs_attention_forward" + sfx)
 
     def backward():
         dy = out.g
@@ -928,11 +939,10 @@ def attention(tape, q, k, v, heads, scale, out=None):
                     t.g.zero_()
         d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
         db = ctypes.byref(d)
-        ws = _ws.get(L.gs_attention_workspace_bytes(db), dev)
-        _lib.check(L.gs_attention_backward(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(),
-                                           q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(), 1 if any(accs) else 0,
-                                           ws.data_ptr(), ws.numel(), current_stream_ptr()),
-                   "gs_attention_backward")
+        ws = _ws.get(ws_bytes(db), dev)
+        _lib.check(bwd(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(), q.g.data_ptr(),
+                       k.g.data_ptr(), v.g.data_ptr(), 1 if any(accs) else 0, ws.data_ptr(), ws.numel(),
+                       current_stream_ptr()), "gs_attention_backward" + sfx)
 
     tape.record(backward)
     return out
@@ -944,12 +954,13 @@ def _forward_only(tape, what, *inputs):
                                   "input that requires grad" % what)
 
 
-def attention_relpos(tape, q, k, v, heads, scale, table, window, out=None):
+def attention_relpos(tape, q, k, v, heads, scale, table, window, out=None, f16=False):
     """BEiT's attention, forward only: ``attention`` with table[idx(i, j), h] added to the scaled score of
     (query i, key j) in head h.  ``table`` is a relative_position_bias_table [(2 Wh - 1)(2 Ww - 1) + 3, heads]
     (fp32, any row pitch), ``window`` = (Wh, Ww), N = Wh * Ww + 1 tokens with the cls token first.  The
-    kernel gathers from the table: no N x N bias exists."""
+    kernel gathers from the table: no N x N bias exists.  ``f16`` as for ``attention``; the bias stays fp32."""
     L = _L()
+    sfx = "_f16" if _attention_f16(f16) else ""
     _forward_only(tape, "attention_relpos", q, k, v, table)
     q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
     c = _lib.ATTENTION_HEAD_DIM * heads
@@ -970,9 +981,9 @@ def attention_relpos(tape, q, k, v, heads, scale, table, window, out=None):
         out = Act.empty(b, 1, n, c, dev)
     lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
     d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
-    _lib.check(L.gs_attention_relpos_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, table.data_ptr(),
-                                             table.stride(0), wh, ww, out.ptr, lse.data_ptr(),
-                                             current_stream_ptr()), "gs_attention_relpos_forward")
+    _lib.check(getattr(L, "gs_attention_relpos_forward" + sfx)(
+        ctypes.byref(d), q.ptr, k.ptr, v.ptr, table.data_ptr(), table.stride(0), wh, ww, out.ptr,
+        lse.data_ptr(), current_stream_ptr()), "gs_attention_relpos_forward" + sfx)
     return out
 
 

@@ -103,6 +103,8 @@ class RelativePositionBias(_RelPosTable):
 
 
 class Attention(_RelPosTable):
+    fp16_attention = False   # set through BEiT.fp16_attention
+
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0.,
                  window_size=None, attn_head_dim=None):
         super().__init__()
@@ -146,9 +148,10 @@ class Attention(_RelPosTable):
         qkv = ops.conv2d(tape, x, self.qkv.weight, self._qkv_bias(), 3 * width)
         q, k, v = (qkv.slice(i * width, (i + 1) * width) for i in range(3))
         if table is None:
-            out = ops.attention(tape, q, k, v, self.num_heads, self.scale)
+            out = ops.attention(tape, q, k, v, self.num_heads, self.scale, f16=self.fp16_attention)
         else:
-            out = ops.attention_relpos(tape, q, k, v, self.num_heads, self.scale, table, window)
+            out = ops.attention_relpos(tape, q, k, v, self.num_heads, self.scale, table, window,
+                                       f16=self.fp16_attention)
         return self.proj.forward_act(tape, out)
 
 
@@ -249,6 +252,20 @@ def _run(tape, module, x):
 @BACKBONES.register_module()
 class BEiT(nn.Module):
     """Vision transformer with BEiT's relative-position bias and a four-level pyramid on top."""
+    _fp16_attention = False
+
+    @property
+    def fp16_attention(self):
+        """Opt-in, as ElasticTransformer.fp16_attention: inside an fp16 mode every attention runs on the
+        fp16-operand kernels (the bias stays fp32)."""
+        return self._fp16_attention
+
+    @fp16_attention.setter
+    def fp16_attention(self, flag):
+        self._fp16_attention = bool(flag)
+        for m in self.modules():
+            if isinstance(m, Attention):
+                m.fp16_attention = self._fp16_attention
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=80, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0.,

@@ -82,6 +82,7 @@ class ElasticRelativePosition2D(nn.Module, DynamicMixin):
 class ElasticMHA(nn.Module, DynamicMixin):
     """x + proj(softmax(scale * Q K^T) V) with ``num_heads`` active heads of width 64."""
     search_space = {"num_heads"}
+    fp16_attention = False   # set through ElasticTransformer.fp16_attention
 
     def __init__(self, embed_dim, num_heads, proj_drop=0.0, attn_drop=0.0, drop_path=0.1,
                  relative_position=False, max_relative_position=14):
@@ -120,7 +121,7 @@ class ElasticMHA(nn.Module, DynamicMixin):
         self.w_qs.forward_act(tape, x, out=q)
         self.w_ks.forward_act(tape, x, out=k)
         self.w_vs.forward_act(tape, x, out=v)
-        out = ops.attention(tape, q, k, v, self.num_heads, self.scale)
+        out = ops.attention(tape, q, k, v, self.num_heads, self.scale, f16=self.fp16_attention)
         self.proj.manipulate_width(residual.C)
         out = self.proj.forward_act(tape, out)
         return ops.layer_scale_add(tape, residual, out, None)
@@ -272,6 +273,7 @@ class ElasticTransformer(nn.Module, DynamicMixin):
     """Vision transformer with an elastic embedding width and, per encoder group, elastic depth, head
     count and feed-forward ratio."""
     search_space = {"embedding", "encoder"}
+    _fp16_attention = False
 
     def __init__(self, embed_dim, num_heads, feedforward_channels, num_layers, patch_size=16, img_size=224,
                  in_channels=3, attn_drop=0.0, proj_drop=0.0, drop_rate=0.0, drop_path=0.1,
@@ -315,6 +317,20 @@ class ElasticTransformer(nn.Module, DynamicMixin):
         self.init_weights(pretrained)
 
     norm1 = property(lambda self: getattr(self, self.norm1_name))
+
+    @property
+    def fp16_attention(self):
+        """Opt-in (core.fp16_utils.wrap_fp16_model(model, attention=True); ``fp16 = dict(attention=True)``
+        in a config): inside an fp16 mode every attention runs on the fp16-operand kernels
+        (ops.attention(f16=True)).  Without an fp16 mode the flag does nothing."""
+        return self._fp16_attention
+
+    @fp16_attention.setter
+    def fp16_attention(self, flag):
+        self._fp16_attention = bool(flag)
+        for m in self.modules():
+            if isinstance(m, ElasticMHA):
+                m.fp16_attention = self._fp16_attention
 
     def make_encoder(self, **kwargs):
         return ElasticEncoder(**kwargs)

@@ -271,6 +271,29 @@ size_t gs_attention_workspace_bytes(const gs_attention_desc* d);
 int gs_attention_backward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
                           const float* o, const float* lse, const float* d_o, float* dq, float* dk,
                           float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* The opt-in fp16-operand twins of the four entries above (csrc/attention_f16.hip): same descriptor, same
+ * arguments, same host-side checks and error codes, same padding rules, fp32 in memory, no float atomics,
+ * bit-identical from run to run -- but every product runs on v_mfma_f32_32x32x16_f16 with fp32
+ * accumulation, so they are NOT fp32-accurate: Q, K, V and dO are rounded to fp16 once where they are
+ * staged; the scores, the relative-position bias, the running maximum, the row sum, lse and delta stay
+ * fp32; exp(S - m) is rounded to fp16 only as the operand of the P V product (the row sum adds the fp32
+ * values); the backward recomputes S with the forward's instruction and k order and rounds exp(S - lse) and
+ * dS = P (dP - delta) to fp16 as operands.  The backward is invariant to a power-of-two scale of dO (a
+ * loss scale): its pre-pass records max|dO| per workgroup beside delta, every product runs on dO * 2^e with
+ * 2^e max|dO| in [4, 8), and the results are multiplied by 2^-e at the store; dO == 0 gives exact zeros;
+ * the conversion of dS saturates at the fp16 maximum.  lse of gs_attention_forward_f16 is what
+ * gs_attention_backward_f16 expects (a pair: do not mix with the fp32 entries).  A zero table gives the
+ * bits of gs_attention_forward_f16.  The workspace is delta[B][heads][N] followed by the
+ * B * heads * ceil(N / 128) maxima.  Error bounds and the protocol that tests them: DESIGN.md section 32. */
+int gs_attention_forward_f16(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+                             float* o, float* lse, void* stream);
+int gs_attention_relpos_forward_f16(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+                                    const float* table, int32_t ld_table, int32_t Wh, int32_t Ww, float* o,
+                                    float* lse, void* stream);
+size_t gs_attention_workspace_bytes_f16(const gs_attention_desc* d);
+int gs_attention_backward_f16(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+                              const float* o, const float* lse, const float* d_o, float* dq, float* dk,
+                              float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 /* ElasticTransformer's token assembly on the leading D columns: from patches [B*T][D] (pitch ldp),
  * cls_token[:D] and pos_embed[:T+1, :D] (pitch ldpos, the max-size embedding width),
  *   x[b,0,:] = cls_token + pos_embed[0],   x[b,1+t,:] = patches[b,t] + pos_embed[1+t]      (x: [B*(T+1)][D]).
