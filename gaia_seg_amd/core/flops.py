@@ -12,7 +12,11 @@ For the ElasticTransformer the patch embedding is a conv, every linear counts as
 tokens of an image (cls row included), and self-attention counts 4 * N^2 * 64 * heads per layer and image:
 the two matrix products Q K^T and P V at 2 * N^2 * 64 FLOPs per head each.  The softmax (O(N^2) exponentials,
 no multiply-add pairs), LayerNorm, GELU and the residual adds count 0.  A DynamicMultiLevelNeck counts its
-1x1 and 3x3 convs at the resolutions they run at (key 'neck' of model_flops); the resizes count 0."""
+1x1 and 3x3 convs at the resolutions they run at (key 'neck' of model_flops); the resizes count 0.
+
+The ElasticConvformer follows both conventions: its bottlenecks, projections and patch embedding are convs,
+its transformer blocks count as the ElasticTransformer's; the coupling units' LayerNorm, GELU, pooling,
+upsample and adds count 0, and the conv-to-token projection counts on the pooled map it runs on."""
 from ..hip.ops import conv_out_size
 from .bricks import DynamicConv2d
 
@@ -86,6 +90,65 @@ def vit_backbone_flops(backbone, h, w, in_channels=3):
     return total, params, 0.0, feats
 
 
+def _trans_block(blk, n, d):
+    """(flops per image, params) of an Elastic_trans_Block on n tokens of width d"""
+    heads = blk.attn.num_heads
+    hw, hidden = 64 * heads, blk.mlp.layer1.width_state
+    total, params = attention_flops(n, heads), 4 * d       # ln1, ln2
+    for cin, cout, count in ((d, hw, 3), (hw, d, 1), (d, hidden, 1), (hidden, d, 1)):
+        total += count * 2.0 * n * cin * cout
+        params += count * (cin * cout + cout)
+    return total, params
+
+
+def _conv_block(blk, c, h, w):
+    """(flops, params, flops of the 3x3, output width, height, width) of an Elastic_conv_Block"""
+    f1, p1, c1, _, _ = _conv(blk.conv1, c, h, w)
+    f2, p2, c2, h2, w2 = _conv(blk.conv2, c1, h, w)
+    f3, p3, c3, _, _ = _conv(blk.conv3, c2, h2, w2)
+    total, params = f1 + f2 + f3, p1 + p2 + p3 + 2 * (c1 + c2 + c3)
+    if blk.res_conv:
+        fr, pr, cr, _, _ = _conv(blk.residual_conv, c, h, w)
+        total += fr
+        params += pr + 2 * cr
+    return total, params, f2, c3, h2, w2
+
+
+def convformer_backbone_flops(backbone, h, w, in_channels=3):
+    """backbone_flops for an ElasticConvformer: (flops per image, params, flops of the 3x3 convs, feature
+    shapes).  Convs and linears count, attention counts 4 * N^2 * 64 * heads; norms, GELU, pooling, the
+    upsample and the adds count 0.  The conv-to-token projection is counted on the POOLED map, as it is
+    executed.  Params are those of the active subnet's used parameters."""
+    f, p, c, h, w = _conv(backbone.conv1, in_channels, h, w)
+    total, params, k3 = f, p + 2 * c, 0.0
+    mp = backbone.maxpool
+    h = (h + 2 * mp.padding - mp.kernel_size) // mp.stride + 1
+    w = (w + 2 * mp.padding - mp.kernel_size) // mp.stride + 1
+    feats, n, d = [], None, None
+    for name in backbone.layers:
+        for blk in getattr(backbone, name).active_blocks():
+            if blk.stage:
+                fp, pp, d, hp, wp = _conv(blk.trans_patch_conv, c, h, w)
+                n = hp * wp + 1
+                ft, pt = _trans_block(blk.trans_1, n, d)
+                fc, pc, f3, c, h, w = _conv_block(blk.conv_1, c, h, w)
+                total += fp + ft + fc
+                params += pp + pt + pc + d                  # + cls_token
+                k3 += f3
+                continue
+            fc, pc, f3, c, h, w = _conv_block(blk.cnn_block, c, h, w)
+            s, med = blk.dw_stride, blk.cnn_block.conv2.width_state
+            fs, ps, _, _, _ = _conv(blk.squeeze_block.conv_project, med, h // s, w // s)
+            ft, pt = _trans_block(blk.trans_block, n, d)
+            fe, pe, ce, _, _ = _conv(blk.expand_block.conv_project, d, h // s, w // s)
+            ff, pf, f3f, c, h, w = _conv_block(blk.fusion_block, c, h, w)
+            total += fc + fs + ft + fe + ff
+            params += pc + ps + 2 * d + pt + pe + 2 * ce + pf
+            k3 += f3 + f3f
+        feats.append((c, h, w))
+    return total, params, k3, feats
+
+
 def neck_flops(neck, feats):
     """DynamicMultiLevelNeck: (flops per image, feature shapes after the neck)"""
     from ..models.necks.dynamic_multilevel_neck import scaled_size
@@ -111,6 +174,8 @@ def backbone_flops(backbone, h, w, in_channels=3):
         return convnext_backbone_flops(backbone, h, w, in_channels)
     if type(backbone).__name__ == "ElasticTransformer":
         return vit_backbone_flops(backbone, h, w, in_channels)
+    if type(backbone).__name__ == "ElasticConvformer":
+        return convformer_backbone_flops(backbone, h, w, in_channels)
     total = params = k3 = 0.0
     c = in_channels
     if backbone.deep_stem:

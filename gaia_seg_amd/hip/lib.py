@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class HipLibraryError(RuntimeError):
@@ -111,6 +111,23 @@ def attention_desc(b, n, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=None, ldk=
     d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
                                       ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
     return d
+
+
+class FcuDownDesc(Structure):
+    """Mirror of ``gs_fcu_down_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("B", "T", "D", "ldz", "ldxt", "ldo", "lddz", "lddxt")]
+                + [("eps", c_float)])
+
+
+def fcu_down_desc(b, t, d, eps=1e-6, ldz=None, ldxt=None, ldo=None, lddz=None, lddxt=None):
+    """A ``FcuDownDesc`` for ``b`` images of ``t`` tokens (+ the cls row) of width ``d``; a forward pitch
+    defaults to d, a gradient's pitch to the pitch of its forward operand."""
+    desc = FcuDownDesc()
+    desc.B, desc.T, desc.D, desc.eps = b, t, d, eps
+    desc.ldz, desc.ldxt, desc.ldo = (d if v is None else v for v in (ldz, ldxt, ldo))
+    desc.lddz = desc.ldz if lddz is None else lddz
+    desc.lddxt = desc.ldxt if lddxt is None else lddxt
+    return desc
 
 
 class BnArgs(Structure):
@@ -260,6 +277,7 @@ _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 _DW = POINTER(DwConvDesc)
 _LN = POINTER(LayerNormDesc)
 _AT = POINTER(AttentionDesc)
+_FD = POINTER(FcuDownDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -295,6 +313,13 @@ PROTOTYPES = {
     "gs_attention_backward_f16": (_i32, [_AT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
     "gs_vit_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_vit_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
+    "gs_fcu_down_workspace_bytes": (_sz, [_FD]),
+    "gs_fcu_down_forward": (_i32, [_FD, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_fcu_down_backward": (_i32, [_FD, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_fcu_up_add_forward": (_i32, [_P, _P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
+    "gs_fcu_up_add_backward": (_i32, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
+    "gs_fcu_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
+    "gs_fcu_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _i32, _i32, _i32, _P]),
     "gs_colsum_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_colsum": (_i32, [_P, _i64, _i32, _i32, _P, _P, _sz, _P]),
     "gs_bn_stats_workspace_bytes": (_sz, [_i64, _i32]),

@@ -1094,6 +1094,130 @@ def vit_feature_map(tape, x, hp, wp):
     return out
 
 
+def fcu_tokens(tape, patches, cls_token):
+    """ElasticConvformer's token assembly: vit_tokens without a position embedding.  From the patch
+    embedding [B, Hp, Wp, D] and the max-size ``cls_token`` [1, 1, D_max] the token activation
+    [B, 1, 1 + Hp*Wp, D] with x[b, 0] = cls[:D] and x[b, 1 + t] = patch[b, t]."""
+    L = _L()
+    patches = materialize(tape, patches)
+    b, t, dch, dev = patches.N, patches.H * patches.W, patches.C, patches.t.device
+    if dch % 4:
+        raise ValueError("fcu_tokens needs an embedding width that is a multiple of 4, got %d" % dch)
+    if dch > cls_token.shape[-1]:
+        raise ValueError("fcu_tokens: width %d exceeds cls_token %s" % (dch, tuple(cls_token.shape)))
+    out = Act.empty(b, 1, t + 1, dch, dev)
+    _lib.check(L.gs_fcu_tokens_forward(patches.ptr, patches.ld, cls_token.data_ptr(), out.ptr, out.ld, b, t,
+                                       dch, current_stream_ptr()), "gs_fcu_tokens_forward")
+
+    def backward():
+        dx = out.g
+        if dx is None:
+            return
+        gc = _param_grad(cls_token, dch, dev)
+        if patches.requires_grad:
+            if _input_grad(patches):
+                raise RuntimeError("patch embedding has more than one consumer; unsupported")
+            dp = patches.g
+        else:
+            dp = torch.empty_like(patches.t)
+        _lib.check(L.gs_fcu_tokens_backward(dx.data_ptr(), dx.stride(2), dp.data_ptr(), dp.stride(2),
+                                            gc.data_ptr(), b, t, dch, current_stream_ptr()),
+                   "gs_fcu_tokens_backward")
+        if cls_token.requires_grad:
+            _notify(cls_token)
+
+    tape.record(backward)
+    return out
+
+
+def fcu_down(tape, z, x_t, ln):
+    """ElasticConvformer's conv-to-token unit behind its pooling and projection, with the add of the token
+    stream: from the projected map ``z`` [B, Hc, Wc, D], the tokens ``x_t`` [B, 1, 1 + Hc*Wc, D] and the DynLN
+    module ``ln`` (leading D of its parameters),
+        out[b, 0] = x_t[b, 0] + x_t[b, 0],   out[b, 1 + t] = x_t[b, 1 + t] + GELU(LN(z[b, t])),
+    one kernel (gs_fcu_down_forward).  The backward recomputes the GELU input; x_t has other consumers (its
+    gradient accumulates), z has this one."""
+    L = _L()
+    z, x_t = materialize(tape, z), materialize(tape, x_t)
+    weight, bias = ln.weight, ln.bias
+    c = _active_width(z, weight, "fcu_down")
+    b, t, dev = z.N, z.H * z.W, z.t.device
+    if (x_t.N, x_t.H, x_t.W, x_t.C) != (b, 1, t + 1, c):
+        raise ValueError("fcu_down: tokens %s do not belong to the map %s"
+                         % (tuple(x_t.t.shape), tuple(z.t.shape)))
+    out = Act.empty(b, 1, t + 1, c, dev)
+    stats = torch.empty(2 * b * t, dtype=torch.float32, device=dev)
+    mean_ptr, rstd_ptr = stats.data_ptr(), stats.data_ptr() + 4 * b * t
+    d = _lib.fcu_down_desc(b, t, c, ln.eps, ldz=z.ld, ldxt=x_t.ld, ldo=out.ld)
+    _lib.check(L.gs_fcu_down_forward(ctypes.byref(d), z.ptr, x_t.ptr, weight.data_ptr(), bias.data_ptr(),
+                                     out.ptr, mean_ptr, rstd_ptr, current_stream_ptr()), "gs_fcu_down_forward")
+
+    def backward():
+        dout = out.g
+        if dout is None:
+            return
+        keep = stats  # noqa: F841 -- the closure owns the storage behind mean_ptr / rstd_ptr
+        gw, gb = _param_grad(weight, c, dev), _param_grad(bias, c, dev)
+        if z.requires_grad:
+            if _input_grad(z):
+                raise RuntimeError("fcu_down: the projected map has more than one consumer; unsupported")
+            dz = z.g
+        else:
+            dz = torch.empty_like(z.t)
+        if x_t.requires_grad:
+            acc = _input_grad(x_t)
+            dxt = x_t.g
+        else:
+            acc, dxt = 0, torch.empty_like(x_t.t)
+        d.ldo, d.lddz, d.lddxt = dout.stride(2), dz.stride(2), dxt.stride(2)
+        db = ctypes.byref(d)
+        ws = _ws.get(L.gs_fcu_down_workspace_bytes(db), dev)
+        _lib.check(L.gs_fcu_down_backward(db, z.ptr, dout.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                          mean_ptr, rstd_ptr, dz.data_ptr(), dxt.data_ptr(), gw.data_ptr(),
+                                          gb.data_ptr(), acc, ws.data_ptr(), ws.numel(), current_stream_ptr()),
+                   "gs_fcu_down_backward")
+        if weight.requires_grad:
+            _notify(weight)
+        if bias.requires_grad:
+            _notify(bias)
+
+    tape.record(backward)
+    return out
+
+
+def fcu_up_add(tape, x, r, s):
+    """ElasticConvformer's token-to-conv unit behind its projection, with the add in front of the 3x3
+    conv: x + nearest_upsample(r, s) for x [B, H, W, C] and r [B, H/s, W/s, C], one kernel.  Both inputs are
+    written out first where their BatchNorm was deferred.  The gradient of x is the output's, handed on
+    without a copy; r's is the ordered sum over its s x s blocks."""
+    L = _L()
+    x, r = materialize(tape, x), materialize(tape, r)
+    c, dev = x.C, x.t.device
+    if s < 1 or (r.N, r.H * s, r.W * s, r.C) != (x.N, x.H, x.W, c):
+        raise ValueError("fcu_up_add: %s is not %s upsampled by %s" % (tuple(x.t.shape), tuple(r.t.shape), s))
+    if c % 4:
+        raise ValueError("fcu_up_add needs a channel count that is a multiple of 4, got %d" % c)
+    out = Act.empty(x.N, x.H, x.W, c, dev)
+    _lib.check(L.gs_fcu_up_add_forward(x.ptr, r.ptr, out.ptr, x.N, x.H, x.W, c, s, x.ld, r.ld, out.ld,
+                                       current_stream_ptr()), "gs_fcu_up_add_forward")
+
+    def backward():
+        dout = out.g
+        if dout is None:
+            return
+        st = current_stream_ptr()
+        if r.requires_grad:
+            acc = _input_grad(r)
+            _lib.check(L.gs_fcu_up_add_backward(dout.data_ptr(), r.g.data_ptr(), x.N, x.H, x.W, c, s,
+                                                dout.stride(2), r.g.stride(2), acc, st),
+                       "gs_fcu_up_add_backward")
+        if x.requires_grad:
+            _pass_residual_grad(L, x, dout, x.rows, c, st)
+
+    tape.record(backward)
+    return out
+
+
 def _input_grad(x):
     """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
     x.g already held a contribution, else 0 after allocating it (a channel slice's storage is

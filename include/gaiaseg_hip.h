@@ -307,6 +307,56 @@ int gs_vit_tokens_backward(const float* dx, int32_t lddx, float* dpatches, int32
                            float* dpos_embed, int32_t ldpos, int32_t B, int32_t T, int32_t D, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* ElasticConvformer: the coupling units between the conv branch and the token stream           */
+/* ------------------------------------------------------------------------------------------ */
+/* All on fp32 "rows x C" views as the ConvNeXt operators above: a pitch >= the width per operand,
+ * parameters sliced to their leading columns, fp32 in every precision mode, arguments checked on the host
+ * before any launch (GS_E_NULL, GS_E_BADARG for a size <= 0, a pitch below the width, eps <= 0 or an s that
+ * does not divide H and W, GS_E_ALIGN for a width or pitch no multiple of 4 or a tensor pointer not
+ * 16-byte aligned, GS_E_WORKSPACE).  No float atomics; every sum has a fixed order.
+ *
+ * Conv features to tokens (Elastic_conv2trans after its pooling and projection, and the `x_st + x_t` of
+ * Elastic_ConvTrans_Block.forward, gaiaseg/models/backbones/elastic_convformer.py).  z is [B*T][D], the
+ * token stream x_t and out are [B*(T+1)][D] with the cls row in front of every image:
+ *   out[b,0,:]   = x_t[b,0,:] + x_t[b,0,:]
+ *   out[b,1+t,:] = x_t[b,1+t,:] + gelu(LN(z[b,t,:]) * weight + bias)            (exact-erf GELU)
+ * mean and rstd are [B*T] and are saved for the backward. */
+typedef struct gs_fcu_down_desc {
+  int32_t B, T, D;          /* images, tokens per image without the cls row, ACTIVE width        */
+  int32_t ldz, ldxt, ldo;   /* pitches of z, of x_t and of out / dout                            */
+  int32_t lddz, lddxt;      /* pitches of dz and of dx_t (all five are always checked)           */
+  float eps;
+} gs_fcu_down_desc;
+int gs_fcu_down_forward(const gs_fcu_down_desc* d, const float* z, const float* x_t, const float* weight,
+                        const float* bias, float* out, float* mean, float* rstd, void* stream);
+/* bytes of scratch gs_fcu_down_backward needs (0 for a descriptor it would refuse): one [2][D] partial
+ * per run of 256 rows of z. */
+size_t gs_fcu_down_workspace_bytes(const gs_fcu_down_desc* d);
+/* From dout [B*(T+1)][D]: dx_t (= or +=, accumulate_dx_t != 0 adds) dout on token rows and 2 dout on cls
+ * rows; dz the gradient through the GELU and the LayerNorm, the GELU input recomputed from z, mean and
+ * rstd; dweight[:D] / dbias[:D] through per-run partials and their ordered sum (columns D.. are never
+ * written).  dx_t may be dout's buffer. */
+int gs_fcu_down_backward(const gs_fcu_down_desc* d, const float* z, const float* dout, const float* weight,
+                         const float* bias, const float* mean, const float* rstd, float* dz, float* dx_t,
+                         float* dweight, float* dbias, int accumulate_dx_t, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* Tokens to conv features (the F.interpolate of Elastic_trans2conv, nearest with an integer factor, and the
+ * `x + x_t` in front of conv2 of Elastic_conv_Block):  out[b,y,x,:C] = x[b,y,x,:C] + r[b,y/s,x/s,:C] with
+ * x, out [B][H][W] and r [B][H/s][W/s]; s >= 1 divides H and W.  out may be x's buffer. */
+int gs_fcu_up_add_forward(const float* x, const float* r, float* out, int32_t B, int32_t H, int32_t W,
+                          int32_t C, int32_t s, int32_t ldx, int32_t ldr, int32_t ldo, void* stream);
+/* dr[b,i,j,:C] (= or +=) the sum of dout over the s x s block of (i, j), rows first, then columns (s == 1:
+ * dout itself).  H, W are the sizes of dout.  The gradient of x is dout. */
+int gs_fcu_up_add_backward(const float* dout, float* dr, int32_t B, int32_t H, int32_t W, int32_t C,
+                           int32_t s, int32_t lddo, int32_t lddr, int accumulate, void* stream);
+/* The token assembly without a position embedding:  x[b,0,:D] = cls_token[:D],  x[b,1+t,:D] = patches[b,t]
+ * (x: [B*(T+1)][D]); dpatches[b,t] = dx[b,1+t], dcls_token[:D] = sum_b dx[b,0] in the order of b. */
+int gs_fcu_tokens_forward(const float* patches, int32_t ldp, const float* cls_token, float* x, int32_t ldx,
+                          int32_t B, int32_t T, int32_t D, void* stream);
+int gs_fcu_tokens_backward(const float* dx, int32_t lddx, float* dpatches, int32_t lddp, float* dcls_token,
+                           int32_t B, int32_t T, int32_t D, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Dynamic BatchNorm (+ residual add, + ReLU) — K4, K8                                         */
 /* ------------------------------------------------------------------------------------------ */
 /* Replaces F.batch_norm on the leading C-slice of max-size parameters (gaiavision DynBN /
