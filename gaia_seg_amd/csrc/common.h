@@ -2,6 +2,7 @@
 // (MI355X only: 64-lane waves, 256 CUs in 8 XCDs; no other target is supported.)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <type_traits>
 #include <stdint.h>
 #include "gaiaseg_hip.h"
@@ -10,6 +11,8 @@ namespace gs {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 constexpr int kWave = 64;      // CDNA wavefront
 constexpr int kNumCUDefault = 256;   // MI355X (8 XCDs x 32 CUs)
@@ -39,6 +42,17 @@ inline int launch_status() {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// An entry's pointer list: `if (any_null({a, b, c})) return GS_E_NULL;` and the same for the alignment.
+inline bool any_null(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (!p) return true;
+  return false;
+}
+inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (!aligned16(p)) return false;
+  return true;
+}
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

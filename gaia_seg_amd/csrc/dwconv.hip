@@ -36,9 +36,6 @@ struct DwStencil {
   int32_t flip, accumulate, strips;
 };
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-
 __global__ __launch_bounds__(256) void dw_stencil_kernel(const DwStencil a, const float* __restrict__ in,
                                                          const float* __restrict__ w,
                                                          const float* __restrict__ bias,

@@ -19,8 +19,6 @@ constexpr int kColQuads = 16;     // channel quads per column-reduction workgrou
 constexpr int kColLanes = 16;     // row lanes per column-reduction workgroup
 constexpr int kRunRows = 256;     // rows per stage-1 workgroup (16 per lane)
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ float hsum(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
 
 // sum over the G lanes of a group (G a power of two <= 64, groups aligned to G): every lane gets it

@@ -904,6 +904,25 @@ def _attention_f16(f16):
                           or _L().gs_get_train_precision() == _lib.PRECISION_FP16)
 
 
+def _attention_setup(tape, what, q, k, v, heads, scale, out, f16):
+    """What ``attention`` and ``attention_relpos`` (``what``) share -> (q, k, v, out, lse, descriptor, suffix
+    of the entries to call): q, k and v materialised and checked to be [B, 1, N, 64 * heads], the output and
+    the log-sum-exp buffer allocated."""
+    sfx = "_f16" if _attention_f16(f16) else ""
+    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
+    c = _lib.ATTENTION_HEAD_DIM * heads
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.C != c or t.rows != q.rows or t.H != 1:
+            raise ValueError("%s: %s is %s, expected [B, 1, N, %d] for %d heads"
+                             % (what, name, tuple(t.t.shape), c, heads))
+    b, n, dev = q.N, q.W, q.t.device
+    if out is None:
+        out = Act.empty(b, 1, n, c, dev)
+    lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
+    d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    return q, k, v, out, lse, d, sfx
+
+
 def attention(tape, q, k, v, heads, scale, out=None, f16=False):
     """Multi-head softmax self-attention, head dimension 64: ``heads`` active heads in the leading
     64 * heads columns of q, k and v (token activations [B, 1, N, 64 * heads], each with its own pitch: three
@@ -911,20 +930,10 @@ def attention(tape, q, k, v, heads, scale, out=None, f16=False):
     kept for the backward, which recomputes the probabilities.  ``f16`` (opt-in, honoured only in an fp16
     mode): fp16 MFMA operands with fp32 accumulation, forward and backward."""
     L = _L()
-    sfx = "_f16" if _attention_f16(f16) else ""
+    q, k, v, out, lse, d, sfx = _attention_setup(tape, "attention", q, k, v, heads, scale, out, f16)
     fwd, bwd = getattr(L, "gs_attention_forward" + sfx), getattr(L, "gs_attention_backward" + sfx)
     ws_bytes = getattr(L, "gs_attention_workspace_bytes" + sfx)
-    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
-    c = _lib.ATTENTION_HEAD_DIM * heads
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.C != c or t.rows != q.rows or t.H != 1:
-            raise ValueError("attention: %s is %s, expected [B, 1, N, %d] for %d heads"
-                             % (name, tuple(t.t.shape), c, heads))
-    b, n, dev = q.N, q.W, q.t.device
-    if out is None:
-        out = Act.empty(b, 1, n, c, dev)
-    lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
-    d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    dev = q.t.device
     _lib.check(fwd(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), current_stream_ptr()),
                "gs_attention_forward" + sfx)
 
@@ -960,14 +969,8 @@ def attention_relpos(tape, q, k, v, heads, scale, table, window, out=None, f16=F
     (fp32, any row pitch), ``window`` = (Wh, Ww), N = Wh * Ww + 1 tokens with the cls token first.  The
     kernel gathers from the table: no N x N bias exists.  ``f16`` as for ``attention``; the bias stays fp32."""
     L = _L()
-    sfx = "_f16" if _attention_f16(f16) else ""
     _forward_only(tape, "attention_relpos", q, k, v, table)
-    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
-    c = _lib.ATTENTION_HEAD_DIM * heads
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        if t.C != c or t.rows != q.rows or t.H != 1:
-            raise ValueError("attention_relpos: %s is %s, expected [B, 1, N, %d] for %d heads"
-                             % (name, tuple(t.t.shape), c, heads))
+    q, k, v, out, lse, d, sfx = _attention_setup(tape, "attention_relpos", q, k, v, heads, scale, out, f16)
     wh, ww = window
     rows = (2 * wh - 1) * (2 * ww - 1) + 3
     if table.dim() != 2 or table.shape[0] != rows or table.shape[1] < heads or table.stride(1) != 1:
@@ -976,11 +979,6 @@ def attention_relpos(tape, q, k, v, heads, scale, table, window, out=None, f16=F
     if rows > _lib.ATTENTION_RELPOS_MAX_ROWS:
         raise ValueError("attention_relpos: a %d x %d window needs %d table rows, the kernel stages at most "
                          "%d in LDS" % (wh, ww, rows, _lib.ATTENTION_RELPOS_MAX_ROWS))
-    b, n, dev = q.N, q.W, q.t.device
-    if out is None:
-        out = Act.empty(b, 1, n, c, dev)
-    lse = torch.empty(b * heads * n, dtype=torch.float32, device=dev)
-    d = _lib.attention_desc(b, n, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
     _lib.check(getattr(L, "gs_attention_relpos_forward" + sfx)(
         ctypes.byref(d), q.ptr, k.ptr, v.ptr, table.data_ptr(), table.stride(0), wh, ww, out.ptr,
         lse.data_ptr(), current_stream_ptr()), "gs_attention_relpos_forward" + sfx)

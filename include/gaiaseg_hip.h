@@ -271,7 +271,8 @@ size_t gs_attention_workspace_bytes(const gs_attention_desc* d);
 int gs_attention_backward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
                           const float* o, const float* lse, const float* d_o, float* dq, float* dk,
                           float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
-/* The opt-in fp16-operand twins of the four entries above (csrc/attention_f16.hip): same descriptor, same
+/* The opt-in fp16-operand twins of the four entries above (csrc/attention_f16.hip: the same kernel
+ * templates of csrc/attention_common.h on another operand format): same descriptor, same
  * arguments, same host-side checks and error codes, same padding rules, fp32 in memory, no float atomics,
  * bit-identical from run to run -- but every product runs on v_mfma_f32_32x32x16_f16 with fp32
  * accumulation, so they are NOT fp32-accurate: Q, K, V and dO are rounded to fp16 once where they are

@@ -17,74 +17,16 @@ from conftest import rel_err
 import util_attention_f16 as W
 import util_beit as B
 import util_vit as U
-from test_attention_gpu import (DEV, GS_E_ALIGN, GS_E_BADARG, GS_E_NULL, GS_E_WORKSPACE, NAN, SENTINEL, Workspace,
-                                active, padded, stream)
-from test_beit_ops_gpu import RELPOS_CASES, make_table
+from util_attention_gpu import (DEV, GS_E_ALIGN, GS_E_BADARG, GS_E_NULL, GS_E_WORKSPACE, NAMES, RELPOS_CASES,
+                                SENTINEL, make_table, stream)
+import util_attention_gpu as A
 
 pytestmark = pytest.mark.gpu
 SEED = 1
-NAMES = ("O", "lse", "dQ", "dK", "dV", "dQ+", "dK+", "dV+")
 
 
 def run_attention(L, lib, b, n, heads, sliced, q, k, v, do, bases, sfx="_f16", scale=U.SCALE):
-    """test_attention_gpu.run_attention on the entries with suffix ``sfx``: forward, backward (overwrite),
-    backward (accumulate onto the bases) -> (O, lse, dQ, dK, dV, dQ+, dK+, dV+)"""
-    fwd, bwd = getattr(L, "gs_attention_forward" + sfx), getattr(L, "gs_attention_backward" + sfx)
-    ws_bytes = getattr(L, "gs_attention_workspace_bytes" + sfx)
-    c = 64 * heads
-    if sliced:
-        hw, ldo = 64 * 4, c + 24
-        qkv = torch.full((b, n, 3 * hw), NAN)
-        for i, t in enumerate((q, k, v)):
-            qkv[..., i * hw:i * hw + c] = t
-        qkv = qkv.to(DEV)
-        ptrs = [qkv.data_ptr() + 4 * i * hw for i in range(3)]
-        ldq = 3 * hw
-        keep = [qkv]
-    else:
-        ldo = ldq = c
-        keep = [t.contiguous().to(DEV) for t in (q, k, v)]
-        ptrs = [t.data_ptr() for t in keep]
-    d = lib.attention_desc(b, n, heads, scale, ldq=ldq, ldk=ldq, ldv=ldq, ldo=ldo)
-    db, st = ctypes.byref(d), stream()
-    o = torch.full((b, n, ldo), SENTINEL, device=DEV)
-    lse = torch.full((b * heads * n + 8,), SENTINEL, device=DEV)
-    lib.check(fwd(db, ptrs[0], ptrs[1], ptrs[2], o.data_ptr(), lse.data_ptr(), st), "fwd")
-    o_got = active(o, 0, c, "O")
-    lse_cpu = lse.cpu()
-    assert bool((lse_cpu[b * heads * n:] == SENTINEL).all()), "lse: a store past [B][heads][N]"
-    lse_got = lse_cpu[:b * heads * n].view(b, heads, n)
-    dog = padded(do, ldo, NAN)
-    outs = []
-    for accumulate in (0, 1):
-        if sliced:   # the three gradients as slices of one buffer, like the operands
-            g = torch.full((b, n, 3 * hw), SENTINEL)
-            if accumulate:
-                for i, t in enumerate(bases):
-                    g[..., i * hw:i * hw + c] = t
-            g = g.to(DEV)
-            gptrs = [g.data_ptr() + 4 * i * hw for i in range(3)]
-            c0s = [0, hw, 2 * hw]
-        else:
-            gbufs = [(bases[i].contiguous().to(DEV) if accumulate else torch.full((b, n, c), SENTINEL, device=DEV))
-                     for i in range(3)]
-            gptrs = [t.data_ptr() for t in gbufs]
-        ws = Workspace(ws_bytes(db))
-        lib.check(bwd(db, ptrs[0], ptrs[1], ptrs[2], o.data_ptr(), lse.data_ptr(), dog.data_ptr(), gptrs[0],
-                      gptrs[1], gptrs[2], accumulate, ws.ptr(), ws.need, st), "bwd")
-        ws.check()
-        if sliced:
-            full = g.cpu()
-            outside = torch.ones_like(full, dtype=torch.bool)
-            for c0 in c0s:
-                outside[..., c0:c0 + c] = False
-            assert bool((full[outside] == SENTINEL).all()), "a gradient store outside the active columns"
-            got = [full[..., c0:c0 + c].contiguous() for c0 in c0s]
-        else:
-            got = [t.cpu() for t in gbufs]
-        outs += got
-    del keep
-    return (o_got, lse_got) + tuple(outs)
+    return A.run_attention(L, lib, b, n, heads, sliced, q, k, v, do, bases, sfx=sfx, scale=scale)
 
 
 def check_budget(name, names, got, wit, want, norm=None):
@@ -186,40 +128,7 @@ def test_gradient_scale_invariance(hip_lib):
 
 
 def run_relpos(L, lib, b, wh, ww, heads, sliced, q, k, v, table):
-    """test_beit_ops_gpu.run_relpos on the fp16 entries: ``table`` None runs gs_attention_forward_f16"""
-    n, c = wh * ww + 1, 64 * heads
-    if sliced:
-        hw, ldo, ldt = 64 * 4, c + 24, heads + 1
-        qkv = torch.full((b, n, 3 * hw), NAN)
-        for i, t in enumerate((q, k, v)):
-            qkv[..., i * hw:i * hw + c] = t
-        keep = [qkv.to(DEV)]
-        ptrs = [keep[0].data_ptr() + 4 * i * hw for i in range(3)]
-        ldq = 3 * hw
-    else:
-        ldo = ldq = c
-        ldt = heads
-        keep = [t.contiguous().to(DEV) for t in (q, k, v)]
-        ptrs = [t.data_ptr() for t in keep]
-    d = lib.attention_desc(b, n, heads, U.SCALE, ldq=ldq, ldk=ldq, ldv=ldq, ldo=ldo)
-    o = torch.full((b, n, ldo), SENTINEL, device=DEV)
-    lse = torch.full((b * heads * n + 8,), SENTINEL, device=DEV)
-    if table is None:
-        lib.check(L.gs_attention_forward_f16(ctypes.byref(d), ptrs[0], ptrs[1], ptrs[2], o.data_ptr(),
-                                             lse.data_ptr(), stream()), "plain forward")
-    else:
-        tg = torch.full((table.shape[0], ldt), NAN)
-        tg[:, :heads] = table
-        tg = tg.to(DEV)
-        lib.check(L.gs_attention_relpos_forward_f16(ctypes.byref(d), ptrs[0], ptrs[1], ptrs[2], tg.data_ptr(), ldt,
-                                                    wh, ww, o.data_ptr(), lse.data_ptr(), stream()), "relpos forward")
-    o_got = active(o, 0, c, "O")
-    lse_cpu = lse.cpu()
-    assert bool((lse_cpu[b * heads * n:] == SENTINEL).all()), "lse: a store past [B][heads][N]"
-    lse_got = lse_cpu[:b * heads * n].view(b, heads, n)
-    assert bool(torch.isfinite(lse_got).all()), "lse: NaN"
-    del keep
-    return o_got, lse_got
+    return A.run_relpos(L, lib, b, wh, ww, heads, sliced, q, k, v, table, sfx="_f16")
 
 
 F16_RELPOS_CASES = [RELPOS_CASES[0], RELPOS_CASES[1], RELPOS_CASES[3]]   # 2x3, crosses a key tile, N > 128

@@ -11,134 +11,25 @@ tests/test_convnext_ops_gpu.py:
 The cases are placed relative to T = 128 (tests/util_vit.py), the larger of the kernels' two tiles: a
 workgroup owns 128 query rows (keys in the dK / dV kernel) and sweeps the other operand in tiles of 32
 rows.  tests/test_elastic_vit.py checks on the CPU that float32 torch stays below 1e-5 on these inputs, so
-the bound here is a statement about the kernels."""
+the bound here is a statement about the kernels.  The harness (run_attention, Workspace, active, ...) is
+tests/util_attention_gpu.py, shared with the fp16-operand and the relative-position tests."""
 import ctypes
+import json
+import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+import util_attention_gpu as A
 import util_vit as U
+from util_attention_gpu import (DEV, GS_E_ALIGN, GS_E_BADARG, GS_E_NULL, GS_E_WORKSPACE, NAN, SENTINEL, active, padded,
+                                run_attention, stream)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 TOL = 3e-5
-SENTINEL = 7.0
-GUARD_BYTES = 4096
-GUARD_BYTE = 0xA5
-NAN = float("nan")
-GS_E_BADARG, GS_E_ALIGN, GS_E_WORKSPACE, GS_E_NULL = -1, -2, -3, -4
-
-
-def stream():
-    from gaia_seg_amd.hip.runtime import current_stream_ptr
-    return current_stream_ptr()
-
-
-class Workspace:
-    """exactly ``need`` bytes of NaN in front of a guard"""
-
-    def __init__(self, need):
-        assert need > 0
-        self.need = need
-        self.buf = torch.empty(need + GUARD_BYTES, dtype=torch.uint8, device=DEV)
-        self.buf[:need] = 0xFF
-        self.buf[need:] = GUARD_BYTE
-
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def check(self):
-        torch.cuda.synchronize()
-        assert bool((self.buf[self.need:] == GUARD_BYTE).all()), "the workspace was overrun"
-
-
-def padded(t, ld, fill, c0=0):
-    """t [..., c] inside a [..., ld] buffer filled with ``fill``, at column c0"""
-    buf = torch.full(t.shape[:-1] + (ld,), fill)
-    buf[..., c0:c0 + t.shape[-1]] = t
-    return buf.to(DEV)
-
-
-def active(buf, c0, c, what):
-    """synchronise; everything outside [..., c0:c0+c] still holds the sentinel; the slice on the CPU"""
-    torch.cuda.synchronize()
-    out = buf.cpu()
-    outside = torch.ones_like(out, dtype=torch.bool)
-    outside[..., c0:c0 + c] = False
-    assert bool((out[outside] == SENTINEL).all()), "%s: a store outside the active slice" % what
-    got = out[..., c0:c0 + c].contiguous()
-    assert bool(torch.isfinite(got).all()), "%s: NaN -- a pad column, an inactive head or unwritten scratch " \
-                                            "was read" % what
-    return got
-
-
-def run_attention(L, lib, b, n, heads, sliced, q, k, v, do, bases):
-    """forward, backward (overwrite), backward (accumulate onto the bases) -> (O, lse, dQ, dK, dV, dQ+, dK+,
-    dV+).  ``sliced``: Q, K, V (and dQ, dK, dV) are column slices of one buffer of 4 heads' width per
-    operand -- the 4th head's columns hold NaN (inputs) / the sentinel (outputs) -- and O / dO have a pitch
-    wider than needed."""
-    c = 64 * heads
-    if sliced:
-        hw, ldo = 64 * 4, c + 24
-        qkv = torch.full((b, n, 3 * hw), NAN)
-        for i, t in enumerate((q, k, v)):
-            qkv[..., i * hw:i * hw + c] = t
-        qkv = qkv.to(DEV)
-        ptrs = [qkv.data_ptr() + 4 * i * hw for i in range(3)]
-        ldq = ldk = ldv = 3 * hw
-        keep = [qkv]
-    else:
-        ldo = ldq = ldk = ldv = c
-        keep = [t.contiguous().to(DEV) for t in (q, k, v)]
-        ptrs = [t.data_ptr() for t in keep]
-    d = lib.attention_desc(b, n, heads, U.SCALE, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo)
-    db, st = ctypes.byref(d), stream()
-    o = torch.full((b, n, ldo), SENTINEL, device=DEV)
-    lse = torch.full((b * heads * n + 8,), SENTINEL, device=DEV)
-    lib.check(L.gs_attention_forward(db, ptrs[0], ptrs[1], ptrs[2], o.data_ptr(), lse.data_ptr(), st), "fwd")
-    o_got = active(o, 0, c, "O")
-    lse_cpu = lse.cpu()
-    assert bool((lse_cpu[b * heads * n:] == SENTINEL).all()), "lse: a store past [B][heads][N]"
-    lse_got = lse_cpu[:b * heads * n].view(b, heads, n)
-    dog = padded(do, ldo, NAN)
-    outs = []
-    for accumulate in (0, 1):
-        if sliced:   # the three gradients as slices of one buffer, like the operands
-            g = torch.full((b, n, 3 * hw), SENTINEL)
-            if accumulate:
-                for i, t in enumerate(bases):
-                    g[..., i * hw:i * hw + c] = t
-            g = g.to(DEV)
-            gptrs = [g.data_ptr() + 4 * i * hw for i in range(3)]
-            gbufs = [g, g, g]
-            c0s = [0, hw, 2 * hw]
-        else:
-            gbufs = [(bases[i].contiguous().to(DEV) if accumulate else torch.full((b, n, c), SENTINEL, device=DEV))
-                     for i in range(3)]
-            gptrs = [t.data_ptr() for t in gbufs]
-            c0s = [0, 0, 0]
-        ws = Workspace(L.gs_attention_workspace_bytes(db))
-        lib.check(L.gs_attention_backward(db, ptrs[0], ptrs[1], ptrs[2], o.data_ptr(), lse.data_ptr(),
-                                          dog.data_ptr(), gptrs[0], gptrs[1], gptrs[2], accumulate, ws.ptr(),
-                                          ws.need, st), "bwd")
-        ws.check()
-        torch.cuda.synchronize()
-        if sliced:
-            full = gbufs[0].cpu()
-            outside = torch.ones_like(full, dtype=torch.bool)
-            for c0 in c0s:
-                outside[..., c0:c0 + c] = False
-            assert bool((full[outside] == SENTINEL).all()), "a gradient store outside the active columns"
-            got = [full[..., c0:c0 + c].contiguous() for c0 in c0s]
-        else:
-            got = [t.cpu() for t in gbufs]
-        for name, t in zip(("dQ", "dK", "dV"), got):
-            assert bool(torch.isfinite(t).all()), "%s: NaN -- a pad column or unwritten scratch was read" % name
-        outs += got
-    del keep
-    return (o_got, lse_got) + tuple(outs)
+PARENT_BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_parent_bits.json")
 
 
 @pytest.mark.parametrize("case", U.ATTENTION_CASES, ids=[c[0] for c in U.ATTENTION_CASES])
@@ -208,6 +99,23 @@ def test_attention_argument_checks(hip_lib):
     torch.cuda.synchronize()
     for t in out + [lse]:
         assert bool((t == SENTINEL).all()), "a refused call wrote to an output"
+
+
+@pytest.mark.parametrize("precision", list(A.PRECISIONS))
+@pytest.mark.parametrize("kind,case", A.BITS_CASES, ids=["%s-%s" % (k, c[0]) for k, c in A.BITS_CASES])
+def test_attention_matches_parent_bits(hip_lib, kind, case, precision):
+    """Every output of the attention entries, bit for bit, against tests/golden/attention_parent_bits.json:
+    SHA-256 digests recorded on an MI355X with the library of the commit before the fp32 and the fp16-operand
+    kernels became one template per kernel over the operand format (csrc/attention_common.h).  A refactor of
+    these kernels keeps every bit; a change that is meant to move them regenerates the file with
+    tests/golden/make_attention_parent_bits.py, whose docstring says how."""
+    from gaia_seg_amd.hip import lib
+    with open(PARENT_BITS) as f:
+        want = json.load(f)["%s/%s/%s" % (kind, case[0], precision)]
+    got = A.output_digests(hip_lib, lib, kind, case, precision)
+    assert sorted(got) == sorted(want)
+    differ = [nm for nm in got if got[nm] != want[nm]]
+    assert not differ, "%s %s %s: %s differ from the parent's bits" % (kind, case[0], precision, differ)
 
 
 def run_tokens(L, lib, b, t, d, n_max, d_max, patches, cls, pos, dx):

@@ -16,69 +16,11 @@ import torch.nn.functional as F
 from conftest import rel_err
 import util_beit as B
 import util_vit as U
-from test_attention_gpu import NAN, SENTINEL, active, stream
+from util_attention_gpu import NAN, RELPOS_CASES, SENTINEL, active, make_table, run_relpos, stream
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 TOL = 3e-5
-
-# (name, B, Wh, Ww, heads, sliced operands + wide ldo + ld_table 4?, only the three cls rows non-zero?)
-RELPOS_CASES = [
-    ("2x3", 2, 2, 3, 1, False, False),
-    ("5x7-crosses-a-key-tile", 1, 5, 7, 2, False, False),
-    ("5x7-cls-rows-only", 1, 5, 7, 2, False, True),
-    ("11x12-sliced-crosses-a-workgroup", 2, 11, 12, 3, True, False),
-    ("12x11-transposed-window", 1, 12, 11, 3, False, False),
-]
-
-
-def make_table(wh, ww, heads, cls_only, seed):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn((2 * wh - 1) * (2 * ww - 1) + 3, heads, generator=g) * 2.0
-    if cls_only:
-        t[:-3] = 0
-    return t
-
-
-def run_relpos(L, lib, b, wh, ww, heads, sliced, q, k, v, table):
-    """-> (O, lse); ``table`` None runs gs_attention_forward on the same operands.  ``sliced``: Q, K, V are
-    column slices of one buffer of 4 heads' width per operand whose 4th head holds NaN, O has a pitch wider
-    than needed, and the table has a 4th column of NaN (ld_table 4 for 3 heads)."""
-    n, c = wh * ww + 1, 64 * heads
-    if sliced:
-        hw, ldo, ldt = 64 * 4, c + 24, heads + 1
-        qkv = torch.full((b, n, 3 * hw), NAN)
-        for i, t in enumerate((q, k, v)):
-            qkv[..., i * hw:i * hw + c] = t
-        qkv = qkv.to(DEV)
-        ptrs = [qkv.data_ptr() + 4 * i * hw for i in range(3)]
-        ldq = 3 * hw
-        keep = [qkv]
-    else:
-        ldo = ldq = c
-        ldt = heads
-        keep = [t.contiguous().to(DEV) for t in (q, k, v)]
-        ptrs = [t.data_ptr() for t in keep]
-    d = lib.attention_desc(b, n, heads, U.SCALE, ldq=ldq, ldk=ldq, ldv=ldq, ldo=ldo)
-    o = torch.full((b, n, ldo), SENTINEL, device=DEV)
-    lse = torch.full((b * heads * n + 8,), SENTINEL, device=DEV)
-    if table is None:
-        lib.check(L.gs_attention_forward(ctypes.byref(d), ptrs[0], ptrs[1], ptrs[2], o.data_ptr(), lse.data_ptr(),
-                                         stream()), "plain forward")
-    else:
-        tg = torch.full((table.shape[0], ldt), NAN)
-        tg[:, :heads] = table
-        tg = tg.to(DEV)
-        lib.check(L.gs_attention_relpos_forward(ctypes.byref(d), ptrs[0], ptrs[1], ptrs[2], tg.data_ptr(), ldt, wh,
-                                                ww, o.data_ptr(), lse.data_ptr(), stream()), "relpos forward")
-    o_got = active(o, 0, c, "O")
-    lse_cpu = lse.cpu()
-    assert bool((lse_cpu[b * heads * n:] == SENTINEL).all()), "lse: a store past [B][heads][N]"
-    lse_got = lse_cpu[:b * heads * n].view(b, heads, n)
-    assert bool(torch.isfinite(lse_got).all()), "lse: NaN"
-    del keep
-    return o_got, lse_got
-
 
 @pytest.mark.parametrize("case", RELPOS_CASES, ids=[c[0] for c in RELPOS_CASES])
 def test_relpos_attention_forward(hip_lib, case):
