@@ -289,8 +289,56 @@ def uper_head_flops(head, feats):
     return total + f + _conv(head.conv_seg, cb, h0, w0)[0]
 
 
+def ocr_head_flops(head, feats, num_prev_classes=None):
+    """DynamicOCRHead: the 3x3 bottleneck, the two query projections, the output projection, the 1x1
+    bottleneck over the concat buffer and the classifier at the input's P = h * w pixels; the two key
+    projections and the value projection on the K x 1 region map.  Convs count as everywhere (2 FLOPs per
+    multiply-add).  The two region products count K * P * C multiply-adds for the gather (2 * K * P * C
+    FLOPs) and 2 * K * P * ch for the attention (scores and weighted values: 4 * K * P * ch FLOPs);
+    softmax exponentials are not counted.  K is the class count of the previous head's logits."""
+    c, h, w = feats[head.in_index % len(feats)]
+    k = head.num_classes if num_prev_classes is None else num_prev_classes
+    ocb = head.object_context_block
+    total, ch = _conv_module(head.bottleneck, c, h, w)
+    total += 2.0 * k * h * w * ch
+    cq = ch
+    for m in ocb.query_project:
+        f, cq = _conv_module(m, cq, h, w)
+        total += f
+    ck = ch
+    for m in ocb.key_project:
+        f, ck = _conv_module(m, ck, k, 1)
+        total += f
+    total += _conv_module(ocb.value_project, ch, k, 1)[0]
+    total += 4.0 * k * h * w * cq
+    f, co = _conv_module(ocb.out_project, cq, h, w)
+    total += f
+    f, cb = _conv_module(ocb.bottleneck, co + ch, h, w)
+    return total + f + _conv(head.conv_seg, cb, h, w)[0]
+
+
+def _head_flops(head, feats, prev=None):
+    name = type(head).__name__
+    if isinstance(head.in_index, int):
+        c, fh, fw = feats[head.in_index % len(feats)]
+    if name == "DynamicFCNHead":
+        return fcn_head_flops(head, c, fh, fw)
+    if name == "DynamicPSPHead":
+        return psp_head_flops(head, c, fh, fw)
+    if name == "DynamicUPerHead":
+        return uper_head_flops(head, feats)
+    if name in ("DynamicASPPHead", "DynamicDepthwiseSeparableASPPHead"):
+        return aspp_head_flops(head, feats)
+    if name == "DynamicOCRHead":
+        return ocr_head_flops(head, feats, prev.num_classes if prev is not None else None)
+    return float("nan")
+
+
 def model_flops(model, h, w):
-    """dict(backbone, backbone_3x3, [neck,] decode, aux, total) in FLOPs per image for the current arch."""
+    """dict(backbone, backbone_3x3, [neck,] decode, aux, total) in FLOPs per image for the current arch.
+    A cascade of decode heads (DynamicCascadeEncoderDecoder) adds one ``decode_<i>`` entry per stage;
+    ``decode`` is their sum."""
+    import torch.nn as nn
     b, params, k3, feats = backbone_flops(model.backbone, h, w)
     out = dict(backbone=b, backbone_3x3=k3, backbone_params=params)
     if getattr(model, "neck", None) is not None:
@@ -298,18 +346,13 @@ def model_flops(model, h, w):
     for key, head in (("decode", model.decode_head), ("aux", getattr(model, "auxiliary_head", None))):
         if head is None:
             continue
-        if isinstance(head.in_index, int):
-            c, fh, fw = feats[head.in_index % len(feats)]
-        name = type(head).__name__
-        if name == "DynamicFCNHead":
-            out[key] = fcn_head_flops(head, c, fh, fw)
-        elif name == "DynamicPSPHead":
-            out[key] = psp_head_flops(head, c, fh, fw)
-        elif name == "DynamicUPerHead":
-            out[key] = uper_head_flops(head, feats)
-        elif name in ("DynamicASPPHead", "DynamicDepthwiseSeparableASPPHead"):
-            out[key] = aspp_head_flops(head, feats)
+        if key == "decode" and isinstance(head, nn.ModuleList):
+            prev = None
+            for i, stage in enumerate(head):
+                out["decode_%d" % i] = _head_flops(stage, feats, prev)
+                prev = stage
+            out[key] = sum(out["decode_%d" % i] for i in range(len(head)))
         else:
-            out[key] = float("nan")
+            out[key] = _head_flops(head, feats)
     out["total"] = sum(v for k, v in out.items() if k in ("backbone", "neck", "decode", "aux") and v == v)
     return out

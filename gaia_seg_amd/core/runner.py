@@ -88,6 +88,10 @@ def check_sandwich_model(model):
         raise ValueError("use_distillation (sandwich) with a %s is not supported: the segmentor "
                          "distils from its own fixed teacher" % type(model).__name__)
     dec = model.decode_head
+    if isinstance(dec, torch.nn.ModuleList):
+        raise ValueError("use_distillation: a cascade of decode heads (%s) is not supported: the MAX member "
+                         "hands out one 'teacher_logits' map, a cascade has one per stage"
+                         % type(model).__name__)
     if getattr(dec, "kd_teacher_key", None) != "teacher_logits":
         raise ValueError(
             "use_distillation: the decode head must be a DynamicPSPHead (it reads 'teacher_logits'); "

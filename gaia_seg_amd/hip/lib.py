@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class HipLibraryError(RuntimeError):
@@ -128,6 +128,47 @@ def fcu_down_desc(b, t, d, eps=1e-6, ldz=None, ldxt=None, ldo=None, lddz=None, l
     desc.lddz = desc.ldz if lddz is None else lddz
     desc.lddxt = desc.ldxt if lddxt is None else lddxt
     return desc
+
+
+OCR_MAX_CLASSES = 256             # GS_OCR_MAX_CLASSES
+OCR_GATHER_MAX_CHANNELS = 2048    # GS_OCR_GATHER_MAX_CHANNELS
+OCR_ATTEND_MAX_CHANNELS = 512     # GS_OCR_ATTEND_MAX_CHANNELS
+
+
+class OcrGatherDesc(Structure):
+    """Mirror of ``gs_ocr_gather_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("B", "P", "K", "C", "ldl", "ldf", "ldc", "lddl", "lddf", "lddc")]
+                + [("scale", c_float)])
+
+
+def ocr_gather_desc(b, p, k, c, scale=1.0, ldl=None, ldf=None, ldc=None, lddl=None, lddf=None, lddc=None):
+    """An ``OcrGatherDesc`` for ``b`` images of ``p`` pixels, ``k`` classes and ``c`` active feature
+    channels; the logits' pitch defaults to round_up(k, 4), the others to c, a gradient's pitch to the pitch
+    of its forward operand."""
+    d = OcrGatherDesc()
+    d.B, d.P, d.K, d.C, d.scale = b, p, k, c, scale
+    d.ldl = (k + 3) // 4 * 4 if ldl is None else ldl
+    d.ldf, d.ldc = (c if v is None else v for v in (ldf, ldc))
+    d.lddl, d.lddf, d.lddc = (f if v is None else v for v, f in ((lddl, d.ldl), (lddf, d.ldf), (lddc, d.ldc)))
+    return d
+
+
+class OcrAttendDesc(Structure):
+    """Mirror of ``gs_ocr_attend_desc``."""
+    _fields_ = [(k, c_int32) for k in ("B", "P", "K", "ch", "ldq", "ldk", "ldv", "ldo", "lddq", "lddk", "lddv",
+                                       "lddo")]
+
+
+def ocr_attend_desc(b, p, k, ch, ldq=None, ldk=None, ldv=None, ldo=None, lddq=None, lddk=None, lddv=None,
+                    lddo=None):
+    """An ``OcrAttendDesc`` for ``b`` images of ``p`` pixels and ``k`` regions of width ``ch``; a forward pitch
+    defaults to ch, a gradient's pitch to the pitch of its forward operand."""
+    d = OcrAttendDesc()
+    d.B, d.P, d.K, d.ch = b, p, k, ch
+    d.ldq, d.ldk, d.ldv, d.ldo = (ch if v is None else v for v in (ldq, ldk, ldv, ldo))
+    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
+                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    return d
 
 
 class BnArgs(Structure):
@@ -278,6 +319,7 @@ _DW = POINTER(DwConvDesc)
 _LN = POINTER(LayerNormDesc)
 _AT = POINTER(AttentionDesc)
 _FD = POINTER(FcuDownDesc)
+_OG, _OA = POINTER(OcrGatherDesc), POINTER(OcrAttendDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
 PROTOTYPES = {
@@ -320,6 +362,12 @@ PROTOTYPES = {
     "gs_fcu_up_add_backward": (_i32, [_P, _P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
     "gs_fcu_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_fcu_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _i32, _i32, _i32, _P]),
+    "gs_ocr_gather_workspace_bytes": (_sz, [_OG]),
+    "gs_ocr_gather_forward": (_i32, [_OG, _P, _P, _P, _P, _P, _sz, _P]),
+    "gs_ocr_gather_backward": (_i32, [_OG, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_ocr_attend_forward": (_i32, [_OA, _P, _P, _P, _P, _P, _P]),
+    "gs_ocr_attend_workspace_bytes": (_sz, [_OA]),
+    "gs_ocr_attend_backward": (_i32, [_OA, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _sz, _P]),
     "gs_colsum_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_colsum": (_i32, [_P, _i64, _i32, _i32, _P, _P, _sz, _P]),
     "gs_bn_stats_workspace_bytes": (_sz, [_i64, _i32]),

@@ -1216,6 +1216,99 @@ def fcu_up_add(tape, x, r, s):
     return out
 
 
+def _grad_or_scratch(x, what):
+    """where a kernel that always produces the gradient of ``x`` writes it: ``x.g`` (first and only
+    contribution) or scratch with x's layout rules for an input that needs none"""
+    if not x.requires_grad:
+        return Act.empty(x.N, x.H, x.W, x.C, x.t.device).t
+    if _input_grad(x):
+        raise RuntimeError("%s has more than one consumer; unsupported" % what)
+    return x.g
+
+
+def ocr_gather(tape, feats, logits, scale=1.0):
+    """OCRNet's soft object regions (mmseg's SpatialGatherModule): from the pixel features ``feats``
+    [B, H, W, C] (possibly a channel slice of a wider buffer) and the previous head's ``logits`` [B, H, W, K]
+        w = softmax over the H*W pixels of scale * logits[..., k],   context[b, k] = sum_p w[b, k, p] feats[b, p]
+    as a K x 1 map [B, K, 1, C] (gs_ocr_gather_forward; w is never stored, the statistics of every class
+    map are kept for the backward).  The features have other consumers (their gradient accumulates); the
+    logits have this one inside the node.  The scratch (one [K, C] partial per 128 pixels) lies far inside
+    what reserve_workspaces sets aside."""
+    L = _L()
+    feats, logits = materialize(tape, feats), materialize(tape, logits)
+    b, p, k, c, dev = feats.N, feats.H * feats.W, logits.C, feats.C, feats.t.device
+    if (logits.N, logits.H, logits.W) != (b, feats.H, feats.W):
+        raise ValueError("ocr_gather: logits %s and features %s differ in size"
+                         % (tuple(logits.t.shape), tuple(feats.t.shape)))
+    if c % 4:
+        raise ValueError("ocr_gather needs a channel count that is a multiple of 4, got %d" % c)
+    out = Act.empty(b, k, 1, c, dev)
+    stats = torch.empty(2 * b * k, dtype=torch.float32, device=dev)
+    d = _lib.ocr_gather_desc(b, p, k, c, scale, ldl=logits.ld, ldf=feats.ld, ldc=out.ld)
+    db = ctypes.byref(d)
+    ws = _ws.get(L.gs_ocr_gather_workspace_bytes(db), dev)
+    _lib.check(L.gs_ocr_gather_forward(db, logits.ptr, feats.ptr, out.ptr, stats.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), current_stream_ptr()), "gs_ocr_gather_forward")
+
+    def backward():
+        dctx = out.g
+        if dctx is None:
+            return
+        dl = _grad_or_scratch(logits, "ocr_gather: the logits map")
+        if feats.requires_grad:
+            acc = _input_grad(feats)
+            df = feats.g
+        else:
+            acc, df = 0, torch.empty_like(feats.t)
+        d.lddl, d.lddf, d.lddc = dl.stride(2), df.stride(2), dctx.stride(2)
+        wsb = _ws.get(L.gs_ocr_gather_workspace_bytes(db), dev)
+        _lib.check(L.gs_ocr_gather_backward(db, logits.ptr, feats.ptr, out.ptr, stats.data_ptr(),
+                                            dctx.data_ptr(), dl.data_ptr(), df.data_ptr(), acc, wsb.data_ptr(),
+                                            wsb.numel(), current_stream_ptr()), "gs_ocr_gather_backward")
+
+    tape.record(backward)
+    return out
+
+
+def ocr_attend(tape, q, k, v):
+    """OCRNet's pixel-to-region attention (the core of mmseg's ObjectAttentionBlock): queries ``q``
+    [B, H, W, ch], keys and values ``k``, ``v`` [B, K, 1, ch] (region maps),
+        out[b, p] = sum_k softmax_k(ch^-0.5 <q[b, p], k[b, k]>) v[b, k],
+    one kernel (gs_ocr_attend_forward).  The [B, H*W, K] map is not kept: the backward recomputes it from
+    q, k and the saved log-sum-exp of every pixel.  Each input has this one consumer."""
+    L = _L()
+    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
+    b, p, ch, dev = q.N, q.H * q.W, q.C, q.t.device
+    kk = k.H * k.W
+    if (k.N, k.C) != (b, ch) or (v.N, v.H, v.W, v.C) != (b, k.H, k.W, ch):
+        raise ValueError("ocr_attend: queries %s, keys %s and values %s do not belong together"
+                         % (tuple(q.t.shape), tuple(k.t.shape), tuple(v.t.shape)))
+    if ch % 4:
+        raise ValueError("ocr_attend needs a channel count that is a multiple of 4, got %d" % ch)
+    out = Act.empty(b, q.H, q.W, ch, dev)
+    lse = torch.empty(b * p, dtype=torch.float32, device=dev)
+    d = _lib.ocr_attend_desc(b, p, kk, ch, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    _lib.check(L.gs_ocr_attend_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(),
+                                       current_stream_ptr()), "gs_ocr_attend_forward")
+
+    def backward():
+        dout = out.g
+        if dout is None:
+            return
+        dq = _grad_or_scratch(q, "ocr_attend: the query map")
+        dk = _grad_or_scratch(k, "ocr_attend: the key map")
+        dv = _grad_or_scratch(v, "ocr_attend: the value map")
+        d.lddq, d.lddk, d.lddv, d.lddo = dq.stride(2), dk.stride(2), dv.stride(2), dout.stride(2)
+        db = ctypes.byref(d)
+        ws = _ws.get(L.gs_ocr_attend_workspace_bytes(db), dev)
+        _lib.check(L.gs_ocr_attend_backward(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dout.data_ptr(),
+                                            dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), current_stream_ptr()), "gs_ocr_attend_backward")
+
+    tape.record(backward)
+    return out
+
+
 def _input_grad(x):
     """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
     x.g already held a contribution, else 0 after allocating it (a channel slice's storage is

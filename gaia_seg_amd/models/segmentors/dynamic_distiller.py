@@ -34,6 +34,9 @@ class DynamicDistiller(DynamicEncoderDecoder):
                  has_distill_loss=True, distill_loss_temperature=1, has_pairwise_loss=True,
                  pairwise_loss_temperature=1, distill_loss_weight=1, pairwise_loss_weight=1,
                  has_channel_loss=False, channel_loss_temperature=1, channel_loss_weight=1):
+        if isinstance(decode_head, (list, tuple)):
+            raise ValueError("DynamicDistiller: a cascade of decode heads is not supported: the distillation "
+                             "losses compare ONE student logit map with the teacher's")
         super().__init__(backbone=backbone, decode_head=decode_head, neck=neck,
                          auxiliary_head=auxiliary_head, train_cfg=train_cfg, test_cfg=test_cfg,
                          pretrained=pretrained)

@@ -358,6 +358,67 @@ int gs_fcu_tokens_backward(const float* dx, int32_t lddx, float* dpatches, int32
                            int32_t B, int32_t T, int32_t D, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* OCRNet: the soft-region gather and the pixel-to-region attention                             */
+/* ------------------------------------------------------------------------------------------ */
+/* Both on fp32 "rows x C" views as the operators above (a pitch >= the width per operand, float4
+ * multiples, 16-byte aligned bases), fp32 in every precision mode.  No float atomics: every sum over
+ * pixels goes through partials per run of rows and a fixed-order sum, so results are bit-identical from
+ * run to run.  Pad columns are never read and nothing outside the active columns is written.  Workspaces
+ * come from the caller (the queries need no device), so both are safe inside a captured step graph.
+ * Checked on the host before any launch: GS_E_NULL (descriptor or pointer), GS_E_BADARG (a size <= 0,
+ * K > GS_OCR_MAX_CLASSES, a width above its maximum, B > 65535, B * P >= 2^31, a pitch below its width, a
+ * scale that is not finite), GS_E_ALIGN (a width or a pitch no multiple of 4, a tensor pointer not
+ * 16-byte aligned), GS_E_WORKSPACE. */
+#define GS_OCR_MAX_CLASSES 256
+#define GS_OCR_GATHER_MAX_CHANNELS 2048
+#define GS_OCR_ATTEND_MAX_CHANNELS 512
+/* mmseg's SpatialGatherModule.  logits L [B][P][K] (pitch ldl >= K), features F [B][P][C]:
+ *   w[b,k,p]   = softmax over the P pixels of scale * L[b,p,k]
+ *   ctx[b,k,:] = sum_p w[b,k,p] * F[b,p,:]                                        (ctx: [B][K][C])
+ * w is never stored; stats [B][K][2] receives (max, log sum) of every class map for the backward. */
+typedef struct gs_ocr_gather_desc {
+  int32_t B, P, K, C;         /* images, pixels per image, classes, ACTIVE feature width         */
+  int32_t ldl, ldf, ldc;      /* pitches of the logits, of the features and of ctx               */
+  int32_t lddl, lddf, lddc;   /* pitches of dlogits, dfeats and dctx (all six are always checked) */
+  float scale;
+} gs_ocr_gather_desc;
+/* bytes of scratch either direction needs (0 for a descriptor they would refuse): the statistics'
+ * partials per run of 64 rows, and one [K][C] partial per run of 128 rows. */
+size_t gs_ocr_gather_workspace_bytes(const gs_ocr_gather_desc* d);
+int gs_ocr_gather_forward(const gs_ocr_gather_desc* d, const float* logits, const float* feats, float* ctx,
+                          float* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* With t[b,k] = <dctx[b,k,:], ctx[b,k,:]> (= sum_p w dw) and dw[b,k,p] = <dctx[b,k,:], F[b,p,:]>:
+ *   dfeats[b,p,:] (= or +=, accumulate_dfeats != 0 adds) sum_k w[b,k,p] * dctx[b,k,:]
+ *   dlogits[b,p,k] = scale * w[b,k,p] * (dw[b,k,p] - t[b,k])
+ * and columns K .. round_up(K, 4) - 1 of dlogits are zeroed. */
+int gs_ocr_gather_backward(const gs_ocr_gather_desc* d, const float* logits, const float* feats, const float* ctx,
+                           const float* stats, const float* dctx, float* dlogits, float* dfeats,
+                           int accumulate_dfeats, void* workspace, size_t workspace_bytes, void* stream);
+/* The core of mmseg's SelfAttentionBlock as ObjectAttentionBlock uses it.  Queries Q [B][P][ch], keys Kr and
+ * values V [B][K][ch]:
+ *   a[b,p,k]   = softmax over the K regions of ch^-0.5 * <Q[b,p,:], Kr[b,k,:]>
+ *   out[b,p,:] = sum_k a[b,p,k] * V[b,k,:]
+ * The map a is not stored: lse [B][P] keeps the log-sum-exp of every pixel's scores, and the backward
+ * recomputes a from Q and Kr.  Keys and values are staged in LDS in chunks of classes with a running
+ * max / sum, so K is bounded by GS_OCR_MAX_CLASSES only. */
+typedef struct gs_ocr_attend_desc {
+  int32_t B, P, K, ch;               /* images, pixels per image, regions, ACTIVE width           */
+  int32_t ldq, ldk, ldv, ldo;        /* pitches of Q, Kr, V and out                               */
+  int32_t lddq, lddk, lddv, lddo;    /* pitches of dQ, dKr, dV and dout (all eight always checked) */
+} gs_ocr_attend_desc;
+int gs_ocr_attend_forward(const gs_ocr_attend_desc* d, const float* q, const float* k, const float* v, float* out,
+                          float* lse, void* stream);
+/* bytes of scratch the backward needs (0 for a descriptor it would refuse): a and ds of every pixel, and
+ * one [K][ch] partial per run of 128 rows. */
+size_t gs_ocr_attend_workspace_bytes(const gs_ocr_attend_desc* d);
+/* With da[b,p,k] = <dout[b,p,:], V[b,k,:]> and ds = a * (da - <dout[b,p,:], out[b,p,:]>):
+ *   dq[b,p,:] = ch^-0.5 * sum_k ds * Kr[b,k,:],   dk[b,k,:] = ch^-0.5 * sum_p ds * Q[b,p,:],
+ *   dv[b,k,:] = sum_p a * dout[b,p,:].   All three are overwritten. */
+int gs_ocr_attend_backward(const gs_ocr_attend_desc* d, const float* q, const float* k, const float* v,
+                           const float* out, const float* lse, const float* dout, float* dq, float* dk, float* dv,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Dynamic BatchNorm (+ residual add, + ReLU) — K4, K8                                         */
 /* ------------------------------------------------------------------------------------------ */
 /* Replaces F.batch_norm on the leading C-slice of max-size parameters (gaiavision DynBN /

@@ -32,7 +32,10 @@ def main(argv=None):
     metas = build_model_sampler(cfg[args.sampler]).traverse()
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     rows = []
+    stem_anchors = cfg.get("stem_anchors") or {}
     for meta in metas[rank::world]:
+        if meta.get("name") in stem_anchors:   # deep-stem (v1c / OS8) supernet: a width per stem conv (as bench.py)
+            meta = dict(meta, **{"arch.backbone.stem.width": list(stem_anchors[meta["name"]])})
         model.manipulate_arch(fold_dict(meta)["arch"])
         shape = tuple(args.shape)
         if args.apply_input_shape and meta.get("data.input_shape") is not None:
