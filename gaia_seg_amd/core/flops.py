@@ -16,7 +16,12 @@ no multiply-add pairs), LayerNorm, GELU and the residual adds count 0.  A Dynami
 
 The ElasticConvformer follows both conventions: its bottlenecks, projections and patch embedding are convs,
 its transformer blocks count as the ElasticTransformer's; the coupling units' LayerNorm, GELU, pooling,
-upsample and adds count 0, and the conv-to-token projection counts on the pooled map it runs on."""
+upsample and adds count 0, and the conv-to-token projection counts on the pooled map it runs on.
+
+The DynamicMixVisionTransformer (SegFormer) counts its patch embeddings, reduction convs, linears and the
+depthwise 3x3 of the Mix-FFN as the convs they are, and its attention -- Nq tokens of the stage against the Nk
+tokens of the reduced map -- 2 x 2 * Nq * Nk * 64 * heads per block and image; the DynamicSegformerHead counts
+its 1x1 convs at the sizes they run at."""
 from ..hip.ops import conv_out_size
 from .bricks import DynamicConv2d
 
@@ -87,6 +92,42 @@ def vit_backbone_flops(backbone, h, w, in_channels=3):
             extra = backbone.out_indices[i]
             n_out = 1 if extra is None else 1 + sum(1 for j in extra if j < len(layers))
             feats.extend([(d, hp, wp)] * n_out)
+    return total, params, 0.0, feats
+
+
+def attention_kv_flops(nq, nk, heads, head_dim=64):
+    """Q K^T and P V of one image with nq queries and nk keys: 2 products x 2 * nq * nk * head_dim per head"""
+    return 4.0 * nq * nk * head_dim * heads
+
+
+def mit_backbone_flops(backbone, h, w, in_channels=3):
+    """backbone_flops for a DynamicMixVisionTransformer: (flops per image, params, 0.0, feature shapes).
+    Params are those of the active subnet: active slices, active blocks, LayerNorm affines."""
+    total, params, c, feats = 0.0, 0.0, in_channels, []
+    for i, stage in enumerate(backbone.stages):
+        f, p, c, h, w = _conv(stage.patch_embeddings.proj, c, h, w)
+        total += f
+        params += p + 2 * c + 2 * c                       # + the embedding's and the stage's LayerNorm
+        for blk in stage.active_blocks():
+            att, hk, wk = blk.attention, h, w
+            params += 4 * c                               # layernorm_before, layernorm_after
+            if att.sr_ratio > 1:
+                f, p, _, hk, wk = _conv(att.sequence_reduction.sequence_reduction, c, h, w)
+                total += f
+                params += p + 2 * c
+            for lin, (lh, lw) in ((att.q_proj, (h, w)), (att.k_proj, (hk, wk)), (att.v_proj, (hk, wk)),
+                                  (att.o_proj, (h, w))):
+                f, p, _, _, _ = _conv(lin, c, lh, lw)
+                total += f
+                params += p
+            total += attention_kv_flops(h * w, hk * wk, att.num_heads)
+            f1, p1, hidden, _, _ = _conv(blk.mlp.fc1, c, h, w)
+            fd, pd, _, _, _ = _conv(blk.mlp.dwconv.dwconv, hidden, h, w)
+            f2, p2, _, _, _ = _conv(blk.mlp.fc2, hidden, h, w)
+            total += f1 + fd + f2
+            params += p1 + pd + p2
+        if i in backbone.out_indices:
+            feats.append((c, h, w))
     return total, params, 0.0, feats
 
 
@@ -176,6 +217,8 @@ def backbone_flops(backbone, h, w, in_channels=3):
         return vit_backbone_flops(backbone, h, w, in_channels)
     if type(backbone).__name__ == "ElasticConvformer":
         return convformer_backbone_flops(backbone, h, w, in_channels)
+    if type(backbone).__name__ == "DynamicMixVisionTransformer":
+        return mit_backbone_flops(backbone, h, w, in_channels)
     total = params = k3 = 0.0
     c = in_channels
     if backbone.deep_stem:
@@ -289,6 +332,16 @@ def uper_head_flops(head, feats):
     return total + f + _conv(head.conv_seg, cb, h0, w0)[0]
 
 
+def segformer_head_flops(head, feats):
+    """DynamicSegformerHead: one 1x1 conv per level at that level's size, the 1x1 fusion conv over the
+    concatenated levels and the classifier at the first level's size; the resizes count 0."""
+    levels = [feats[i] for i in head.in_index]
+    total = sum(_conv(m.conv, c, h, w)[0] for (c, h, w), m in zip(levels, head.convs))
+    _, h0, w0 = levels[0]
+    f, _, cb, _, _ = _conv(head.fusion_conv.conv, len(levels) * head.channels, h0, w0)
+    return total + f + _conv(head.conv_seg, cb, h0, w0)[0]
+
+
 def ocr_head_flops(head, feats, num_prev_classes=None):
     """DynamicOCRHead: the 3x3 bottleneck, the two query projections, the output projection, the 1x1
     bottleneck over the concat buffer and the classifier at the input's P = h * w pixels; the two key
@@ -327,6 +380,8 @@ def _head_flops(head, feats, prev=None):
         return psp_head_flops(head, c, fh, fw)
     if name == "DynamicUPerHead":
         return uper_head_flops(head, feats)
+    if name == "DynamicSegformerHead":
+        return segformer_head_flops(head, feats)
     if name in ("DynamicASPPHead", "DynamicDepthwiseSeparableASPPHead"):
         return aspp_head_flops(head, feats)
     if name == "DynamicOCRHead":

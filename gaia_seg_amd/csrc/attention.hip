@@ -10,7 +10,7 @@ namespace {
 __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs a, const float* __restrict__ dO,
                                                          const float* __restrict__ O,
                                                          float* __restrict__ delta) {
-  const int64_t items = (int64_t)a.B * a.N * a.heads;
+  const int64_t items = (int64_t)a.B * a.Nq * a.heads;
   for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (int64_t)gridDim.x * 256) {
     const int hd = (int)(it % a.heads);
     const int64_t tok = it / a.heads;
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs a, const
       acc = fmaf(x.z, y.z, acc);
       acc = fmaf(x.w, y.w, acc);
     }
-    delta[((tok / a.N) * a.heads + hd) * a.N + tok % a.N] = acc;
+    delta[((tok / a.Nq) * a.heads + hd) * a.Nq + tok % a.Nq] = acc;
   }
 }
 
@@ -100,12 +100,12 @@ struct F32Ops {
   static __device__ __forceinline__ int grad_exponent(const GradMax&) { return 0; }
 
   // delta[B][heads][N]
-  static size_t ws_bytes(const gs_attention_desc* d) {
-    return (size_t)ceil_div((int64_t)d->B * d->heads * d->N * (int64_t)sizeof(float), 16) * 16;
+  static size_t ws_bytes(const gs_attention_kv_desc* d) {
+    return (size_t)ceil_div((int64_t)d->B * d->heads * d->Nq * (int64_t)sizeof(float), 16) * 16;
   }
-  static GradMax launch_delta(const gs_attention_desc* d, const AttnArgs& a, const float* d_o, const float* o,
+  static GradMax launch_delta(const gs_attention_kv_desc* d, const AttnArgs& a, const float* d_o, const float* o,
                               float* delta, hipStream_t stream) {
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(stream_grid((int64_t)d->B * d->N * d->heads, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(attn_delta_kernel, dim3(stream_grid((int64_t)d->B * d->Nq * d->heads, 256)), dim3(256), 0,
                        stream, a, d_o, o, delta);
     return GradMax{};
   }
@@ -166,26 +166,52 @@ int tokens_check(int32_t B, int32_t T, int32_t D, const int32_t* ld, int n_ld) {
 using namespace gs;
 
 extern "C" size_t gs_attention_workspace_bytes(const gs_attention_desc* d) {
-  return attn_workspace_bytes<F32Ops>(d);
+  return attn_workspace_bytes<F32Ops>(SelfDesc(d).p, 1);
 }
 
 extern "C" int gs_attention_forward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
                                     float* o, float* lse, void* stream) {
-  return attn_forward<F32Ops>(d, q, k, v, o, lse, stream);
+  return attn_forward<F32Ops>(SelfDesc(d).p, q, k, v, o, lse, stream);
 }
 
 extern "C" int gs_attention_relpos_forward(const gs_attention_desc* d, const float* q, const float* k,
                                            const float* v, const float* table, int32_t ld_table, int32_t Wh,
                                            int32_t Ww, float* o, float* lse, void* stream) {
-  return attn_relpos_forward<F32Ops>(d, q, k, v, table, ld_table, Wh, Ww, o, lse, stream);
+  return attn_relpos_forward<F32Ops>(SelfDesc(d).p, q, k, v, table, ld_table, Wh, Ww, o, lse, stream);
 }
 
 extern "C" int gs_attention_backward(const gs_attention_desc* d, const float* q, const float* k,
                                      const float* v, const float* o, const float* lse, const float* d_o,
                                      float* dq, float* dk, float* dv, int accumulate, void* workspace,
                                      size_t workspace_bytes, void* stream) {
+  return attn_backward<F32Ops>(SelfDesc(d).p, q, k, v, o, lse, d_o, dq, dk, dv, accumulate, workspace,
+                               workspace_bytes, 1, stream);
+}
+
+// gs_debug_set_attention_kv_split: >= 1 forces that query split on gs_attention_kv_*, -1 is the plan
+static int g_kv_split = -1;
+
+extern "C" int gs_debug_set_attention_kv_split(int32_t S) {
+  if (S != -1 && S < 1) return GS_E_BADARG;
+  g_kv_split = S;
+  return GS_OK;
+}
+
+extern "C" size_t gs_attention_kv_workspace_bytes(const gs_attention_kv_desc* d) {
+  return attn_workspace_bytes<F32Ops>(d, g_kv_split);
+}
+
+extern "C" int gs_attention_kv_forward(const gs_attention_kv_desc* d, const float* q, const float* k,
+                                       const float* v, float* o, float* lse, void* stream) {
+  return attn_forward<F32Ops>(d, q, k, v, o, lse, stream);
+}
+
+extern "C" int gs_attention_kv_backward(const gs_attention_kv_desc* d, const float* q, const float* k,
+                                        const float* v, const float* o, const float* lse, const float* d_o,
+                                        float* dq, float* dk, float* dv, int accumulate, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
   return attn_backward<F32Ops>(d, q, k, v, o, lse, d_o, dq, dk, dv, accumulate, workspace, workspace_bytes,
-                               stream);
+                               g_kv_split, stream);
 }
 
 extern "C" int gs_vit_tokens_forward(const float* patches, int32_t ldp, const float* cls_token,

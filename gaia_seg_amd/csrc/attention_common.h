@@ -40,6 +40,15 @@
 //                        S^T and dP^T as in the forward, dQ^T += K^T dS^T.
 //              Seven products instead of five, and no sum across workgroups.
 //   padding  : rows past N are staged as zeros and never read from memory, rows past N are not stored.
+//   lengths  : the kernels take the number of queries Nq and of keys Nk separately (AttnArgs): the forward and
+//              dQ own queries and sweep keys, dK / dV owns keys and sweeps queries.  The self-attention
+//              entries run them at Nq = Nk = N; gs_attention_kv_* (the Mix Transformer's attention to a
+//              reduced map, fp32 operands only) at any two lengths.
+//   slabs    : with few keys and many queries the dK / dV grid of one workgroup per 128 keys leaves the chip
+//              idle, so its grid has a slab dimension: S slabs of whole query tiles, each workgroup sweeping
+//              one slab.  S == 1 (always, for the self-attention entries) stores dK / dV directly; S > 1
+//              stores every slab's partial in the workspace and attn_slab_combine_kernel adds the slabs in
+//              slab order: still no atomics and a fixed order.  attn_split_plan chooses S.
 //
 // What a policy supplies (and nothing else differs between the two precisions):
 //   Row                  the operand registers of a row the lane owns, and load_row (with a multiplier);
@@ -99,6 +108,8 @@
 #pragma once
 #include <math.h>
 
+#include <algorithm>
+
 #include "common.h"
 
 namespace gs {
@@ -119,11 +130,14 @@ __device__ __forceinline__ f32x16 zero16() {
 }
 __device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
 
+// Nq queries attend to Nk keys per image (the self-attention entries pass Nq = Nk = N).  slab_rows: the
+// queries one workgroup of the dK / dV kernel sweeps (a multiple of kTK; >= Nq when there is one slab).
 struct AttnArgs {
-  int32_t B, N, heads;
+  int32_t B, Nq, Nk, heads;
   int32_t ldq, ldk, ldv, ldo, lddq, lddk, lddv, lddo;
   float scale;
   int32_t accumulate;
+  int32_t slab_rows;
 };
 
 // BEiT's relative-position bias: one fp32 table [(2 Wh - 1)(2 Ww - 1) + 3][heads] (row pitch ld)
@@ -132,25 +146,27 @@ struct AttnBias {
   int32_t ld, Wh, Ww, R;   // R = (2 Wh - 1)(2 Ww - 1): rows R, R + 1, R + 2 are the three cls entries
 };
 
-// The row this lane owns in a grid (ceil(N / 128), heads, B): lane column l32 of wave's 32 x 32 results,
-// lane half h, row `row` of (batch b, head hd); ok: the row exists (row0 is a row that may be addressed).
+// The row this lane owns in a grid (ceil(n_owned / 128) [x slabs], heads, B): lane column l32 of wave's
+// 32 x 32 results, lane half h, row `row` (tile `tile` of the n_owned queries or keys) of (batch b, head hd);
+// ok: the row exists (row0 is a row that may be addressed).
 struct Owner {
   int l32, h, hd, b, row, row0;
   bool ok;
-  int64_t tok0, stat0;   // the batch's first token; the (batch, head)'s first lse / delta entry
+  int64_t qtok0, ktok0, stat0;   // the batch's first query / key token; the (batch, head)'s first lse / delta
 };
-__device__ __forceinline__ Owner owner(const AttnArgs& a) {
+__device__ __forceinline__ Owner owner(const AttnArgs& a, int n_owned, int tile) {
   Owner w;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   w.l32 = lane & 31;
   w.h = lane >> 5;
   w.hd = blockIdx.y;
   w.b = blockIdx.z;
-  w.row = blockIdx.x * kTQ + wave * 32 + w.l32;
-  w.ok = w.row < a.N;
+  w.row = tile * kTQ + wave * 32 + w.l32;
+  w.ok = w.row < n_owned;
   w.row0 = w.ok ? w.row : 0;
-  w.tok0 = (int64_t)w.b * a.N;
-  w.stat0 = ((int64_t)w.b * a.heads + w.hd) * a.N;
+  w.qtok0 = (int64_t)w.b * a.Nq;
+  w.ktok0 = (int64_t)w.b * a.Nk;
+  w.stat0 = ((int64_t)w.b * a.heads + w.hd) * a.Nq;
   return w;
 }
 
@@ -247,7 +263,7 @@ __device__ __forceinline__ void forward_store(const AttnArgs& a, const Owner& w,
                                               const f32x16& o0, const f32x16& o1, float m, float l) {
   l += __shfl_xor(l, 32, 64);
   if (w.ok) {
-    store_row(O + (w.tok0 + w.row) * a.ldo + w.hd * kD, o0, o1, w.h, 1.0f / l, 0);
+    store_row(O + (w.qtok0 + w.row) * a.ldo + w.hd * kD, o0, o1, w.h, 1.0f / l, 0);
     if (w.h == 0) lse[w.stat0 + w.row] = m + logf(l);
   }
 }
@@ -262,30 +278,30 @@ __global__ __launch_bounds__(256) void attn_forward_kernel(const AttnArgs a, con
   __shared__ typename P::template Tile<false, true> sV;
   __shared__ int sKoff[kBias ? kTK : 1];
   extern __shared__ float sTab[];
-  const Owner w = owner(a);
+  const Owner w = owner(a, a.Nq, blockIdx.x);
   typename P::Row qreg;
-  P::load_row(qreg, Q + (w.tok0 + w.row0) * a.ldq + w.hd * kD, w.ok, w.h, 1.f);
-  const float* Kb = K + w.tok0 * a.ldk + w.hd * kD;
-  const float* Vb = V + w.tok0 * a.ldv + w.hd * kD;
+  P::load_row(qreg, Q + (w.qtok0 + w.row0) * a.ldq + w.hd * kD, w.ok, w.h, 1.f);
+  const float* Kb = K + w.ktok0 * a.ldk + w.hd * kD;
+  const float* Vb = V + w.ktok0 * a.ldv + w.hd * kD;
   f32x16 o0 = zero16(), o1 = zero16();
   float m = -INFINITY, l = 0.f;   // l: the sum over this lane half's keys
   BiasLane bl = {};
   if constexpr (kBias) bl = bias_stage(rb, sTab, w);
   typename P::TileLoad tk, tv;
-  P::load_tile(tk, Kb, 0, a.N, a.ldk);
-  P::load_tile(tv, Vb, 0, a.N, a.ldv);
-  for (int k0 = 0; k0 < a.N; k0 += kTK) {
+  P::load_tile(tk, Kb, 0, a.Nk, a.ldk);
+  P::load_tile(tv, Vb, 0, a.Nk, a.ldv);
+  for (int k0 = 0; k0 < a.Nk; k0 += kTK) {
     __syncthreads();
     P::store_tile(sK, tk, 1.f);
     P::store_tile(sV, tv, 1.f);
-    P::load_tile(tk, Kb, k0 + kTK, a.N, a.ldk);   // the next tile (nothing is read past N)
-    P::load_tile(tv, Vb, k0 + kTK, a.N, a.ldv);
-    if constexpr (kBias) bias_key_offsets(rb, sKoff, k0, a.N);
+    P::load_tile(tk, Kb, k0 + kTK, a.Nk, a.ldk);   // the next tile (nothing is read past Nk)
+    P::load_tile(tv, Vb, k0 + kTK, a.Nk, a.ldv);
+    if constexpr (kBias) bias_key_offsets(rb, sKoff, k0, a.Nk);
     __syncthreads();
     f32x16 s = zero16();   // S^T[key][query]
 #pragma unroll
     for (int st = 0; st < P::kSteps1; ++st) s = P::mma1(sK, w.l32, st, qreg, s, w.h);
-    const float tmax = scores<kBias>(s, a.scale, k0, a.N, w.h, sTab, sKoff, bl);
+    const float tmax = scores<kBias>(s, a.scale, k0, a.Nk, w.h, sTab, sKoff, bl);
     softmax_step(s, tmax, m, l, o0, o1);
 #pragma unroll
     for (int st = 0; st < P::kSteps2; ++st) {   // O^T[d][query] += V^T[d][key] P^T[key][query]
@@ -297,38 +313,45 @@ __global__ __launch_bounds__(256) void attn_forward_kernel(const AttnArgs a, con
   forward_store(a, w, O, lse, o0, o1, m, l);
 }
 
-// the workgroup owns dK and dV of its 128 keys
+// The workgroup owns dK and dV of its 128 keys over one slab of the queries: grid.x = key tiles x slabs
+// (blockIdx.x = slab * key tiles + key tile), slab s = queries [s * slab_rows, min(Nq, (s + 1) * slab_rows)).
+// One slab: dK / dV are stored (= or +=) as they stand.  Several: slab s stores (=) its partial of the
+// image's [Nk][64 * heads] block at dK + s * slab_stride, dV + s * slab_stride (pitches lddk, lddv: the
+// caller points them into the workspace), and attn_slab_combine_kernel sums the slabs in slab order.
 template <class P>
 __global__ __launch_bounds__(256) void attn_backward_dkv_kernel(
     const AttnArgs a, const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
     const float* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ delta,
-    const typename P::GradMax gm, float* dK, float* dV) {
+    const typename P::GradMax gm, float* dK, float* dV, const int ktiles, const int64_t slab_stride) {
   __shared__ typename P::template Tile<true, true> sQ;
   __shared__ typename P::template Tile<true, true> sG;
   __shared__ float sL[kTK];
   __shared__ float sD[kTK];
-  const Owner w = owner(a);
+  const int slab = blockIdx.x / ktiles;
+  const Owner w = owner(a, a.Nk, blockIdx.x - slab * ktiles);
+  const int q_begin = slab * a.slab_rows;
+  const int q_end = (int64_t)q_begin + a.slab_rows < a.Nq ? q_begin + a.slab_rows : a.Nq;   // a ragged tile: Nq
   const int e = P::grad_exponent(gm);
   const float gs = pow2f(e);
   typename P::Row kreg, vreg;
-  P::load_row(kreg, K + (w.tok0 + w.row0) * a.ldk + w.hd * kD, w.ok, w.h, 1.f);
-  P::load_row(vreg, V + (w.tok0 + w.row0) * a.ldv + w.hd * kD, w.ok, w.h, 1.f);
-  const float* Qb = Q + w.tok0 * a.ldq + w.hd * kD;
-  const float* Gb = dO + w.tok0 * a.lddo + w.hd * kD;
+  P::load_row(kreg, K + (w.ktok0 + w.row0) * a.ldk + w.hd * kD, w.ok, w.h, 1.f);
+  P::load_row(vreg, V + (w.ktok0 + w.row0) * a.ldv + w.hd * kD, w.ok, w.h, 1.f);
+  const float* Qb = Q + w.qtok0 * a.ldq + w.hd * kD;
+  const float* Gb = dO + w.qtok0 * a.lddo + w.hd * kD;
   const float* Lb = lse + w.stat0;
   const float* Db = delta + w.stat0;
   f32x16 dk0 = zero16(), dk1 = zero16(), dv0 = zero16(), dv1 = zero16();
   typename P::TileLoad tq, tg;
-  P::load_tile(tq, Qb, 0, a.N, a.ldq);
-  P::load_tile(tg, Gb, 0, a.N, a.lddo);
-  for (int q0 = 0; q0 < a.N; q0 += kTK) {
+  P::load_tile(tq, Qb, q_begin, q_end, a.ldq);
+  P::load_tile(tg, Gb, q_begin, q_end, a.lddo);
+  for (int q0 = q_begin; q0 < q_end; q0 += kTK) {
     __syncthreads();
     P::store_tile(sQ, tq, 1.f);
     P::store_tile(sG, tg, gs);
-    P::load_tile(tq, Qb, q0 + kTK, a.N, a.ldq);   // the next tile (nothing is read past N)
-    P::load_tile(tg, Gb, q0 + kTK, a.N, a.lddo);
+    P::load_tile(tq, Qb, q0 + kTK, q_end, a.ldq);   // the next tile (nothing is read past the slab)
+    P::load_tile(tg, Gb, q0 + kTK, q_end, a.lddo);
     if (threadIdx.x < kTK) {
-      const bool ok = q0 + (int)threadIdx.x < a.N;
+      const bool ok = q0 + (int)threadIdx.x < q_end;
       sL[threadIdx.x] = ok ? Lb[q0 + threadIdx.x] : 0.f;
       sD[threadIdx.x] = ok ? Db[q0 + threadIdx.x] * gs : 0.f;
     }
@@ -342,7 +365,7 @@ __global__ __launch_bounds__(256) void attn_backward_dkv_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int qq = acc_row(r, w.h);
-      const float p = (q0 + qq < a.N) ? expf(__fmul_rn(s[r], a.scale) - sL[qq]) : 0.f;
+      const float p = (q0 + qq < q_end) ? expf(__fmul_rn(s[r], a.scale) - sL[qq]) : 0.f;
       s[r] = p;
       dp[r] = p * (dp[r] - sD[qq]);
     }
@@ -357,8 +380,9 @@ __global__ __launch_bounds__(256) void attn_backward_dkv_kernel(
   }
   if (w.ok) {
     const float inv = pow2f(-e);
-    store_row(dK + (w.tok0 + w.row) * a.lddk + w.hd * kD, dk0, dk1, w.h, a.scale * inv, a.accumulate);
-    store_row(dV + (w.tok0 + w.row) * a.lddv + w.hd * kD, dv0, dv1, w.h, inv, a.accumulate);
+    const int64_t at = slab * slab_stride + w.ktok0 + w.row;
+    store_row(dK + at * a.lddk + w.hd * kD, dk0, dk1, w.h, a.scale * inv, a.accumulate);
+    store_row(dV + at * a.lddv + w.hd * kD, dv0, dv1, w.h, inv, a.accumulate);
   }
 }
 
@@ -370,26 +394,26 @@ __global__ __launch_bounds__(256) void attn_backward_dq_kernel(
     const typename P::GradMax gm, float* dQ) {
   __shared__ typename P::template Tile<true, true> sK;
   __shared__ typename P::template Tile<true, false> sV;
-  const Owner w = owner(a);
+  const Owner w = owner(a, a.Nq, blockIdx.x);
   const int e = P::grad_exponent(gm);
   const float gs = pow2f(e);
   typename P::Row qreg, greg;
-  P::load_row(qreg, Q + (w.tok0 + w.row0) * a.ldq + w.hd * kD, w.ok, w.h, 1.f);
-  P::load_row(greg, dO + (w.tok0 + w.row0) * a.lddo + w.hd * kD, w.ok, w.h, gs);
+  P::load_row(qreg, Q + (w.qtok0 + w.row0) * a.ldq + w.hd * kD, w.ok, w.h, 1.f);
+  P::load_row(greg, dO + (w.qtok0 + w.row0) * a.lddo + w.hd * kD, w.ok, w.h, gs);
   const float lse_q = w.ok ? lse[w.stat0 + w.row0] : 0.f;
   const float delta_q = w.ok ? delta[w.stat0 + w.row0] * gs : 0.f;
-  const float* Kb = K + w.tok0 * a.ldk + w.hd * kD;
-  const float* Vb = V + w.tok0 * a.ldv + w.hd * kD;
+  const float* Kb = K + w.ktok0 * a.ldk + w.hd * kD;
+  const float* Vb = V + w.ktok0 * a.ldv + w.hd * kD;
   f32x16 dq0 = zero16(), dq1 = zero16();
   typename P::TileLoad tk, tv;
-  P::load_tile(tk, Kb, 0, a.N, a.ldk);
-  P::load_tile(tv, Vb, 0, a.N, a.ldv);
-  for (int k0 = 0; k0 < a.N; k0 += kTK) {
+  P::load_tile(tk, Kb, 0, a.Nk, a.ldk);
+  P::load_tile(tv, Vb, 0, a.Nk, a.ldv);
+  for (int k0 = 0; k0 < a.Nk; k0 += kTK) {
     __syncthreads();
     P::store_tile(sK, tk, 1.f);
     P::store_tile(sV, tv, 1.f);
-    P::load_tile(tk, Kb, k0 + kTK, a.N, a.ldk);   // the next tile (nothing is read past N)
-    P::load_tile(tv, Vb, k0 + kTK, a.N, a.ldv);
+    P::load_tile(tk, Kb, k0 + kTK, a.Nk, a.ldk);   // the next tile (nothing is read past Nk)
+    P::load_tile(tv, Vb, k0 + kTK, a.Nk, a.ldv);
     __syncthreads();
     f32x16 s = zero16(), dp = zero16();   // S^T[key][query], dP^T[key][query]
 #pragma unroll
@@ -399,7 +423,7 @@ __global__ __launch_bounds__(256) void attn_backward_dq_kernel(
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float p = (k0 + acc_row(r, w.h) < a.N) ? expf(__fmul_rn(s[r], a.scale) - lse_q) : 0.f;
+      const float p = (k0 + acc_row(r, w.h) < a.Nk) ? expf(__fmul_rn(s[r], a.scale) - lse_q) : 0.f;
       dp[r] = p * (dp[r] - delta_q);
     }
 #pragma unroll
@@ -410,13 +434,50 @@ __global__ __launch_bounds__(256) void attn_backward_dq_kernel(
     }
   }
   if (w.ok)
-    store_row(dQ + (w.tok0 + w.row) * a.lddq + w.hd * kD, dq0, dq1, w.h, a.scale * pow2f(-e), a.accumulate);
+    store_row(dQ + (w.qtok0 + w.row) * a.lddq + w.hd * kD, dq0, dq1, w.h, a.scale * pow2f(-e), a.accumulate);
+}
+
+
+// dK / dV = (or +=) the sum over the slabs, in slab order, of the partials the dK / dV kernel left in the
+// workspace: part = dK partials [slabs][rows][4 c4] then dV partials in the same shape.  One thread per four
+// columns of a key row of dK or dV: a fixed order, no atomics.
+__global__ __launch_bounds__(256) void attn_slab_combine_kernel(const float* __restrict__ part, float* dK,
+                                                                float* dV, const int64_t rows, const int c4,
+                                                                const int slabs, const int lddk, const int lddv,
+                                                                const int accumulate) {
+  const int64_t per = rows * c4, items = 2 * per;
+  for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (int64_t)gridDim.x * 256) {
+    const bool is_v = it >= per;
+    const int64_t at = is_v ? it - per : it;
+    const int64_t row = at / c4;
+    const int cq = (int)(at - row * c4);
+    const float* src = part + (is_v ? (int64_t)slabs * per * 4 : 0) + at * 4;
+    f32x4 sum = ld4(src);
+    for (int sl = 1; sl < slabs; ++sl) sum += ld4(src + (int64_t)sl * per * 4);
+    float* dst = is_v ? dV + row * lddv + cq * 4 : dK + row * lddk + cq * 4;
+    if (accumulate) sum += ld4(dst);
+    st4(dst, sum);
+  }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-int attn_check(const gs_attention_desc* d) {
+// Every entry runs on a gs_attention_kv_desc; the self-attention entries pass theirs through SelfDesc.
+struct SelfDesc {
+  gs_attention_kv_desc kv;
+  const gs_attention_kv_desc* p;
+  explicit SelfDesc(const gs_attention_desc* d) : kv(), p(nullptr) {
+    if (!d) return;
+    kv.B = d->B; kv.Nq = d->N; kv.Nk = d->N; kv.heads = d->heads;
+    kv.ldq = d->ldq; kv.ldk = d->ldk; kv.ldv = d->ldv; kv.ldo = d->ldo;
+    kv.lddq = d->lddq; kv.lddk = d->lddk; kv.lddv = d->lddv; kv.lddo = d->lddo;
+    kv.scale = d->scale;
+    p = &kv;
+  }
+};
+
+int attn_check(const gs_attention_kv_desc* d) {
   if (!d) return GS_E_NULL;
-  if (d->B <= 0 || d->N <= 0 || d->heads <= 0 || !(d->scale > 0.f)) return GS_E_BADARG;
+  if (d->B <= 0 || d->Nq <= 0 || d->Nk <= 0 || d->heads <= 0 || !(d->scale > 0.f)) return GS_E_BADARG;
   if (d->B > 65535 || d->heads > 65535 || d->heads > INT32_MAX / kD) return GS_E_BADARG;
   const int32_t ld[8] = {d->ldq, d->ldk, d->ldv, d->ldo, d->lddq, d->lddk, d->lddv, d->lddo};
   for (int i = 0; i < 8; ++i)
@@ -427,35 +488,76 @@ int attn_check(const gs_attention_desc* d) {
 }
 
 // what gs_attention_relpos_forward checks beyond attn_check, before the pointers
-int attn_relpos_check(const gs_attention_desc* d, int32_t ld_table, int32_t Wh, int32_t Ww) {
-  if (Wh < 1 || Ww < 1 || (int64_t)Wh * Ww + 1 != d->N || ld_table < d->heads) return GS_E_BADARG;
+int attn_relpos_check(const gs_attention_kv_desc* d, int32_t ld_table, int32_t Wh, int32_t Ww) {
+  if (d->Nq != d->Nk) return GS_E_BADARG;
+  if (Wh < 1 || Ww < 1 || (int64_t)Wh * Ww + 1 != d->Nq || ld_table < d->heads) return GS_E_BADARG;
   const int64_t R = (2 * (int64_t)Wh - 1) * (2 * (int64_t)Ww - 1);
   return R + 3 > GS_ATTENTION_RELPOS_MAX_ROWS ? GS_E_BADARG : GS_OK;
 }
 
-AttnArgs attn_args(const gs_attention_desc* d, int accumulate) {
+// How the dK / dV kernel splits the queries: `slabs` slabs of slab_rows queries each (a multiple of kTK; the
+// last one may be shorter; no slab is empty).
+struct AttnSplit {
+  int32_t slabs, slab_rows;
+};
+// the split nearest to `want` slabs that has whole tiles per slab
+inline AttnSplit attn_split(const gs_attention_kv_desc* d, int64_t want) {
+  const int64_t qtiles = ceil_div(d->Nq, kTK), ktiles = ceil_div(d->Nk, kTQ);
+  want = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, qtiles), INT32_MAX / ktiles));
+  const int64_t per = ceil_div(qtiles, want);
+  const int64_t slabs = ceil_div(qtiles, per);
+  return AttnSplit{(int32_t)slabs, slabs == 1 ? d->Nq : (int32_t)(per * kTK)};
+}
+// The planned split of gs_attention_kv_backward, a pure function of the descriptor and the CU count.  The
+// dK / dV kernel's 210 VGPRs and 64 AGPRs (two owned rows, four accumulators, two score tiles) leave one wave
+// per SIMD, so a CU holds ONE workgroup: the key tiles x heads x B workgroups are multiplied by query slabs
+// until they fill one round of those CU places, and not past it -- measured (profiles/r23_segformer.md), the
+// whole backward is fastest there at three of the recipe's four stage shapes (40 workgroups of stage 3: S = 4 /
+// 6 / 8 / 16 take 224 / 197 / 233 / 212 us) and within the spread between runs of twice as many slabs at
+// the fourth, where it halves the workspace.  No slab gets fewer than kMinSlabTiles query tiles: a slab's partial pair of [128][64] dK /
+// dV blocks, stored and read again by the combine, is as many bytes as four query tiles of Q and dO.
+constexpr int kMinSlabTiles = 4;
+inline AttnSplit attn_split_plan(const gs_attention_kv_desc* d) {
+  const int64_t wgs = ceil_div(d->Nk, kTQ) * d->heads * d->B;
+  const int64_t by_places = (int64_t)num_cu() / wgs;
+  const int64_t by_work = ceil_div(d->Nq, kTK) / kMinSlabTiles;
+  return attn_split(d, std::min(by_places, by_work));
+}
+
+AttnArgs attn_args(const gs_attention_kv_desc* d, int accumulate) {
   AttnArgs a;
-  a.B = d->B; a.N = d->N; a.heads = d->heads;
+  a.B = d->B; a.Nq = d->Nq; a.Nk = d->Nk; a.heads = d->heads;
   a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv; a.ldo = d->ldo;
   a.lddq = d->lddq; a.lddk = d->lddk; a.lddv = d->lddv; a.lddo = d->lddo;
   a.scale = d->scale;
   a.accumulate = accumulate ? 1 : 0;
+  a.slab_rows = d->Nq;
   return a;
 }
 
-inline int64_t attn_tiles(const gs_attention_desc* d) { return ceil_div(d->N, kTQ); }
-inline dim3 attn_grid(const gs_attention_desc* d) {
+// workgroups that own 128 queries each: the forward, dQ and the fp16 delta pre-pass
+inline int64_t attn_tiles(const gs_attention_kv_desc* d) { return ceil_div(d->Nq, kTQ); }
+inline dim3 attn_grid(const gs_attention_kv_desc* d) {
   return dim3((unsigned)attn_tiles(d), (unsigned)d->heads, (unsigned)d->B);
+}
+
+// the backward's workspace: what the policy's pre-pass leaves (delta first), then the slabs' partials
+// [2][slabs][B * Nk][64 * heads] when there is more than one slab
+template <class P>
+size_t attn_ws_bytes(const gs_attention_kv_desc* d, const AttnSplit& sp) {
+  const size_t part = (size_t)2 * sp.slabs * d->B * d->Nk * kD * d->heads * sizeof(float);
+  return P::ws_bytes(d) + (sp.slabs > 1 ? part : 0);
 }
 
 // Errors are reported in this order: descriptor, relpos arguments, NULL, alignment, workspace.
 template <class P>
-size_t attn_workspace_bytes(const gs_attention_desc* d) {
-  return attn_check(d) == GS_OK ? P::ws_bytes(d) : 0;
+size_t attn_workspace_bytes(const gs_attention_kv_desc* d, int64_t want_slabs) {
+  if (attn_check(d) != GS_OK) return 0;
+  return attn_ws_bytes<P>(d, want_slabs > 0 ? attn_split(d, want_slabs) : attn_split_plan(d));
 }
 
 template <class P>
-int attn_forward(const gs_attention_desc* d, const float* q, const float* k, const float* v, float* o,
+int attn_forward(const gs_attention_kv_desc* d, const float* q, const float* k, const float* v, float* o,
                  float* lse, void* stream) {
   const int rc = attn_check(d);
   if (rc != GS_OK) return rc;
@@ -467,7 +569,7 @@ int attn_forward(const gs_attention_desc* d, const float* q, const float* k, con
 }
 
 template <class P>
-int attn_relpos_forward(const gs_attention_desc* d, const float* q, const float* k, const float* v,
+int attn_relpos_forward(const gs_attention_kv_desc* d, const float* q, const float* k, const float* v,
                         const float* table, int32_t ld_table, int32_t Wh, int32_t Ww, float* o, float* lse,
                         void* stream) {
   int rc = attn_check(d);
@@ -483,20 +585,39 @@ int attn_relpos_forward(const gs_attention_desc* d, const float* q, const float*
   return launch_status();
 }
 
+// want_slabs: the query split of the dK / dV kernel -- 1 for the self-attention entries (one slab, stored
+// directly), <= 0 for the plan
 template <class P>
-int attn_backward(const gs_attention_desc* d, const float* q, const float* k, const float* v, const float* o,
+int attn_backward(const gs_attention_kv_desc* d, const float* q, const float* k, const float* v, const float* o,
                   const float* lse, const float* d_o, float* dq, float* dk, float* dv, int accumulate,
-                  void* workspace, size_t workspace_bytes, void* stream) {
+                  void* workspace, size_t workspace_bytes, int64_t want_slabs, void* stream) {
   const int rc = attn_check(d);
   if (rc != GS_OK) return rc;
   if (any_null({q, k, v, o, lse, d_o, dq, dk, dv, workspace})) return GS_E_NULL;
   if (!all_aligned16({q, k, v, o, lse, d_o, dq, dk, dv, workspace})) return GS_E_ALIGN;
-  if (workspace_bytes < P::ws_bytes(d)) return GS_E_WORKSPACE;
+  const AttnSplit sp = want_slabs > 0 ? attn_split(d, want_slabs) : attn_split_plan(d);
+  if (workspace_bytes < attn_ws_bytes<P>(d, sp)) return GS_E_WORKSPACE;
   const AttnArgs a = attn_args(d, accumulate);
   float* delta = static_cast<float*>(workspace);
   const typename P::GradMax gm = P::launch_delta(d, a, d_o, o, delta, as_stream(stream));
-  hipLaunchKernelGGL(attn_backward_dkv_kernel<P>, attn_grid(d), dim3(256), 0, as_stream(stream), a, q, k, v,
-                     d_o, lse, delta, gm, dk, dv);
+  const int ktiles = (int)ceil_div(d->Nk, kTQ);
+  const dim3 kgrid((unsigned)(ktiles * sp.slabs), (unsigned)d->heads, (unsigned)d->B);
+  if (sp.slabs == 1) {
+    hipLaunchKernelGGL(attn_backward_dkv_kernel<P>, kgrid, dim3(256), 0, as_stream(stream), a, q, k, v, d_o, lse,
+                       delta, gm, dk, dv, ktiles, (int64_t)0);
+  } else {
+    AttnArgs ap = a;   // the partials: packed rows, plain stores
+    ap.slab_rows = sp.slab_rows;
+    ap.lddk = ap.lddv = kD * d->heads;
+    ap.accumulate = 0;
+    const int64_t rows = (int64_t)d->B * d->Nk;
+    float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + P::ws_bytes(d));
+    hipLaunchKernelGGL(attn_backward_dkv_kernel<P>, kgrid, dim3(256), 0, as_stream(stream), ap, q, k, v, d_o,
+                       lse, delta, gm, part, part + (int64_t)sp.slabs * rows * ap.lddk, ktiles, rows);
+    hipLaunchKernelGGL(attn_slab_combine_kernel, dim3(stream_grid(2 * rows * (ap.lddk / 4), 256)), dim3(256), 0,
+                       as_stream(stream), part, dk, dv, rows, ap.lddk / 4, (int)sp.slabs, (int)d->lddk,
+                       (int)d->lddv, a.accumulate);
+  }
   hipLaunchKernelGGL(attn_backward_dq_kernel<P>, attn_grid(d), dim3(256), 0, as_stream(stream), a, q, k, v,
                      d_o, lse, delta, gm, dq);
   return launch_status();

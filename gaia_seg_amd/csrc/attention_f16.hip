@@ -20,9 +20,9 @@ __global__ __launch_bounds__(256) void attn_delta_f16_kernel(const AttnArgs a, c
   const int hd = blockIdx.y, b = blockIdx.z;
   const int tok = blockIdx.x * kTQ + (threadIdx.x >> 1), half = threadIdx.x & 1;
   float acc = 0.f, amax = 0.f;
-  if (tok < a.N) {
-    const float* g = dO + ((int64_t)b * a.N + tok) * a.lddo + hd * kD + 32 * half;
-    const float* o = O + ((int64_t)b * a.N + tok) * a.ldo + hd * kD + 32 * half;
+  if (tok < a.Nq) {
+    const float* g = dO + ((int64_t)b * a.Nq + tok) * a.lddo + hd * kD + 32 * half;
+    const float* o = O + ((int64_t)b * a.Nq + tok) * a.ldo + hd * kD + 32 * half;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const f32x4 x = ld4(g + c * 4), y = ld4(o + c * 4);
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void attn_delta_f16_kernel(const AttnArgs a, c
     }
   }
   const float other = __shfl_xor(acc, 1, 64);
-  if (tok < a.N && half == 0) delta[((int64_t)b * a.heads + hd) * a.N + tok] = acc + other;
+  if (tok < a.Nq && half == 0) delta[((int64_t)b * a.heads + hd) * a.Nq + tok] = acc + other;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
   if ((threadIdx.x & 63) == 0) sMax[threadIdx.x >> 6] = amax;
@@ -171,13 +171,13 @@ struct F16Ops {
   }
 
   // delta[B][heads][N], then max|dO| of each of the pre-pass's B * heads * ceil(N / 128) workgroups
-  static size_t ws_bytes(const gs_attention_desc* d) {
-    const int64_t floats = (int64_t)d->B * d->heads * (d->N + attn_tiles(d));
+  static size_t ws_bytes(const gs_attention_kv_desc* d) {
+    const int64_t floats = (int64_t)d->B * d->heads * (d->Nq + attn_tiles(d));
     return (size_t)ceil_div(floats * (int64_t)sizeof(float), 16) * 16;
   }
-  static GradMax launch_delta(const gs_attention_desc* d, const AttnArgs& a, const float* d_o, const float* o,
+  static GradMax launch_delta(const gs_attention_kv_desc* d, const AttnArgs& a, const float* d_o, const float* o,
                               float* delta, hipStream_t stream) {
-    float* gmax = delta + (int64_t)d->B * d->heads * d->N;
+    float* gmax = delta + (int64_t)d->B * d->heads * d->Nq;
     hipLaunchKernelGGL(attn_delta_f16_kernel, attn_grid(d), dim3(256), 0, stream, a, d_o, o, delta, gmax);
     return GradMax{gmax, (int64_t)d->B * d->heads * attn_tiles(d)};
   }
@@ -203,24 +203,24 @@ struct F16Ops::Tile<true, true> {
 using namespace gs;
 
 extern "C" size_t gs_attention_workspace_bytes_f16(const gs_attention_desc* d) {
-  return attn_workspace_bytes<F16Ops>(d);
+  return attn_workspace_bytes<F16Ops>(SelfDesc(d).p, 1);
 }
 
 extern "C" int gs_attention_forward_f16(const gs_attention_desc* d, const float* q, const float* k,
                                         const float* v, float* o, float* lse, void* stream) {
-  return attn_forward<F16Ops>(d, q, k, v, o, lse, stream);
+  return attn_forward<F16Ops>(SelfDesc(d).p, q, k, v, o, lse, stream);
 }
 
 extern "C" int gs_attention_relpos_forward_f16(const gs_attention_desc* d, const float* q, const float* k,
                                                const float* v, const float* table, int32_t ld_table,
                                                int32_t Wh, int32_t Ww, float* o, float* lse, void* stream) {
-  return attn_relpos_forward<F16Ops>(d, q, k, v, table, ld_table, Wh, Ww, o, lse, stream);
+  return attn_relpos_forward<F16Ops>(SelfDesc(d).p, q, k, v, table, ld_table, Wh, Ww, o, lse, stream);
 }
 
 extern "C" int gs_attention_backward_f16(const gs_attention_desc* d, const float* q, const float* k,
                                          const float* v, const float* o, const float* lse, const float* d_o,
                                          float* dq, float* dk, float* dv, int accumulate, void* workspace,
                                          size_t workspace_bytes, void* stream) {
-  return attn_backward<F16Ops>(d, q, k, v, o, lse, d_o, dq, dk, dv, accumulate, workspace, workspace_bytes,
-                               stream);
+  return attn_backward<F16Ops>(SelfDesc(d).p, q, k, v, o, lse, d_o, dq, dk, dv, accumulate, workspace,
+                               workspace_bytes, 1, stream);
 }

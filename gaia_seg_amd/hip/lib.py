@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 class HipLibraryError(RuntimeError):
@@ -106,6 +106,25 @@ def attention_desc(b, n, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=None, ldk=
     defaults to 64 * heads, a gradient's pitch to the pitch of its forward operand."""
     d = AttentionDesc()
     d.B, d.N, d.heads, d.scale = b, n, heads, scale
+    c = ATTENTION_HEAD_DIM * heads
+    d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
+    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
+                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    return d
+
+
+class AttentionKvDesc(Structure):
+    """Mirror of ``gs_attention_kv_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("B", "Nq", "Nk", "heads", "ldq", "ldk", "ldv", "ldo", "lddq", "lddk",
+                                        "lddv", "lddo")] + [("scale", c_float)])
+
+
+def attention_kv_desc(b, nq, nk, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=None, ldk=None, ldv=None, ldo=None,
+                      lddq=None, lddk=None, lddv=None, lddo=None):
+    """An ``AttentionKvDesc`` for ``b`` images of ``nq`` queries and ``nk`` keys and ``heads`` active heads;
+    pitches default as in ``attention_desc``."""
+    d = AttentionKvDesc()
+    d.B, d.Nq, d.Nk, d.heads, d.scale = b, nq, nk, heads, scale
     c = ATTENTION_HEAD_DIM * heads
     d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
     d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
@@ -318,6 +337,7 @@ _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 _DW = POINTER(DwConvDesc)
 _LN = POINTER(LayerNormDesc)
 _AT = POINTER(AttentionDesc)
+_AK = POINTER(AttentionKvDesc)
 _FD = POINTER(FcuDownDesc)
 _OG, _OA = POINTER(OcrGatherDesc), POINTER(OcrAttendDesc)
 
@@ -353,6 +373,10 @@ PROTOTYPES = {
     "gs_attention_relpos_forward_f16": (_i32, [_AT, _P, _P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
     "gs_attention_workspace_bytes_f16": (_sz, [_AT]),
     "gs_attention_backward_f16": (_i32, [_AT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_attention_kv_forward": (_i32, [_AK, _P, _P, _P, _P, _P, _P]),
+    "gs_attention_kv_workspace_bytes": (_sz, [_AK]),
+    "gs_attention_kv_backward": (_i32, [_AK, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_debug_set_attention_kv_split": (_i32, [_i32]),
     "gs_vit_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_vit_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_fcu_down_workspace_bytes": (_sz, [_FD]),

@@ -957,6 +957,48 @@ def attention(tape, q, k, v, heads, scale, out=None, f16=False):
     return out
 
 
+def attention_kv(tape, q, k, v, heads, scale, out=None):
+    """Multi-head softmax attention of every pixel of ``q`` [B, Hq, Wq, 64 * heads] to the pixels of ``k`` and
+    ``v`` [B, Hk, Wk, 64 * heads] (the Mix Transformer's spatial-reduction attention: k and v come from a
+    reduced map; two column slices of one buffer are fine).  fp32 operands in every precision mode (there is
+    no fp16-operand form).  No Nq x Nk matrix is stored; the backward's workspace (delta and, where the dK /
+    dV kernel splits the queries, the slabs' partials) comes from the pool."""
+    L = _L()
+    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
+    c = _lib.ATTENTION_HEAD_DIM * heads
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.C != c or t.N != q.N or (name != "q" and (t.H, t.W) != (k.H, k.W)):
+            raise ValueError("attention_kv: %s is %s, expected [%d, H, W, %d] for %d heads (k and v of one size)"
+                             % (name, tuple(t.t.shape), q.N, c, heads))
+    b, nq, nk, dev = q.N, q.H * q.W, k.H * k.W, q.t.device
+    if out is None:
+        out = Act.empty(b, q.H, q.W, c, dev)
+    lse = torch.empty(b * heads * nq, dtype=torch.float32, device=dev)
+    d = _lib.attention_kv_desc(b, nq, nk, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    _lib.check(L.gs_attention_kv_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(),
+                                         current_stream_ptr()), "gs_attention_kv_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad):
+            return
+        accs = [_input_grad(t) for t in (q, k, v)]
+        if any(accs) and not all(accs):   # one flag for the three: start the fresh ones from zero
+            for t, acc in zip((q, k, v), accs):
+                if not acc:
+                    t.g.zero_()
+        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        db = ctypes.byref(d)
+        ws = _ws.get(L.gs_attention_kv_workspace_bytes(db), dev)
+        _lib.check(L.gs_attention_kv_backward(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(),
+                                              q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(),
+                                              1 if any(accs) else 0, ws.data_ptr(), ws.numel(),
+                                              current_stream_ptr()), "gs_attention_kv_backward")
+
+    tape.record(backward)
+    return out
+
+
 def _forward_only(tape, what, *inputs):
     if tape.enabled and any(t.requires_grad for t in inputs):
         raise NotImplementedError("%s: forward only (no backward kernel); called with a recording tape and an "

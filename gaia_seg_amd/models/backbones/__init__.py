@@ -3,3 +3,4 @@ from .dynamic_convnext import DynamicConvNeXt  # noqa: F401
 from .elastic_transformer import ElasticTransformer  # noqa: F401
 from .beit import BEiT  # noqa: F401
 from .elastic_convformer import ElasticConvformer  # noqa: F401
+from .dynamic_mit import DynamicMixVisionTransformer  # noqa: F401

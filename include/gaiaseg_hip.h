@@ -295,6 +295,39 @@ size_t gs_attention_workspace_bytes_f16(const gs_attention_desc* d);
 int gs_attention_backward_f16(const gs_attention_desc* d, const float* q, const float* k, const float* v,
                               const float* o, const float* lse, const float* d_o, float* dq, float* dk,
                               float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* Attention with separate query and key lengths (the spatial-reduction attention of SegFormer's Mix
+ * Transformer: all Nq tokens of a stage attend to the Nk tokens of a map reduced by sr_ratio):
+ *   O[b,i,h,:] = sum_{j < Nk} softmax_j(scale * <Q[b,i,h,:], K[b,j,h,:]>) V[b,j,h,:],   i < Nq.
+ * Q, O, dQ, dO are [B*Nq] rows, K, V, dK, dV are [B*Nk] rows, lse is [B][heads][Nq]; everything else is the
+ * contract of gs_attention_* above, and these ARE those kernels (csrc/attention_common.h) with the owned and
+ * the swept length taken from different fields: exact fp32 MFMA, online softmax (no Nq x Nk matrix), no float
+ * atomics, a fixed summation order (bit-identical from run to run), nothing written outside the active
+ * columns and rows, rows past Nq or Nk staged as zeros and never read, a key past Nk scores -inf.  Any
+ * Nq >= 1 and Nk >= 1 is legal, Nk > Nq too.  With Nq == Nk and a forced split of 1 every output equals
+ * gs_attention_* bit for bit.  The same host-side checks and codes, applied to both lengths.
+ * Backward: dQ as in gs_attention_backward (a workgroup owns 128 queries and sweeps the keys).  dK / dV: a
+ * workgroup owns 128 keys and sweeps one SLAB of the queries; the grid has a slab dimension S.  S == 1
+ * stores dK / dV directly.  S > 1: every slab (whole 32-row tiles of queries; none is empty) writes its
+ * [B*Nk][64 * heads] partials of dK and dV into the workspace and a second launch sums them in slab order
+ * into dK / dV (= or +=).  S is a pure function of the descriptor and the device's CU count: the key tiles
+ * x heads x B workgroups are multiplied until they fill one round of the CUs (the kernel runs one workgroup
+ * per CU), with at least 4 query tiles per slab.  The workspace is delta[B][heads][Nq] (rounded up to 16 bytes) followed by
+ * the partials [2][S][B*Nk][64 * heads] when S > 1.
+ * gs_debug_set_attention_kv_split(S >= 1) forces the split (clipped to what gives whole, non-empty slabs) for
+ * the workspace query and the backward alike; -1 restores the plan; anything else is GS_E_BADARG. */
+typedef struct gs_attention_kv_desc {
+  int32_t B, Nq, Nk, heads;         /* batch, queries and keys per image, ACTIVE heads           */
+  int32_t ldq, ldk, ldv, ldo;       /* token pitches of Q, K, V, O                               */
+  int32_t lddq, lddk, lddv, lddo;   /* token pitches of dQ, dK, dV, dO (all eight are checked)   */
+  float scale;
+} gs_attention_kv_desc;
+int gs_attention_kv_forward(const gs_attention_kv_desc* d, const float* q, const float* k, const float* v,
+                            float* o, float* lse, void* stream);
+size_t gs_attention_kv_workspace_bytes(const gs_attention_kv_desc* d);
+int gs_attention_kv_backward(const gs_attention_kv_desc* d, const float* q, const float* k, const float* v,
+                             const float* o, const float* lse, const float* d_o, float* dq, float* dk,
+                             float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int gs_debug_set_attention_kv_split(int32_t S);
 /* ElasticTransformer's token assembly on the leading D columns: from patches [B*T][D] (pitch ldp),
  * cls_token[:D] and pos_embed[:T+1, :D] (pitch ldpos, the max-size embedding width),
  *   x[b,0,:] = cls_token + pos_embed[0],   x[b,1+t,:] = patches[b,t] + pos_embed[1+t]      (x: [B*(T+1)][D]).
