@@ -131,6 +131,44 @@ def mit_backbone_flops(backbone, h, w, in_channels=3):
     return total, params, 0.0, feats
 
 
+def swin_backbone_flops(backbone, h, w, in_channels=3):
+    """backbone_flops for a DynamicSwinTransformer: (flops per image, params, 0.0, feature shapes).  It counts
+    what runs: q / k / v and the attention on the map padded to the window (every token attends to ws^2 keys: 2
+    products x 2 * Hp Wp * ws^2 * 32 heads), o_proj and the MLP on the cropped map, the merge as its 2x2 stride-2
+    conv.  (Published Swin counts put o_proj on the padded map too; here it runs after the crop, so its term is
+    smaller wherever a stage pads.)  Params are those of the active subnet (swin.layernorm, which nothing reads,
+    is not counted)."""
+    ws = backbone.window_size
+    emb = backbone.swin.embeddings
+    total, params, c, h, w = _conv(emb.patch_embeddings.projection, in_channels, h, w)
+    params += 2 * c                                       # embeddings.norm
+    feats = []
+    for i, stage in enumerate(backbone.stages):
+        hp, wp = -(-h // ws) * ws, -(-w // ws) * ws
+        for blk in stage.active_blocks():
+            att = blk.attention
+            params += 4 * c + (2 * ws - 1) ** 2 * att.num_heads      # the two LayerNorms, the table's active part
+            for lin, (lh, lw) in ((att.q_proj, (hp, wp)), (att.k_proj, (hp, wp)), (att.v_proj, (hp, wp)),
+                                  (att.o_proj, (h, w))):
+                f, p, _, _, _ = _conv(lin, c, lh, lw)
+                total += f
+                params += p
+            total += 4.0 * hp * wp * ws * ws * 32 * att.num_heads
+            f1, p1, hidden, _, _ = _conv(blk.mlp.fc1, c, h, w)
+            f2, p2, _, _, _ = _conv(blk.mlp.fc2, hidden, h, w)
+            total += f1 + f2
+            params += p1 + p2
+        if i in backbone.out_indices:
+            feats.append((c, h, w))
+            params += 2 * c                               # hidden_states_norms.stage{i+1}
+        if stage.downsample is not None:
+            params += 2 * 4 * c                           # the merge's LayerNorm over 4 C
+            f, p, c, h, w = _conv(stage.downsample.reduction, c, h, w)
+            total += f
+            params += p
+    return total, params, 0.0, feats
+
+
 def _trans_block(blk, n, d):
     """(flops per image, params) of an Elastic_trans_Block on n tokens of width d"""
     heads = blk.attn.num_heads
@@ -219,6 +257,8 @@ def backbone_flops(backbone, h, w, in_channels=3):
         return convformer_backbone_flops(backbone, h, w, in_channels)
     if type(backbone).__name__ == "DynamicMixVisionTransformer":
         return mit_backbone_flops(backbone, h, w, in_channels)
+    if type(backbone).__name__ == "DynamicSwinTransformer":
+        return swin_backbone_flops(backbone, h, w, in_channels)
     total = params = k3 = 0.0
     c = in_channels
     if backbone.deep_stem:

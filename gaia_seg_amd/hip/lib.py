@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class HipLibraryError(RuntimeError):
@@ -129,6 +129,45 @@ def attention_kv_desc(b, nq, nk, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=No
     d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
     d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
                                       ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    return d
+
+
+class WindowAttentionDesc(Structure):
+    """Mirror of ``gs_window_attention_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("B", "H", "W", "ws", "shift", "heads", "ldq", "ldk", "ldv", "ldo", "lddq",
+                                        "lddk", "lddv", "lddo", "ld_table")] + [("scale", c_float)])
+
+
+WINDOW_ATTENTION_HEAD_DIM = 32
+
+
+def window_attention_desc(b, h, w, ws, shift, heads, ld_table=None, scale=WINDOW_ATTENTION_HEAD_DIM ** -0.5,
+                          ldq=None, ldk=None, ldv=None, ldo=None, lddq=None, lddk=None, lddv=None, lddo=None):
+    """A ``WindowAttentionDesc`` for ``b`` padded maps of ``h`` x ``w`` tokens, ``ws`` x ``ws`` windows shifted by
+    ``shift`` and ``heads`` active heads; pitches default as in ``attention_desc`` (32 * heads), the table's
+    pitch to ``heads``."""
+    d = WindowAttentionDesc()
+    d.B, d.H, d.W, d.ws, d.shift, d.heads, d.scale = b, h, w, ws, shift, heads, scale
+    d.ld_table = heads if ld_table is None else ld_table
+    c = WINDOW_ATTENTION_HEAD_DIM * heads
+    d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
+    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
+                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    return d
+
+
+class CellLayerNormDesc(Structure):
+    """Mirror of ``gs_cell_layernorm_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("B", "H", "W", "C", "Cmax", "ldx", "ldy")] + [("eps", c_float)])
+
+
+def cell_layernorm_desc(b, h, w, c, cmax=None, eps=1e-5, ldx=None, ldy=None):
+    """A ``CellLayerNormDesc`` for ``b`` maps of ``h`` x ``w`` pixels of ``c`` active channels under parameter
+    groups of ``cmax`` (default c) channels; pitches default to c."""
+    d = CellLayerNormDesc()
+    d.B, d.H, d.W, d.C, d.eps = b, h, w, c, eps
+    d.Cmax = c if cmax is None else cmax
+    d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
     return d
 
 
@@ -339,6 +378,7 @@ _LN = POINTER(LayerNormDesc)
 _AT = POINTER(AttentionDesc)
 _AK = POINTER(AttentionKvDesc)
 _FD = POINTER(FcuDownDesc)
+_WA, _CL = POINTER(WindowAttentionDesc), POINTER(CellLayerNormDesc)
 _OG, _OA = POINTER(OcrGatherDesc), POINTER(OcrAttendDesc)
 
 # name -> (restype, argtypes): one entry per declaration in include/gaiaseg_hip.h
@@ -377,6 +417,15 @@ PROTOTYPES = {
     "gs_attention_kv_workspace_bytes": (_sz, [_AK]),
     "gs_attention_kv_backward": (_i32, [_AK, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
     "gs_debug_set_attention_kv_split": (_i32, [_i32]),
+    "gs_window_attention_forward": (_i32, [_WA, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_window_attention_workspace_bytes": (_sz, [_WA]),
+    "gs_window_attention_backward": (_i32, [_WA, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
+    "gs_debug_set_window_attention_split": (_i32, [_i32]),
+    "gs_map_pad": (_i32, [_P, _i32, _P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
+    "gs_map_crop": (_i32, [_P, _i32, _P, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
+    "gs_cell_layernorm_forward": (_i32, [_CL, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_cell_layernorm_workspace_bytes": (_sz, [_CL]),
+    "gs_cell_layernorm_backward": (_i32, [_CL, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _P, _sz, _P]),
     "gs_vit_tokens_forward": (_i32, [_P, _i32, _P, _P, _i32, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_vit_tokens_backward": (_i32, [_P, _i32, _P, _i32, _P, _P, _i32, _i32, _i32, _i32, _P]),
     "gs_fcu_down_workspace_bytes": (_sz, [_FD]),

@@ -999,6 +999,158 @@ def attention_kv(tape, q, k, v, heads, scale, out=None):
     return out
 
 
+def window_attention(tape, q, k, v, table, heads, ws, shift, scale, out=None):
+    """Swin's shifted-window attention, head dimension 32, on padded maps: q, k and v are [B, Hp, Wp, 32 * heads]
+    (three column slices of one buffer are fine), Hp and Wp multiples of ``ws``; ``table`` is the max-size
+    relative_position_bias_table [(2 ws - 1)^2, heads_max], of which the leading ``heads`` columns are read
+    and get a gradient (written like every parameter gradient, then notified).  The roll, the window
+    partition, the bias gather and the region mask happen inside the kernel; fp32 operands in every precision
+    mode.  lse is kept for the backward, whose workspace (the table partials) comes from the pool."""
+    L = _L()
+    q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
+    c = _lib.WINDOW_ATTENTION_HEAD_DIM * heads
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.C != c or (t.N, t.H, t.W) != (q.N, q.H, q.W):
+            raise ValueError("window_attention: %s is %s, expected [%d, %d, %d, %d] for %d heads"
+                             % (name, tuple(t.t.shape), q.N, q.H, q.W, c, heads))
+    rows = (2 * ws - 1) ** 2
+    if table.dim() != 2 or table.shape[0] != rows or table.shape[1] < heads or table.stride(1) != 1:
+        raise ValueError("window_attention: the table is %s, expected [%d, >= %d]" % (tuple(table.shape), rows, heads))
+    b, dev = q.N, q.t.device
+    if out is None:
+        out = Act.empty(b, q.H, q.W, c, dev)
+    lse = torch.empty(b * heads * q.H * q.W, dtype=torch.float32, device=dev)
+    d = _lib.window_attention_desc(b, q.H, q.W, ws, shift, heads, ld_table=table.stride(0), scale=scale, ldq=q.ld,
+                                   ldk=k.ld, ldv=v.ld, ldo=out.ld)
+    _lib.check(L.gs_window_attention_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, table.data_ptr(), out.ptr,
+                                             lse.data_ptr(), current_stream_ptr()), "gs_window_attention_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad or table.requires_grad):
+            return
+        fresh = all(t.g is None for t in (q, k, v))   # nothing held a contribution: every output is written (=)
+        accs = [_input_grad(t) for t in (q, k, v)]
+        if not fresh and not all(accs):   # one flag for the three: start the fresh ones from zero
+            for t, acc in zip((q, k, v), accs):
+                if not acc:
+                    t.g.zero_()
+        acc = 0 if fresh else 1
+        gt = ensure_grad(table) if table.requires_grad else torch.empty_like(table)
+        if acc:   # the flag covers the table too: its active columns start from zero
+            gt[:, :heads].zero_()
+        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        db = ctypes.byref(d)
+        ws_buf = _ws.get(L.gs_window_attention_workspace_bytes(db), dev)
+        _lib.check(L.gs_window_attention_backward(db, q.ptr, k.ptr, v.ptr, table.data_ptr(), out.ptr, lse.data_ptr(),
+                                                  dy.data_ptr(), q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(),
+                                                  gt.data_ptr(), acc, ws_buf.data_ptr(), ws_buf.numel(),
+                                                  current_stream_ptr()), "gs_window_attention_backward")
+        if table.requires_grad:
+            _notify(table)
+
+    tape.record(backward)
+    return out
+
+
+def map_pad(tape, x, hp, wp, out=None):
+    """x [B, H, W, C] zero-padded at the bottom and right to [B, hp, wp, C] (Swin pads the normalised map to a
+    multiple of the window before the q / k / v linears).  The backward is the crop."""
+    L = _L()
+    x = materialize(tape, x)
+    b, h, w, c, dev = x.N, x.H, x.W, x.C, x.t.device
+    if out is None:
+        out = Act.empty(b, hp, wp, c, dev)
+    _lib.check(L.gs_map_pad(x.ptr, x.ld, out.ptr, out.ld, b, h, w, hp, wp, c, 0, current_stream_ptr()), "gs_map_pad")
+
+    def backward():
+        dy = out.g
+        if dy is None or not x.requires_grad:
+            return
+        acc = _input_grad(x)
+        if not acc and x.parent is not None:
+            acc = 1   # a slice of a zeroed buffer
+        _lib.check(L.gs_map_crop(dy.data_ptr(), dy.stride(2), x.g.data_ptr(), x.g.stride(2), b, h, w, hp, wp, c, acc,
+                                 current_stream_ptr()), "gs_map_crop")
+
+    tape.record(backward)
+    return out
+
+
+def map_crop(tape, x, h, w, out=None):
+    """the leading [B, h, w, C] of the padded map x [B, Hp, Wp, C].  The backward is the zero-filling pad (added
+    where x already holds a gradient)."""
+    L = _L()
+    x = materialize(tape, x)
+    b, hp, wp, c, dev = x.N, x.H, x.W, x.C, x.t.device
+    if out is None:
+        out = Act.empty(b, h, w, c, dev)
+    _lib.check(L.gs_map_crop(x.ptr, x.ld, out.ptr, out.ld, b, h, w, hp, wp, c, 0, current_stream_ptr()),
+               "gs_map_crop")
+
+    def backward():
+        dy = out.g
+        if dy is None or not x.requires_grad:
+            return
+        acc = 1 if (_input_grad(x) or x.parent is not None) else 0
+        _lib.check(L.gs_map_pad(dy.data_ptr(), dy.stride(2), x.g.data_ptr(), x.g.stride(2), b, h, w, hp, wp, c, acc,
+                                current_stream_ptr()), "gs_map_pad")
+
+    tape.record(backward)
+    return out
+
+
+def cell_layernorm(tape, x, weight, bias, eps=1e-5, out=None):
+    """The LayerNorm of Swin's patch merging on the map itself: statistics over the 4 C values of every 2 x 2
+    cell of x [B, H, W, C] (H, W even), ``weight`` / ``bias`` the max-size [4 Cmax] parameters in transformers'
+    order, read at (2 col + row) * Cmax + c.  The result is a map again: a 2x2 stride-2 convolution is the
+    reduction.  The per-cell mean and 1/std are kept for the backward."""
+    L = _L()
+    x = materialize(tape, x)
+    c, cmax = x.C, weight.shape[0] // 4
+    if weight.shape[0] % 4 or c > cmax or c % 4 or x.H % 2 or x.W % 2:
+        raise ValueError("cell_layernorm: a map %s under parameters of %d entries (needs even sides, C %% 4 == 0 "
+                         "and C <= Cmax)" % (tuple(x.t.shape), weight.shape[0]))
+    dev, cells = x.t.device, x.N * (x.H // 2) * (x.W // 2)
+    if out is None:
+        out = Act.empty(x.N, x.H, x.W, c, dev)
+    stats = torch.empty(2 * cells, dtype=torch.float32, device=dev)
+    mean_ptr, rstd_ptr = stats.data_ptr(), stats.data_ptr() + 4 * cells
+    d = _lib.cell_layernorm_desc(x.N, x.H, x.W, c, cmax, eps, ldx=x.ld, ldy=out.ld)
+    _lib.check(L.gs_cell_layernorm_forward(ctypes.byref(d), x.ptr, weight.data_ptr(), bias.data_ptr(), out.ptr,
+                                           mean_ptr, rstd_ptr, current_stream_ptr()), "gs_cell_layernorm_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None:
+            return
+        keep = stats  # noqa: F841 -- the closure owns the storage behind mean_ptr / rstd_ptr
+        if dy.stride(2) != d.ldy:
+            raise RuntimeError("cell_layernorm: the gradient's pitch %d differs from the output's %d"
+                               % (dy.stride(2), d.ldy))
+        db = ctypes.byref(d)
+        gw = ensure_grad(weight) if weight.requires_grad else torch.empty_like(weight)
+        gb = ensure_grad(bias) if bias.requires_grad else torch.empty_like(bias)
+        ws_buf = _ws.get(L.gs_cell_layernorm_workspace_bytes(db), dev)
+        if x.requires_grad:
+            acc = _input_grad(x)
+            dx = x.g
+        else:
+            acc, dx = 0, torch.empty_like(x.t)
+        if dx.stride(2) != d.ldx:
+            raise RuntimeError("cell_layernorm: dx has pitch %d, x has %d" % (dx.stride(2), d.ldx))
+        _lib.check(L.gs_cell_layernorm_backward(db, x.ptr, dy.data_ptr(), weight.data_ptr(), mean_ptr, rstd_ptr,
+                                                dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), acc, ws_buf.data_ptr(),
+                                                ws_buf.numel(), current_stream_ptr()), "gs_cell_layernorm_backward")
+        if weight.requires_grad:
+            _notify(weight)
+        if bias.requires_grad:
+            _notify(bias)
+
+    tape.record(backward)
+    return out
+
+
 def _forward_only(tape, what, *inputs):
     if tape.enabled and any(t.requires_grad for t in inputs):
         raise NotImplementedError("%s: forward only (no backward kernel); called with a recording tape and an "

@@ -4,3 +4,4 @@ from .elastic_transformer import ElasticTransformer  # noqa: F401
 from .beit import BEiT  # noqa: F401
 from .elastic_convformer import ElasticConvformer  # noqa: F401
 from .dynamic_mit import DynamicMixVisionTransformer  # noqa: F401
+from .dynamic_swin import DynamicSwinTransformer  # noqa: F401

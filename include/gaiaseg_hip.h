@@ -328,6 +328,91 @@ int gs_attention_kv_backward(const gs_attention_kv_desc* d, const float* q, cons
                              const float* o, const float* lse, const float* d_o, float* dq, float* dk,
                              float* dv, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 int gs_debug_set_attention_kv_split(int32_t S);
+/* Swin's shifted-window attention, head dimension 32 (transformers' SwinLayer with always_partition):
+ * attention local to ws x ws windows of an NHWC map [B][H][W] (the PADDED map: H % ws == W % ws == 0), on a
+ * cyclically shifted frame with a region mask when shift > 0, with a learned per-head relative-position bias.
+ * Row b*H*W + y*W + x of every operand is the token at (y, x); head h sits in columns [32 h, 32 h + 32); one
+ * pitch per operand (Q, K, V may be three column slices of one buffer); `heads` is the ACTIVE head count.
+ *   shifted frame  y' = (y - shift) mod H, x' = (x - shift) mod W;   window (y' / ws, x' / ws);
+ *   in-window position (iy, ix) = (y' % ws, x' % ws);
+ *   s(i, j) = scale * <q_i, k_j> + table[idx(i, j)][h] + mask(i, j)   for tokens i, j of one window,
+ *   idx(i, j) = (iy - jy + ws - 1) * (2 ws - 1) + (ix - jx + ws - 1),
+ *   mask = 0 if shift == 0 or region(i) == region(j), else -100.0 (finite, as in the original),
+ *   region(y', x') = 3 r(y', H) + r(x', W),   r(t, L) = (t >= L - ws) + (t >= L - shift),
+ *   O_i = sum_j softmax_j(s(i, j)) v_j.
+ * table is fp32 [(2 ws - 1)^2][ld_table], ld_table >= heads (a checkpoint's relative_position_bias_table at
+ * the supernet's maximum head count; the leading `heads` columns are read).  lse is [B][heads][H*W] at the
+ * token's (y, x) and is saved for the backward.  The roll, the partition, the bias gather, the mask, the
+ * reverse and the roll back are index arithmetic inside one kernel (csrc/window_attention.hip): a one-wave
+ * workgroup per (window, head), the ws^2 tokens padded to 64 in LDS (a padded key scores -inf and contributes
+ * nothing, a padded query is never stored), every product on the exact fp32 MFMA.
+ * Backward: dQ, dK, dV (each = or +=) are complete inside a window.  dtable[r][h] = (or +=, the same flag) the
+ * sum over batch, windows and pairs with idx == r of dS; only columns < heads are written.  It is formed
+ * without atomics: the (batch, window) items are cut into S slabs of consecutive items, a workgroup per (slab,
+ * head) walks its slab and sums every table entry's pairs in a fixed order, writes its [heads][(2 ws - 1)^2]
+ * partial to the workspace (S * heads * (2 ws - 1)^2 floats, rounded up to 16 bytes), and a second launch
+ * adds the partials in slab order.  S is a pure function of the descriptor and the CU count (3 * CUs / heads,
+ * at most one item per slab); gs_debug_set_window_attention_split(S >= 1) forces it (clipped so that no slab
+ * is empty) for the query and the backward alike, -1 restores the plan, anything else is GS_E_BADARG.
+ * Bit-identical from run to run.  Nothing outside the active columns and rows is written.
+ * Checked on the host before any launch, in this order: GS_E_NULL (descriptor); GS_E_BADARG (B, H, W or heads
+ * <= 0, B or heads > 65535, scale <= 0, ws outside 2..8, H % ws or W % ws != 0, shift outside [0, ws), more
+ * than 2^31 - 1 tokens); GS_E_ALIGN (a pitch no multiple of 4); GS_E_BADARG (a pitch below 32 * heads,
+ * ld_table < heads); GS_E_NULL (any pointer, table and dtable included); GS_E_ALIGN (an operand pointer not
+ * 16-byte aligned, table or dtable not 4-byte aligned); GS_E_WORKSPACE. */
+typedef struct gs_window_attention_desc {
+  int32_t B, H, W;                  /* batch and the (padded) map                                */
+  int32_t ws, shift, heads;         /* window size 2..8, shift in [0, ws), ACTIVE heads          */
+  int32_t ldq, ldk, ldv, ldo;       /* token pitches of Q, K, V, O                               */
+  int32_t lddq, lddk, lddv, lddo;   /* token pitches of dQ, dK, dV, dO (all eight are checked)   */
+  int32_t ld_table;                 /* row pitch of table and dtable                             */
+  float scale;                      /* 32^-0.5 in Swin                                           */
+} gs_window_attention_desc;
+int gs_window_attention_forward(const gs_window_attention_desc* d, const float* q, const float* k,
+                                const float* v, const float* table, float* o, float* lse, void* stream);
+size_t gs_window_attention_workspace_bytes(const gs_window_attention_desc* d);
+int gs_window_attention_backward(const gs_window_attention_desc* d, const float* q, const float* k,
+                                 const float* v, const float* table, const float* o, const float* lse,
+                                 const float* d_o, float* dq, float* dk, float* dv, float* dtable,
+                                 int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int gs_debug_set_window_attention_split(int32_t S);
+/* Window padding as a materialised pad and crop; each is the other's backward.
+ * gs_map_pad: dst[b, y, x, :C] (= or +=) src[b, y, x, :C] for y < H and x < W, else 0: src is [B][H][W] with
+ * pixel pitch lds, dst [B][Hp][Wp] with pitch ldd, Hp >= H, Wp >= W.
+ * gs_map_crop: dst[b, y, x, :C] (= or +=) src[b, y, x, :C]: src is [B][Hp][Wp] (pitch lds), dst [B][H][W]
+ * (pitch ldd).  Columns C.. are never written.  GS_E_BADARG (a size <= 0, Hp < H, Wp < W, a pitch below C,
+ * more than 2^31 - 1 pixels), GS_E_ALIGN (C or a pitch no multiple of 4, a pointer not 16-byte aligned),
+ * GS_E_NULL. */
+int gs_map_pad(const float* src, int32_t lds, float* dst, int32_t ldd, int32_t B, int32_t H, int32_t W,
+               int32_t Hp, int32_t Wp, int32_t C, int accumulate, void* stream);
+int gs_map_crop(const float* src, int32_t lds, float* dst, int32_t ldd, int32_t B, int32_t H, int32_t W,
+                int32_t Hp, int32_t Wp, int32_t C, int accumulate, void* stream);
+/* The LayerNorm of Swin's patch merging without the space-to-depth copy: statistics over the 4 C values of
+ * each 2 x 2 cell of an NHWC map [B][H][W] (H, W even), the result written back as a map of the same shape
+ * (a 2x2 stride-2 gs_conv2d then is the reduction).  Pixel (2 cy + r, 2 cx + q) of a cell is phase
+ * g = 2 q + r (transformers' order of the four concatenated slices) and reads weight and bias at
+ * g * Cmax + c: a subnet of C active channels under a maximum of Cmax takes the leading C channels of each of
+ * the four groups of the [4 Cmax] parameters.
+ *   y = (x - mean[cell]) * rstd[cell] * weight[g Cmax + c] + bias[g Cmax + c],  rstd = 1 / sqrt(var + eps).
+ * mean and rstd are [B * H/2 * W/2] and are saved for the backward.  Backward: dx (= or +=, pitch ldx);
+ * dweight and dbias (written, =) at g * Cmax + c for c < C only, through one [2][4 C] partial per run of 64
+ * cells in the workspace and their sum in run order.  No atomics; bit-identical from run to run.
+ * GS_E_NULL, GS_E_BADARG (a size <= 0, odd H or W, Cmax < C, a pitch below C, eps <= 0, more than 2^31 - 1
+ * pixels), GS_E_ALIGN (C, Cmax or a pitch no multiple of 4, a tensor pointer not 16-byte aligned),
+ * GS_E_WORKSPACE. */
+typedef struct gs_cell_layernorm_desc {
+  int32_t B, H, W;        /* the map (H and W even)                                          */
+  int32_t C, Cmax;        /* ACTIVE channels, channel count of a parameter group             */
+  int32_t ldx, ldy;       /* pixel pitches of x / dx and of y / dy                           */
+  float eps;
+} gs_cell_layernorm_desc;
+int gs_cell_layernorm_forward(const gs_cell_layernorm_desc* d, const float* x, const float* weight,
+                              const float* bias, float* y, float* mean, float* rstd, void* stream);
+size_t gs_cell_layernorm_workspace_bytes(const gs_cell_layernorm_desc* d);
+int gs_cell_layernorm_backward(const gs_cell_layernorm_desc* d, const float* x, const float* dy,
+                               const float* weight, const float* mean, const float* rstd, float* dx,
+                               float* dweight, float* dbias, int accumulate, void* workspace,
+                               size_t workspace_bytes, void* stream);
 /* ElasticTransformer's token assembly on the leading D columns: from patches [B*T][D] (pitch ldp),
  * cls_token[:D] and pos_embed[:T+1, :D] (pitch ldpos, the max-size embedding width),
  *   x[b,0,:] = cls_token + pos_embed[0],   x[b,1+t,:] = patches[b,t] + pos_embed[1+t]      (x: [B*(T+1)][D]).
