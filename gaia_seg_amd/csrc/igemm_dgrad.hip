@@ -125,8 +125,11 @@ int conv2d_dgrad_impl(const gs_conv_desc* d, const float* dy, const float* w, fl
   if (!aligned16(dy) || !aligned16(w) || !aligned16(dx)) return GS_E_ALIGN;
   hipStream_t st = as_stream(stream);
   const ConvRoute r = route_dgrad(d, RouteHints{false, bw ? std::max(bw->ldy, bw->ldact) : 0});
-  if (r.path == PATH_STRIDED_CLASSES)
+  if (r.path == PATH_STRIDED_CLASSES) {
+    // (refused before the zero fill: r.need is the largest class's slabs)
+    if (r.need > workspace_bytes || (r.need && !workspace)) return GS_E_WORKSPACE;
     return dgrad_strided_fast(d, dy, w, dx, accumulate, workspace, workspace_bytes, st);
+  }
   const Plan& pl = r.plan;
   const long M = (long)d->N * d->H * d->W;
   const size_t need = r.need;

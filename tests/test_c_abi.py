@@ -252,6 +252,163 @@ def test_wgrad_cases_make_their_coverage_claims_without_gpu():
     assert seen_aff >= {(lib.KLOOP_FP32, True), (lib.KLOOP_FP32, False), (lib.KLOOP_FP32_PAIRS, True)}
 
 
+def test_conv_rows_cases_make_their_coverage_claims_without_gpu():
+    """tests/test_conv_rows_gpu.py states per case and op which row kernel, K loop, tile, split count and
+    form of the split-K reduce it is there for.  Every claim is checked here against
+    gs_debug_query_conv_launch (host arithmetic; the GPU test re-checks it against the launch that really
+    happened), and so is what the table covers as a whole, per op."""
+    import test_conv_rows_gpu as T
+    L = lib.load()
+    FAST = (lib.KLOOP_FP32, lib.KLOOP_FP32_PAIRS)
+    seen = {op: dict(kloop=set(), tiles=set(), reduce=set(), strides=set(), tapless=0, divs=set(), scalar=0,
+                     aff=set()) for op in (T.FWD, T.DGRAD)}
+    for c, op in T.PARAMS:
+        d = T.make_desc(lib, c)
+        if c.aff:
+            d.in_affine = 4096          # any aligned address: the query does not read it
+            assert L.gs_conv2d_in_affine_supported(ctypes.byref(d)) == (0 if T.NO_FAST else 1), c
+        q = lib.DebugLaunch()
+        with T.forced_plan(L, c):
+            assert L.gs_debug_query_conv_launch(ctypes.byref(d), lib.OP_FORWARD if op == T.FWD else lib.OP_DGRAD,
+                                                ctypes.byref(q)) == 0
+            need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+        T.check_claim(L, lib, c, d, op, q)
+        m, n, _ = T.gemm_dims(c, d, op)
+        classes = T.in_classes(c, d, op)
+        if classes:      # the largest slab among the classes' own plans
+            recs = [T.class_record(L, lib, c, rows, taps) for _, _, rows, taps in T.dgrad_classes(c, d) if rows and taps]
+            assert need >= max(r.splits * rows * n * 4 if r.splits > 1 else 0
+                               for r, (_, _, rows, taps) in zip(recs, [x for x in T.dgrad_classes(c, d) if x[2] and x[3]]))
+        else:
+            assert need >= (q.splits * m * n * 4 if q.splits > 1 else 0), (c, op)
+        assert T.exact_bound(c, d, op) < 2 ** 22
+        s = seen[op]
+        s["kloop"].add(q.kloop)
+        if q.kloop in FAST:
+            s["tiles"].add((q.bm, q.bn))
+            if c.aff and op == T.FWD:
+                s["aff"].add(q.kloop)
+        if q.splits > 1 and not classes:
+            # (form, an epilogue operand behind it, on the fast kernels); every data-gradient case runs = and +=
+            for epi in ((c.bias or c.addend,) if op == T.FWD else (False, True)):
+                s["reduce"].add(("launch" if T.combines(q) else "reduce", bool(epi), q.kloop in FAST))
+        if op == T.DGRAD:
+            if classes:
+                s["strides"].add(c.stride)
+                s["tapless"] += any(rows and not taps for _, _, rows, taps in T.dgrad_classes(c, d))
+            elif q.kloop in FAST:
+                s["strides"].add(1)
+            elif c.stride > 1:
+                s["divs"].add(3 if (d.KH, d.KW) == (3, 3) else (1 if (d.KH, d.KW) == (1, 1) else 0))
+        elif not T.is_vector(c):
+            s["scalar"] += 1
+    if T.NO_FAST:
+        assert all(s["kloop"] == {lib.KLOOP_GENERIC} for s in seen.values())
+        return
+    six = {128, 96, 80, 64, 48, 32}
+    for op, s in seen.items():
+        assert s["tiles"] >= {(bm, bn) for bm in (64, 128) for bn in six}, (op, s["tiles"])
+    assert seen[T.FWD]["scalar"] >= 3
+    assert seen[T.DGRAD]["strides"] >= {1, 2, 3} and seen[T.DGRAD]["tapless"] >= 1
+    assert seen[T.DGRAD]["divs"] >= {3, 0}
+    if T.PLAN_ENV or T.NO_COMBINE:
+        return
+    for op, s in seen.items():
+        assert s["kloop"] == {lib.KLOOP_GENERIC, lib.KLOOP_FP32, lib.KLOOP_FP32_PAIRS}, op
+        # both reduce forms behind the fast kernels, each with and without an epilogue operand, and the
+        # reduce launch behind the generic kernel
+        assert s["reduce"] >= {("launch", False, True), ("launch", True, True), ("reduce", False, True),
+                               ("reduce", True, True), ("reduce", False, False)}, (op, s["reduce"])
+    assert seen[T.FWD]["aff"] == {lib.KLOOP_FP32, lib.KLOOP_FP32_PAIRS}
+
+
+def test_forward_and_dgrad_argument_checks_need_no_gpu():
+    """gs_conv2d_forward and gs_conv2d_dgrad refuse bad arguments before any launch (every refusal of
+    include/gaiaseg_hip.h, conv2d_forward_impl and conv2d_dgrad_impl).  The addresses are never read."""
+    L = lib.load()
+    OK_PTR, ODD_PTR = 1 << 20, (1 << 20) + 4
+    E_BADARG, E_ALIGN, E_WORKSPACE, E_NULL = -1, -2, -3, -4
+
+    def fwd(d, x=OK_PTR, w=OK_PTR, bias=None, addend=None, y=OK_PTR, ws=OK_PTR, ws_bytes=None):
+        need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+        return L.gs_conv2d_forward(ctypes.byref(d), x, w, bias, addend, y, ws, need if ws_bytes is None else ws_bytes,
+                                   None)
+
+    def dgrad(d, dy=OK_PTR, w=OK_PTR, dx=OK_PTR, acc=0, ws=OK_PTR, ws_bytes=None):
+        need = L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+        return L.gs_conv2d_dgrad(ctypes.byref(d), dy, w, dx, acc, ws, need if ws_bytes is None else ws_bytes, None)
+
+    def shape(**kw):
+        return lib.conv_desc(2, 13, 17, 48, 48, 3, **kw)     # 6 splits either way: needs slabs
+
+    d, q = shape(), lib.DebugLaunch()
+    slab = {}
+    for op in (lib.OP_FORWARD, lib.OP_DGRAD):
+        assert L.gs_debug_query_conv_launch(ctypes.byref(d), op, ctypes.byref(q)) == 0
+        assert q.splits > 1
+        slab[op] = q.splits * 2 * 13 * 17 * 48 * 4            # what the op itself needs
+        assert 0 < slab[op] <= L.gs_conv2d_workspace_bytes(ctypes.byref(d))
+    # ---- forward ----
+    assert L.gs_conv2d_forward(None, OK_PTR, OK_PTR, None, None, OK_PTR, OK_PTR, slab[lib.OP_FORWARD], None) == E_NULL
+    assert fwd(d, x=None) == E_NULL and fwd(d, w=None) == E_NULL and fwd(d, y=None) == E_NULL
+    assert fwd(d, w=ODD_PTR) == E_ALIGN and fwd(d, y=ODD_PTR) == E_ALIGN
+    assert fwd(d, bias=ODD_PTR) == E_ALIGN and fwd(shape(ld_add=48), addend=ODD_PTR) == E_ALIGN
+    assert fwd(d, x=ODD_PTR) == E_ALIGN                      # a vector source is read as float4
+    assert fwd(shape(ld_add=50), addend=OK_PTR) == E_ALIGN   # ld_add % 4
+    assert fwd(shape(ld_add=44), addend=OK_PTR) == E_ALIGN   # ld_add < Co
+    assert fwd(d, addend=OK_PTR) == E_ALIGN                  # ld_add = 0 beside an addend
+    assert fwd(d, ws_bytes=slab[lib.OP_FORWARD] - 1) == E_WORKSPACE and fwd(d, ws=None) == E_WORKSPACE
+    assert fwd(d, ws=None, ws_bytes=0) == E_WORKSPACE
+    bad = shape()
+    bad.Ho += 1
+    assert fwd(bad) == E_BADARG
+    # the descriptor's own alignment rules (check_desc)
+    assert fwd(lib.conv_desc(2, 13, 17, 48, 46, 3)) == E_ALIGN                 # Co % 4
+    assert fwd(shape(ldy=44)) == E_ALIGN                                        # ldy < Co
+    assert fwd(shape(ci_max=32)) == E_BADARG                                    # Ci > Ci_max
+    # in_affine: at most kAffMaxC = 640 channels, a vector source, a 1x1 or 3x3 ...
+    for dims in [(2, 9, 9, 656, 64, 1), (2, 17, 19, 6, 24, 3), (1, 20, 24, 16, 32, 5)]:
+        a = lib.conv_desc(*dims)
+        a.in_affine = OK_PTR
+        assert L.gs_conv2d_in_affine_supported(ctypes.byref(a)) == 0
+        assert fwd(a) == E_BADARG, dims
+    # ... and 64-row tiles: not under a forced 128-row plan
+    a = lib.conv_desc(2, 9, 9, 640, 64, 1)
+    a.in_affine = OK_PTR
+    if L.gs_conv2d_in_affine_supported(ctypes.byref(a)) == 1:      # (not under GS_NO_FAST)
+        assert L.gs_debug_force_plan(128, 64, 1) == 0
+        try:
+            assert L.gs_conv2d_in_affine_supported(ctypes.byref(a)) == 0
+            assert fwd(a) == E_BADARG
+        finally:
+            L.gs_debug_force_plan(0, 0, 0)
+        a.in_affine = ODD_PTR
+        assert fwd(a) == E_ALIGN
+    # ---- data gradient ----
+    assert L.gs_conv2d_dgrad(None, OK_PTR, OK_PTR, OK_PTR, 0, OK_PTR, slab[lib.OP_DGRAD], None) == E_NULL
+    assert dgrad(d, dy=None) == E_NULL and dgrad(d, w=None) == E_NULL and dgrad(d, dx=None) == E_NULL
+    assert dgrad(d, dy=ODD_PTR) == E_ALIGN and dgrad(d, w=ODD_PTR) == E_ALIGN and dgrad(d, dx=ODD_PTR) == E_ALIGN
+    assert dgrad(d, ws_bytes=slab[lib.OP_DGRAD] - 1) == E_WORKSPACE and dgrad(d, ws=None) == E_WORKSPACE
+    assert dgrad(d, ws=None, ws_bytes=0) == E_WORKSPACE
+    assert dgrad(bad) == E_BADARG
+    nchw = shape()
+    nchw.x_sn, nchw.x_sc, nchw.x_sh, nchw.x_sw = 48 * 13 * 17, 13 * 17, 17, 1
+    assert dgrad(nchw) == E_ALIGN                                               # x_sc != 1
+    assert dgrad(lib.conv_desc(2, 13, 17, 6, 48, 3)) == E_ALIGN                 # Ci % 4
+    assert dgrad(shape(ldx=50)) == E_ALIGN                                      # x_sw % 4
+    for field in ("x_sh", "x_sn"):                                              # dx is packed [N][H][W][x_sw]
+        loose = shape(ldx=64)
+        setattr(loose, field, getattr(loose, field) + 64)
+        assert dgrad(loose) == E_BADARG, field
+    # a strided data gradient in parity classes needs the largest class's slabs (+=: the call would
+    # queue nothing in front of that check in any case)
+    s2 = lib.conv_desc(2, 15, 15, 64, 256, 1, stride=2, pad=0)
+    assert L.gs_debug_query_conv_launch(ctypes.byref(s2), lib.OP_DGRAD, ctypes.byref(q)) == 0
+    if q.kloop != lib.KLOOP_GENERIC and q.splits > 1:
+        assert dgrad(s2, acc=1, ws_bytes=q.splits * 2 * 8 * 8 * 64 * 4 - 1) == E_WORKSPACE
+        assert dgrad(s2, acc=1, ws=None) == E_WORKSPACE
+
+
 def test_wgrad_argument_checks_need_no_gpu():
     """gs_conv2d_wgrad refuses bad arguments before any launch.  (The addresses are never read.)"""
     L = lib.load()
