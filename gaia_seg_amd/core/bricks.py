@@ -462,6 +462,38 @@ for _n in ("DynLN", "ElaLN", "LN"):
     NORM_LAYERS.register_module(_n, module=_layernorm_factory)
 
 
+# ------------------------------------------------------------------------------------------
+# GELU + GRN (ConvNeXt V2)
+# ------------------------------------------------------------------------------------------
+class DynamicGRN(nn.Module, DynamicMixin):
+    """ConvNeXt V2's Global Response Normalization together with the GELU in front of it
+    (ops.gelu_grn): ``forward_act`` takes the PRE-activation of the hidden layer.  ``weight`` and
+    ``bias`` have transformers' ``ConvNextV2GRN`` shape [1, 1, 1, dim] and start at zero (the
+    identity); the active width is the incoming activation's, and the mean of the response runs
+    over those channels only."""
+    search_space = set()
+
+    def __init__(self, dim, eps=1e-6):
+        super().__init__()
+        self.dim, self.eps = dim, eps
+        self.weight = nn.Parameter(torch.zeros(1, 1, 1, dim))
+        self.bias = nn.Parameter(torch.zeros(1, 1, 1, dim))
+
+    def extra_repr(self):
+        return "%d, eps=%g" % (self.dim, self.eps)
+
+    def forward_act(self, tape, x, out=None):
+        if getattr(self, "_deploying", False) and self.dim != x.C:
+            self.dim = x.C
+            self.weight = nn.Parameter(self.weight.data[..., :x.C].clone(), self.weight.requires_grad)
+            self.bias = nn.Parameter(self.bias.data[..., :x.C].clone(), self.bias.requires_grad)
+        return ops.gelu_grn(tape, x, self.weight, self.bias, self.eps, out=out)
+
+    def forward(self, x):
+        """GRN(GELU(x)) of a channels-last [N, H, W, C] tensor"""
+        return _nhwc_tape_call(self.forward_act, x)
+
+
 def build_norm_layer(cfg, num_features, postfix=""):
     """mmcv.cnn.build_norm_layer: returns (name, layer); the abbreviation is 'bn' for the BN family and
     'ln' for DynLN / LN."""

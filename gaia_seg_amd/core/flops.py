@@ -4,8 +4,8 @@ reference's tools/count_flops.py:118-179 obtains from gaiavision's get_model_com
 forward FLOPs of a conv = 2 * N * Ho * Wo * Cout_act * Cin_act * kh * kw,
 Ho = floor((H + 2p - d(k-1) - 1)/s) + 1.  Only convolutions are counted (BN / ReLU / pooling are
 O(activations) and excluded).  For ConvNeXt a depthwise conv counts
-2 * K * K * C * Ho * Wo and a DynamicLinear counts as the 1x1 conv it is; LayerNorm, GELU and the layer
-scale count 0: the reference's counter lives in gaiavision, which is absent, so there is no count of
+2 * K * K * C * Ho * Wo and a DynamicLinear counts as the 1x1 conv it is; LayerNorm, GELU, the layer
+scale and ConvNeXt V2's GRN count 0: the reference's counter lives in gaiavision, which is absent, so there is no count of
 theirs to reproduce, and they are O(activations) like BN / ReLU above.
 
 For the ElasticTransformer the patch embedding is a conv, every linear counts as the 1x1 conv it is on the N
@@ -39,20 +39,22 @@ def _conv(m, cin, h, w):
 
 
 def convnext_backbone_flops(backbone, h, w, in_channels=3):
-    """backbone_flops for a DynamicConvNeXt: (flops per image, params, 0.0, feature shapes).  Params are
-    those of the extracted subnet: active slices, active blocks, LayerNorm affines and layer scales."""
+    """backbone_flops for a DynamicConvNeXt or a DynamicConvNeXtV2: (flops per image, params, 0.0, feature
+    shapes).  Params are those of the extracted subnet: active slices, active blocks, LayerNorm affines and
+    layer scales (V1) or the GRN weight and bias of the 4C-wide hidden layer (V2; GRN counts 0 FLOPs)."""
     total, params, c = 0.0, 0.0, in_channels
     f, p, c, h, w = _conv(backbone.stem, c, h, w)
     total += f
     params += p + 2 * c                                   # + the stem LayerNorm
     feats = []
-    for i, name in enumerate(backbone.blocks):
-        for blk in getattr(backbone, name).active_blocks():
+    for i in range(4):
+        for blk in backbone.stage(i).active_blocks():
             fd, pd, _, _, _ = _conv(blk.dwconv, c, h, w)
             f1, p1, c1, _, _ = _conv(blk.pwconv1, c, h, w)
             f2, p2, _, _, _ = _conv(blk.pwconv2, c1, h, w)
             total += fd + f1 + f2
-            params += pd + p1 + p2 + 2 * c + (c if blk.gamma is not None else 0)
+            params += pd + p1 + p2 + 2 * c
+            params += 2 * c1 if hasattr(blk, "grn") else (c if blk.gamma is not None else 0)
         feats.append((c, h, w))
         if i in backbone.out_indices:
             params += 2 * c                               # norm{i}
@@ -249,7 +251,7 @@ def neck_flops(neck, feats):
 
 def backbone_flops(backbone, h, w, in_channels=3):
     """(flops per image, params, flops of the 3x3 bottleneck convs, feature shapes)."""
-    if type(backbone).__name__ == "DynamicConvNeXt":
+    if type(backbone).__name__ in ("DynamicConvNeXt", "DynamicConvNeXtV2"):
         return convnext_backbone_flops(backbone, h, w, in_channels)
     if type(backbone).__name__ == "ElasticTransformer":
         return vit_backbone_flops(backbone, h, w, in_channels)

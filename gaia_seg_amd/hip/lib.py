@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 class HipLibraryError(RuntimeError):
@@ -87,6 +87,20 @@ def layernorm_desc(rows, c, eps=1e-6, ldx=None, ldy=None):
     d = LayerNormDesc()
     d.rows, d.C, d.eps = rows, c, eps
     d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
+    return d
+
+
+class GeluGrnDesc(Structure):
+    """Mirror of ``gs_gelu_grn_desc``."""
+    _fields_ = [(k, c_int32) for k in ("N", "P", "C", "ldx", "ldy", "lddy", "lddx")] + [("eps", c_float)]
+
+
+def gelu_grn_desc(n, p, c, eps=1e-6, ldx=None, ldy=None, lddy=None, lddx=None):
+    """A ``GeluGrnDesc`` for ``n`` samples of ``p`` pixels with ``c`` active channels; pitches default to c."""
+    d = GeluGrnDesc()
+    d.N, d.P, d.C, d.eps = n, p, c, eps
+    d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
+    d.lddy, d.lddx = c if lddy is None else lddy, c if lddx is None else lddx
     return d
 
 
@@ -375,6 +389,7 @@ _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTE
 _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 _DW = POINTER(DwConvDesc)
 _LN = POINTER(LayerNormDesc)
+_GG = POINTER(GeluGrnDesc)
 _AT = POINTER(AttentionDesc)
 _AK = POINTER(AttentionKvDesc)
 _FD = POINTER(FcuDownDesc)
@@ -405,6 +420,9 @@ PROTOTYPES = {
     "gs_layer_scale_add_forward": (_i32, [_P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P]),
     "gs_layer_scale_workspace_bytes": (_sz, [_i64, _i32]),
     "gs_layer_scale_backward": (_i32, [_P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P, _sz, _P]),
+    "gs_gelu_grn_workspace_bytes": (_sz, [_GG]),
+    "gs_gelu_grn_forward": (_i32, [_GG, _P, _P, _P, _P, _P, _P, _sz, _P]),
+    "gs_gelu_grn_backward": (_i32, [_GG, _P, _P, _P, _P, _P, _P, _P, _P, _sz, _P]),
     "gs_attention_forward": (_i32, [_AT, _P, _P, _P, _P, _P, _P]),
     "gs_attention_relpos_forward": (_i32, [_AT, _P, _P, _P, _P, _i32, _i32, _i32, _P, _P, _P]),
     "gs_attention_workspace_bytes": (_sz, [_AT]),

@@ -769,8 +769,8 @@ def dwconv2d(tape, x, weight, pad, dil=1, out=None, bias=None):
 
 def _active_width(x, param, what):
     c = x.C
-    if c > param.shape[0]:
-        raise ValueError("input has %d channels, %s supports at most %d" % (c, what, param.shape[0]))
+    if c > param.shape[-1]:     # the channels are the last dimension of a parameter ([C] or [1, 1, 1, C])
+        raise ValueError("input has %d channels, %s supports at most %d" % (c, what, param.shape[-1]))
     if c % 4:
         raise ValueError("%s needs a channel count that is a multiple of 4, got %d" % (what, c))
     return c
@@ -844,6 +844,54 @@ def gelu(tape, x, out=None):
             raise RuntimeError("GELU input has more than one consumer; unsupported")
         _lib.check(L.gs_gelu_backward(x.ptr, dy.data_ptr(), x.g.data_ptr(), x.rows, x.C, x.ld, dy.stride(2),
                                       x.g.stride(2), current_stream_ptr()), "gs_gelu_backward")
+
+    tape.record(backward)
+    return out
+
+
+def gelu_grn(tape, x, weight, bias, eps=1e-6, out=None):
+    """ConvNeXt V2's hidden activation in one operator: Global Response Normalization of a = GELU(x) over
+    the x.C active channels, y = a * (1 + weight[:C] * Nx) + bias[:C] with Nx = G / (mean_c G + eps) and
+    G[n, c] the 2-norm of a over the pixels of sample n.  ``weight`` / ``bias`` are the max-size vectors
+    (any shape whose last dimension holds the channels, transformers' [1, 1, 1, C]).  a is never stored:
+    G [N, C] is kept, and the backward recomputes a from x."""
+    L = _L()
+    x = materialize(tape, x)
+    c = _active_width(x, weight, "gelu_grn")
+    if weight.numel() != weight.shape[-1] or bias.shape != weight.shape:
+        raise ValueError("gelu_grn: weight %s / bias %s are not per-channel vectors" % (tuple(weight.shape),
+                                                                                      tuple(bias.shape)))
+    dev = x.t.device
+    if out is None:
+        out = Act.empty(x.N, x.H, x.W, c, dev)
+    G = torch.empty(x.N * c, dtype=torch.float32, device=dev)
+    d = _lib.gelu_grn_desc(x.N, x.H * x.W, c, eps, ldx=x.ld, ldy=out.ld, lddy=out.ld, lddx=x.ld)
+    ws = _ws.get(L.gs_gelu_grn_workspace_bytes(ctypes.byref(d)), dev)
+    _lib.check(L.gs_gelu_grn_forward(ctypes.byref(d), x.ptr, weight.data_ptr(), bias.data_ptr(), out.ptr,
+                                     G.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr()),
+               "gs_gelu_grn_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None:
+            return
+        gw, gb = _param_grad(weight, c, dev), _param_grad(bias, c, dev)
+        if x.requires_grad:
+            if _input_grad(x):
+                raise RuntimeError("gelu_grn input has more than one consumer; unsupported")
+            dx = x.g
+        else:
+            dx = torch.empty_like(x.t)
+        d.lddy, d.lddx = dy.stride(2), dx.stride(2)
+        db = ctypes.byref(d)
+        ws = _ws.get(L.gs_gelu_grn_workspace_bytes(db), dev)
+        _lib.check(L.gs_gelu_grn_backward(db, x.ptr, dy.data_ptr(), weight.data_ptr(), G.data_ptr(),
+                                          dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), current_stream_ptr()), "gs_gelu_grn_backward")
+        if weight.requires_grad:
+            _notify(weight)
+        if bias.requires_grad:
+            _notify(bias)
 
     tape.record(backward)
     return out

@@ -148,6 +148,14 @@ class DynamicConvNeXt(nn.Module, DynamicMixin):
     def make_dynamic_convnext_block(self, **kwargs):
         return DynamicBlock(**kwargs)
 
+    # where the modules of stage i live: everything below goes through these two and the stem / ds*
+    # attributes, so a subclass with other module names (DynamicConvNeXtV2) only redirects them
+    def stage(self, i):
+        return getattr(self, self.blocks[i])
+
+    def out_norm(self, i):
+        return getattr(self, "norm%d" % i)
+
     def init_weights(self, pretrained=None):
         """Truncated normal (std 0.02) conv and linear weights with zero biases, unit LayerNorms; then
         the checkpoint, if a path is given."""
@@ -171,8 +179,8 @@ class DynamicConvNeXt(nn.Module, DynamicMixin):
         convs follow the width of the stage they feed."""
         self.body_state = arch_meta
         convs = (self.stem, self.ds1_conv, self.ds2_conv, self.ds3_conv)
-        for name, conv, meta in zip(self.blocks, convs, unzip_meta(arch_meta)):
-            getattr(self, name).manipulate_arch(meta)
+        for i, (conv, meta) in enumerate(zip(convs, unzip_meta(arch_meta))):
+            self.stage(i).manipulate_arch(meta)
             conv.manipulate_width(meta["width"])
 
     def full_arch_meta(self):
@@ -184,12 +192,12 @@ class DynamicConvNeXt(nn.Module, DynamicMixin):
         x = self.stem.forward_act(tape, x)
         x = self.stem_ln.forward_act(tape, x)
         outs = []
-        for i, name in enumerate(self.blocks):
-            x = getattr(self, name).forward_act(tape, x)
+        for i in range(4):
+            x = self.stage(i).forward_act(tape, x)
             if i == 0:
                 ops.side_checkpoint(tape)   # as DynamicResNet: later layers' gradients are ready first
             if i in self.out_indices:
-                outs.append(getattr(self, "norm%d" % i).forward_act(tape, x))
+                outs.append(self.out_norm(i).forward_act(tape, x))
             if i < 3:
                 x = getattr(self, "ds%d_ln" % (i + 1)).forward_act(tape, x)
                 x = getattr(self, "ds%d_conv" % (i + 1)).forward_act(tape, x)
@@ -201,7 +209,7 @@ class DynamicConvNeXt(nn.Module, DynamicMixin):
 
     def late_gradient_parameters(self):
         """Parameters whose gradients are produced after the side-stream checkpoint (stem, stage 1)."""
-        mods = [self.stem, self.stem_ln, getattr(self, self.blocks[0])]
+        mods = [self.stem, self.stem_ln, self.stage(0)]
         return [p for m in mods for p in m.parameters()]
 
     def active_modules(self):
@@ -209,7 +217,7 @@ class DynamicConvNeXt(nn.Module, DynamicMixin):
         depth states skip, and the output norms of stages outside ``out_indices``."""
         mods = [self.stem, self.stem_ln, self.ds1_ln, self.ds1_conv, self.ds2_ln, self.ds2_conv, self.ds3_ln,
                 self.ds3_conv]
-        mods += [getattr(self, "norm%d" % i) for i in range(4) if i in self.out_indices]
-        for name in self.blocks:
-            mods.extend(getattr(self, name).active_blocks())
+        mods += [self.out_norm(i) for i in range(4) if i in self.out_indices]
+        for i in range(4):
+            mods.extend(self.stage(i).active_blocks())
         return mods

@@ -202,6 +202,43 @@ int gs_layer_scale_backward(const float* dout, const float* z, const float* gamm
                             int32_t lddz, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* ConvNeXt V2: GELU fused with Global Response Normalization (arXiv 2301.00808)                */
+/* ------------------------------------------------------------------------------------------ */
+/* On the [N, P, C] hidden tensor of a block (P = H*W pixels per sample, C ACTIVE channels, NHWC rows
+ * with a pixel pitch per operand), with a = gelu(x) in the exact erf form of gs_gelu_*:
+ *   G[n,c]  = sqrt(sum_p a[n,p,c]^2)
+ *   Nx[n,c] = G[n,c] / (mean over the C active channels of G[n,:] + eps)
+ *   y[n,p,c] = a[n,p,c] * (1 + weight[c] * Nx[n,c]) + bias[c]
+ * a is never stored: the forward reads x twice and writes y, the backward reads dy and x twice and
+ * writes dx.  weight / bias are the physical max-size vectors; only their leading C entries are read,
+ * and only the leading C entries of dweight / dbias are written.  fp32 in every precision mode, no
+ * atomics, every sum in a fixed order (sums over pixels in runs of 256 cut per sample, so the result
+ * for a sample does not depend on the batch it sits in).  Checked on the host before any launch:
+ * GS_E_NULL (descriptor or pointer), GS_E_BADARG (N, P or C <= 0, a pitch below C, eps <= 0,
+ * N > 65535), GS_E_ALIGN (C or a pitch no multiple of 4, a pointer not 16-byte aligned), GS_E_WORKSPACE. */
+typedef struct gs_gelu_grn_desc {
+  int32_t N, P;           /* samples, pixels per sample (H*W)                                */
+  int32_t C;              /* ACTIVE channels                                                 */
+  int32_t ldx, ldy;       /* pixel strides of x and y                                        */
+  int32_t lddy, lddx;     /* pixel strides of dy and dx                                      */
+  float eps;
+} gs_gelu_grn_desc;
+/* bytes of scratch either direction needs (0 for a descriptor they would refuse): [2][C] partials per
+ * run of 256 pixels of a sample, and [4][C] per sample for their sums and the backward's coefficients. */
+size_t gs_gelu_grn_workspace_bytes(const gs_gelu_grn_desc* d);
+/* y as above; G [N][C] is saved for the backward. */
+int gs_gelu_grn_forward(const gs_gelu_grn_desc* d, const float* x, const float* weight, const float* bias,
+                        float* y, float* G, void* workspace, size_t workspace_bytes, void* stream);
+/* With S[n,c] = sum_p dy * a, T[n,c] = sum_p dy, D = weight * S and m = mean_c G[n,:] + eps:
+ *   dbias[c] = sum_n T,  dweight[c] = sum_n Nx * S  (samples added in order),
+ *   dG[n,c] = D / m - (1/C) sum_c' D[n,c'] G[n,c'] / m^2,
+ *   dx = (dy * (1 + weight * Nx) + a * dG / G) * gelu'(x),  the term through G zero where G == 0.
+ * a and gelu' are recomputed from the saved pre-activation x.  dx may be dy's buffer. */
+int gs_gelu_grn_backward(const gs_gelu_grn_desc* d, const float* x, const float* dy, const float* weight,
+                         const float* G, float* dx, float* dweight, float* dbias, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* ConvTranspose2d(kernel_size = 2, stride = 2), forward only (BEiT's fpn1 / fpn2)              */
 /* ------------------------------------------------------------------------------------------ */
 /* y[n, 2 h + dy, 2 w + dx, :Cout] = sum_ci x[n, h, w, ci] * w4[ci][(2 dy + dx) * Cout + co] (+ bias[co]):
