@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from ..hip import ops
+from ..hip import ops, streams
 from ..hip import runtime as _runtime
 from ..hip.runtime import round_up, tape_function
 from .dynamic import DynamicMixin
@@ -762,7 +762,7 @@ class DynamicBottleneck(nn.Module, DynamicMixin):
         identity, br = x, None
         if self.downsample is not None:
             # The projection shortcut is independent of conv1 -> conv2: it runs on the branch stream
-            # beside them, forward and backward (ops.Branch).  In backward its data gradient is the
+            # beside them, forward and backward (streams.Branch).  In backward its data gradient is the
             # FIRST writer of x.g (a strided one clears the pixel classes it has no tap for) and
             # conv1's accumulates onto it after the join, so conv1 owns the input gradient here too.
             # The shortcut's BatchNorm is applied inside norm3's apply pass (relu(bn3(y3) + bn_s(y_s))):
@@ -771,7 +771,7 @@ class DynamicBottleneck(nn.Module, DynamicMixin):
             # convolutions that fill the chip alone and only take it away from the block's K3 launch:
             # K3 0.77 -> 0.64 of peak on the v1c supernet with no gain in images/s)
             small = self._shortcut_gflop(x) <= ops.BRANCH_SHORTCUT_MAX_GFLOP
-            br = ops.Branch(tape, x.t.device, ops.BRANCH_SHORTCUT and small)
+            br = streams.Branch(tape, x.t.device, ops.BRANCH_SHORTCUT and small)
             with br:
                 identity = self._shortcut_act(tape, x, ops.DEFER_SHORTCUT_BN
                                               and fused_call_ok(conv3, norm3))

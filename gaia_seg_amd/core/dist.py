@@ -235,9 +235,9 @@ class GradReducer:
             # the all-reduce is issued in the side stream's context — torch's RCCL backend makes its
             # communication stream wait for the stream that is current at the call.  (r01 joined the
             # side stream into the main stream here, which serialised backward behind every bucket.)
-            from ..hip import ops as _ops
-            _ops.flush_wgrads()   # (no-op when this call comes from a flush: the queue is already empty)
-            side = _ops.side_stream_after_main(self.flat_grad.device)
+            from ..hip import streams
+            streams.flush_wgrads()   # (no-op when this call comes from a flush: the queue is already empty)
+            side = streams.side_stream_after_main(self.flat_grad.device)
             with torch.cuda.stream(side):
                 self._issue(runs)
         else:

@@ -256,7 +256,7 @@ class ArenaOptimizerHook(Hook):
 
     Two instalments, each as early as its gradients are final:
       * everything but the stem and stage 1 once the weight-gradient stream has passed the
-        checkpoint behind stage 1 (ops.side_checkpoint);
+        checkpoint behind stage 1 (streams.side_checkpoint);
       * the stem and stage 1 after the weight-gradient stream has drained."""
 
     in_graph = True   # backward + SGD are part of a captured step graph (IterBasedRunner)
@@ -266,7 +266,7 @@ class ArenaOptimizerHook(Hook):
             raise NotImplementedError("grad_clip is not configured by the in-tree configs")
 
     def after_train_iter(self, runner):
-        from ..hip import ops
+        from ..hip import streams
         ck = runner.backward(runner.outputs["loss"])
         t0 = runner._tick()
         scale = runner.grad_scale()
@@ -277,10 +277,10 @@ class ArenaOptimizerHook(Hook):
             for ev in ck:
                 torch.cuda.current_stream().wait_event(ev)
             runner._sgd(early, scale, runner.hyper)
-            ops.join_side_streams()
+            streams.join_side_streams()
             runner._sgd(late, scale, runner.hyper)
         else:
-            ops.join_side_streams()
+            streams.join_side_streams()
             runner._sgd(runner.active_ranges, scale, runner.hyper)
         # the step cleared exactly the ranges backward wrote: the next zero_grad has nothing to do
         runner.arena.grads_clean = True
@@ -648,24 +648,24 @@ class IterBasedRunner:
         self.reducer.begin(self.trainable_params, self.cache_key)
 
     def backward(self, loss):
-        """``loss.backward()`` (seeded with the static loss scale) under ops.deferred_join, then the
+        """``loss.backward()`` (seeded with the static loss scale) under streams.deferred_join, then the
         branch streams joined and the reducer finished.  Returns the side stream's checkpoint events
         or None (kept in ``last_checkpoint``); joining the side stream is left to the caller, which
         may step the early instalment first (ArenaOptimizerHook)."""
-        from ..hip import ops
+        from ..hip import streams
         t0 = self._tick()
         self.mark("fwd_end")
-        with ops.deferred_join() as dj:
+        with streams.deferred_join() as dj:
             if self.loss_scale != 1.0:
                 loss.backward(gradient=self.loss_seed(loss))   # (static loss scale S)
             else:
                 loss.backward()
         t1 = self._tick("backward", t0)
         self.mark("bwd_end_main")
-        side = ops.side_stream(self.arena.device)
+        side = streams.side_stream(self.arena.device)
         if side is not None:
             self.mark("bwd_end_side0", side)
-        ops.join_branch_streams()      # (auxiliary head / shortcut work on the branch stream)
+        streams.join_branch_streams()  # (auxiliary head / shortcut work on the branch stream)
         self.reducer.finish()
         self._tick("finish+sgd", t1)
         self.last_checkpoint = dj.checkpoint
@@ -686,10 +686,10 @@ class IterBasedRunner:
 
     def _capture_step(self, key, data_batch):
         """Capture forward + backward + SGD of the current subnet into a graph, then run it once."""
-        from ..hip import ops, runtime
+        from ..hip import runtime, streams
         dev = self.arena.flat_param.device
         static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data_batch.items()}
-        ops.reserve_workspaces(dev)   # no workspace may be (re)allocated inside the capture
+        streams.reserve_workspaces(dev)   # no workspace may be (re)allocated inside the capture
         graph = torch.cuda.CUDAGraph()
         runtime.CAPTURE_LOG = []
         self.arena.capture_refs = []   # (the graph entry owns the tables its SGD launches name)
@@ -844,7 +844,7 @@ class IterBasedRunner:
     # gradients over the union of the members' ranges and one fused SGD step clears them again.
     # Eager only: no step graphs, no early / split SGD instalments.
     def _sandwich_iter(self, data_batch, members, kd_cfg):
-        from ..hip import ops
+        from ..hip import streams
         total, log_vars, union, names = None, OrderedDict(), [], []
         teacher = None
         n_random = 0
@@ -862,7 +862,7 @@ class IterBasedRunner:
                 out = self.model.train_step(data_batch, None, teacher_logits=teacher[0],
                                             aux_teacher_logits=teacher[1], **kd_cfg)
             self.backward(out["loss"])
-            ops.join_side_streams()    # (every stream joined: the member's gradients are final)
+            streams.join_side_streams()    # (every stream joined: the member's gradients are final)
             self.arena.accumulate(self.active_ranges, into="buffer")
             self.arena.grads_clean = True          # (the move left zeros behind)
             union = _ranges_union(union, self.active_ranges)

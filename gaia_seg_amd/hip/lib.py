@@ -114,16 +114,24 @@ ATTENTION_HEAD_DIM = 64
 ATTENTION_RELPOS_MAX_ROWS = 8192   # GS_ATTENTION_RELPOS_MAX_ROWS
 
 
+def _fill_pitches(d, c, **pitches):
+    """Set the pitch fields of descriptor ``d`` from keywords named like them, forward pitches first:
+    a forward pitch (``ldX``) given as None becomes ``c``, a gradient's pitch (``lddX``) the pitch of
+    its forward operand ``ldX``."""
+    for name, v in pitches.items():
+        if v is None:
+            v = getattr(d, "ld" + name[3:]) if name.startswith("ldd") else c
+        setattr(d, name, v)
+
+
 def attention_desc(b, n, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=None, ldk=None, ldv=None, ldo=None,
                    lddq=None, lddk=None, lddv=None, lddo=None):
     """An ``AttentionDesc`` for ``b`` images of ``n`` tokens and ``heads`` active heads; a forward pitch
     defaults to 64 * heads, a gradient's pitch to the pitch of its forward operand."""
     d = AttentionDesc()
     d.B, d.N, d.heads, d.scale = b, n, heads, scale
-    c = ATTENTION_HEAD_DIM * heads
-    d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
-    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
-                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    _fill_pitches(d, ATTENTION_HEAD_DIM * heads, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo,
+                  lddq=lddq, lddk=lddk, lddv=lddv, lddo=lddo)
     return d
 
 
@@ -139,10 +147,8 @@ def attention_kv_desc(b, nq, nk, heads, scale=ATTENTION_HEAD_DIM ** -0.5, ldq=No
     pitches default as in ``attention_desc``."""
     d = AttentionKvDesc()
     d.B, d.Nq, d.Nk, d.heads, d.scale = b, nq, nk, heads, scale
-    c = ATTENTION_HEAD_DIM * heads
-    d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
-    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
-                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    _fill_pitches(d, ATTENTION_HEAD_DIM * heads, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo,
+                  lddq=lddq, lddk=lddk, lddv=lddv, lddo=lddo)
     return d
 
 
@@ -163,10 +169,8 @@ def window_attention_desc(b, h, w, ws, shift, heads, ld_table=None, scale=WINDOW
     d = WindowAttentionDesc()
     d.B, d.H, d.W, d.ws, d.shift, d.heads, d.scale = b, h, w, ws, shift, heads, scale
     d.ld_table = heads if ld_table is None else ld_table
-    c = WINDOW_ATTENTION_HEAD_DIM * heads
-    d.ldq, d.ldk, d.ldv, d.ldo = (c if v is None else v for v in (ldq, ldk, ldv, ldo))
-    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
-                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    _fill_pitches(d, WINDOW_ATTENTION_HEAD_DIM * heads, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo,
+                  lddq=lddq, lddk=lddk, lddv=lddv, lddo=lddo)
     return d
 
 
@@ -196,9 +200,7 @@ def fcu_down_desc(b, t, d, eps=1e-6, ldz=None, ldxt=None, ldo=None, lddz=None, l
     defaults to d, a gradient's pitch to the pitch of its forward operand."""
     desc = FcuDownDesc()
     desc.B, desc.T, desc.D, desc.eps = b, t, d, eps
-    desc.ldz, desc.ldxt, desc.ldo = (d if v is None else v for v in (ldz, ldxt, ldo))
-    desc.lddz = desc.ldz if lddz is None else lddz
-    desc.lddxt = desc.ldxt if lddxt is None else lddxt
+    _fill_pitches(desc, d, ldz=ldz, ldxt=ldxt, ldo=ldo, lddz=lddz, lddxt=lddxt)
     return desc
 
 
@@ -220,8 +222,7 @@ def ocr_gather_desc(b, p, k, c, scale=1.0, ldl=None, ldf=None, ldc=None, lddl=No
     d = OcrGatherDesc()
     d.B, d.P, d.K, d.C, d.scale = b, p, k, c, scale
     d.ldl = (k + 3) // 4 * 4 if ldl is None else ldl
-    d.ldf, d.ldc = (c if v is None else v for v in (ldf, ldc))
-    d.lddl, d.lddf, d.lddc = (f if v is None else v for v, f in ((lddl, d.ldl), (lddf, d.ldf), (lddc, d.ldc)))
+    _fill_pitches(d, c, ldf=ldf, ldc=ldc, lddl=lddl, lddf=lddf, lddc=lddc)
     return d
 
 
@@ -237,9 +238,7 @@ def ocr_attend_desc(b, p, k, ch, ldq=None, ldk=None, ldv=None, ldo=None, lddq=No
     defaults to ch, a gradient's pitch to the pitch of its forward operand."""
     d = OcrAttendDesc()
     d.B, d.P, d.K, d.ch = b, p, k, ch
-    d.ldq, d.ldk, d.ldv, d.ldo = (ch if v is None else v for v in (ldq, ldk, ldv, ldo))
-    d.lddq, d.lddk, d.lddv, d.lddo = (f if v is None else v for v, f in
-                                      ((lddq, d.ldq), (lddk, d.ldk), (lddv, d.ldv), (lddo, d.ldo)))
+    _fill_pitches(d, ch, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, lddq=lddq, lddk=lddk, lddv=lddv, lddo=lddo)
     return d
 
 

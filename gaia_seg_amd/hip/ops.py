@@ -1,420 +1,36 @@
 """Tape-aware operators: each function launches the forward HIP kernel(s) through the C-ABI and
 records the closure that launches the backward kernel(s).
 
-Nothing in this file computes with torch ops on the data path; torch is used for allocation,
-stream handles and (SyncBN only) the tiny statistics exchange over RCCL.
+Nothing in this file computes with torch ops on the data path; torch is used for allocation
+and (SyncBN only) the tiny statistics exchange over RCCL.
+
+This module is the operator catalogue and the home of the policy flags (SIDE_WGRAD, BRANCH_*,
+DEFER_*: whether an op uses the side stream, a branch stream or a deferred BatchNorm).  The streams
+themselves, their scratch and the scopes that switch them are ``streams``; ``Act`` and the tape are
+``runtime``.  Imports go one way: lib <- streams <- runtime <- ops.
+
+Every backward closure gets the buffers its kernel writes from three helpers: ``_grad_target`` (the
+gradient of an input activation), ``_param_grad`` (of a parameter, followed by ``_notify_params``
+after the launch) and ``_qkv_grads`` (the three gradients of an attention op, which share one flag).
 """
 import ctypes
+import os
 
 import torch
 
-import os
-
 from . import lib as _lib
-from .runtime import WORKSPACE, Act, _Workspace, current_stream_ptr, round_up
+from . import streams as _streams
+from .runtime import Act, round_up
+from .streams import WORKSPACE as _ws
+from .streams import _notify, current_stream_ptr
 
-_ws = WORKSPACE
-
-# ---- stream state ------------------------------------------------------------------------------
-# Besides the training stream a device has one weight-gradient side stream and up to two branch
-# streams.  Every order between them is set by ``_fork`` (one event recorded on one stream, waited
-# for on another); the dirty flags say which of them hold work that the training stream has not
-# joined yet.  (More weight-gradient streams, an optimizer stream inside backward, stream priorities
-# and an earlier fork of the auxiliary head were measured and removed: profiles/r04_stream_experiments.md.)
-class _DeviceStreams:
-    __slots__ = ("side", "side_dirty", "branch", "origin", "branch_dirty")
-
-    def __init__(self):
-        self.side = None           # the weight-gradient stream (created on first use)
-        self.side_dirty = False
-        self.branch = {}           # slot -> branch stream (created on first use)
-        self.origin = {}           # slot -> raw handle of the stream the branch was last forked from
-        self.branch_dirty = set()  # slots with work the origin has not joined yet
-
-
-_streams = {}   # (device type, index) -> _DeviceStreams
-
-
-def _state(dev):
-    st = _streams.get((dev.type, dev.index))
-    if st is None:
-        st = _streams[(dev.type, dev.index)] = _DeviceStreams()
-    return st
-
-
-def _fork(src, dst, dev):
-    """Stream ``dst`` waits for everything queued on stream ``src`` so far (raw handles)."""
-    with torch.cuda.device(dev):
-        _lib.check(_L().gs_stream_fork(src, dst), "gs_stream_fork")
-
-
-# ---- weight gradients on a side stream -------------------------------------------------------
-# In backward the weight gradient of a conv is needed only by the optimizer (and the gradient
-# all-reduce), while the data gradient is on the critical path.  The wgrad kernels (MFMA-bound) are
-# therefore launched on a second HIP stream, fenced by events, and run concurrently with the
-# BN-backward / dgrad kernels of the following layers (HBM-bound) on the main stream.  The main
-# stream joins the side stream at the end of every tape backward and before a gradient bucket is
-# handed to RCCL.  GS_SIDE_WGRAD=0 keeps everything on one stream.
+# Policy: which ops use the streams of ``streams``.  GS_SIDE_WGRAD=0 keeps the conv weight gradients
+# on the stream of their data gradients; GS_BRANCH_SHORTCUT / GS_BRANCH_AUX switch the two uses of the
+# branch streams separately (GS_BRANCH=0, read by ``streams``, switches both off).
 SIDE_WGRAD = os.environ.get("GS_SIDE_WGRAD", "1") != "0"
-_ws_side = _Workspace()
-
-
-def _side_stream(dev):
-    st = _state(dev)
-    if st.side is None:
-        st.side = torch.cuda.Stream(device=dev)
-    return st.side
-
-
-def side_stream(dev):
-    """The weight-gradient stream of ``dev``, or None while nothing has used it."""
-    st = _streams.get((dev.type, dev.index))
-    return st.side if st is not None else None
-
-
-# Weight gradients are handed to the side stream in BATCHES: every hand-over costs one event on the
-# main stream (hipEventRecord puts a marker packet into the queue; the r02 kernel trace shows a
-# ~7 us bubble behind each of them, 57 per R50 step).  A conv's backward therefore only queues its
-# weight-gradient job; after WGRAD_BATCH jobs (or at the end of a tape, or before a gradient bucket
-# is all-reduced) one event covers them all and the jobs are launched on the side stream.  The
-# "gradient ready" notifications of the reducer fire when the job is actually enqueued.
-WGRAD_BATCH = max(1, int(os.environ.get("GS_WGRAD_BATCH", "4")))
-_wgrad_jobs = []
-_wgrad_stream = None   # raw handle of the stream the queued jobs' operands were produced on
-
-
-_side_keep = []   # (dy, x) of weight-gradient kernels launched on the side stream, until the join
-
-
-def queue_wgrad(d, x, dy, weight, gw, need, dev):
-    """x: Act (kept alive until the launch), dy: gradient of the conv output, gw: weight.grad."""
-    global _wgrad_stream
-    st = current_stream_ptr()
-    if _wgrad_jobs and st != _wgrad_stream:
-        flush_wgrads()     # one event covers one batch: a batch never mixes producer streams
-    _wgrad_stream = st
-    _wgrad_jobs.append((d, x, dy, weight, gw, need, dev))
-    if len(_wgrad_jobs) >= WGRAD_BATCH:
-        flush_wgrads()
-
-
-def flush_wgrads():
-    """One event for all queued weight-gradient jobs, then launch them on the side stream."""
-    global _wgrad_jobs
-    if not _wgrad_jobs:
-        return
-    jobs, _wgrad_jobs = _wgrad_jobs, []
-    L = _L()
-    dev = jobs[0][6]
-    side = _side_stream(dev)
-    _fork(_wgrad_stream, side.cuda_stream, dev)
-    with torch.cuda.device(dev):
-        for d, x, dy, weight, gw, need, _ in jobs:
-            ws_s = _side_workspace(need, dev, side)
-            # dy and x must outlive the side-stream kernel that reads them: they are kept referenced
-            # until the main stream has joined the side stream (join_side_streams) instead of being
-            # handed to the caching allocator with record_stream (two calls and one pending event
-            # per convolution and step)
-            _side_keep.append((dy, x))
-            # (descriptors are shared per layer: the operand-loader coefficients are per call)
-            d.in_affine = x.affine.data_ptr() if x.affine is not None else None
-            _lib.check(L.gs_conv2d_wgrad(ctypes.byref(d), x.ptr, dy.data_ptr(), gw.data_ptr(),
-                                         ws_s.data_ptr(), ws_s.numel(), side.cuda_stream),
-                       "gs_conv2d_wgrad")
-    _state(dev).side_dirty = True
-    for job in jobs:
-        _notify(job[3])
-
-
-_deferred = None   # the deferred_join scope a backward runs in (None: every tape joins the side stream)
-
-
-class deferred_join:
-    """``with ops.deferred_join() as dj: loss.backward()`` -- the tapes hand their weight gradients to
-    the side stream but do not join it (runtime.Tape.backward): the caller overlaps the optimizer
-    step with the last weight gradients and joins afterwards (join_side_streams).  ``dj.checkpoint``:
-    the events ``side_checkpoint`` left on the side streams (every weight gradient queued before them
-    is done once they have fired), or None when backward crossed no checkpoint.  Nothing outside
-    this scope switches the protocol on or off."""
-
-    def __init__(self):
-        self.checkpoint = None
-
-    def __enter__(self):
-        global _deferred
-        _deferred = self
-        return self
-
-    def __exit__(self, *exc):
-        global _deferred
-        _deferred = None
-        return False
-
-
-def side_checkpoint(tape):
-    """Mark a point of the backward replay (recorded in forward order, so it fires when backward
-    crosses it): all weight gradients of the layers AFTER this point have been handed to the side
-    stream; an event on the side stream lets the optimizer update those parameters while the side
-    stream still works on the layers before the point (the runner waits on deferred_join.checkpoint)."""
-    def backward():
-        dj = _deferred
-        if dj is None:
-            return
-        flush_wgrads()
-        events = [st.side.record_event() for st in _streams.values() if st.side_dirty]
-        dj.checkpoint = events or None
-    tape.record(backward)
-
-
-def join_side_streams(dev=None):
-    """Make the current stream wait for the weight-gradient kernels queued on the side stream."""
-    flush_wgrads()
-    for key, st in _streams.items():
-        if st.side_dirty and (dev is None or (dev.type, dev.index) == key):
-            _fork(st.side.cuda_stream, current_stream_ptr(), st.side.device)
-            st.side_dirty = False
-    if dev is None or not any(st.side_dirty for st in _streams.values()):
-        # everything the side stream read is now ordered before whatever the current stream does
-        # next: the operands may go back to the allocator
-        _side_keep.clear()
-
-
-def side_stream_after_main(dev):
-    """The side stream, made to wait for everything queued so far on the current stream and on the
-    branch streams of this device (a gradient bucket holds BatchNorm gradients written on the
-    training stream and, where a branch ran, on the branch stream)."""
-    s = _side_stream(dev)
-    st = _state(dev)
-    cur = current_stream_ptr()
-    _fork(cur, s.cuda_stream, dev)
-    others = set()
-    for slot, br in st.branch.items():
-        if slot in st.branch_dirty:
-            others.add(br.cuda_stream)
-            others.add(st.origin[slot])
-    for other in others:
-        if other != cur:
-            _fork(other, s.cuda_stream, dev)
-    st.side_dirty = True   # the main stream joins it at the end of backward
-    return s
-
-
-def _side_workspace(need, dev, side):
-    """Split-K scratch of the side stream (allocated under that stream, so the caching allocator
-    orders its reuse against that stream's kernels)."""
-    buf = _ws_side._buf.get((dev.type, dev.index, 0))
-    if buf is not None and buf.numel() >= need:
-        return buf
-    with torch.cuda.stream(side):
-        return _ws_side.get(need, dev)
-
-
-def reserve_workspaces(dev, nbytes=192 << 20):
-    """Size the main and the side-stream scratch buffers for the largest request a convolution of
-    the supernet can make (96 MiB of split-K slabs + reduction partials), so that a step graph
-    capture never sees a workspace being (re)allocated."""
-    _ws.get(nbytes, dev)
-    _side_workspace(nbytes, dev, _side_stream(dev))
-
-
-# ---- the branch stream -------------------------------------------------------------------------
-# A bs-2 step is ~450 launches of 5-100 us, each a single round of 1-4 workgroups per CU with its
-# ramp and its tail; the only thing that fills those is ANOTHER launch running beside
-# it.  Two sub-chains of the network are independent of the main chain and run on a second in-order
-# queue, fenced by events:
-#   * the projection shortcut (conv + BN) of a stage's first block, beside conv1 -> conv2, forward
-#     and backward (gaiaseg/models/utils/dynamic_res_layer.py:70-125);
-#   * the auxiliary head with its loss, beside the decode head
-#     ("dynamic_encoder_decoder-distill-backup (1).py":85-143: two independent consumers of x).
-# Same kernels, same operands, same results; only the queue differs.  GS_BRANCH=0 keeps one queue;
-# GS_BRANCH_SHORTCUT / GS_BRANCH_AUX switch the two uses separately.
-BRANCH = os.environ.get("GS_BRANCH", "1") != "0"
-BRANCH_SHORTCUT = BRANCH and os.environ.get("GS_BRANCH_SHORTCUT", "1") != "0"
-BRANCH_AUX = BRANCH and os.environ.get("GS_BRANCH_AUX", "1") != "0"
+BRANCH_SHORTCUT = _streams.BRANCH and os.environ.get("GS_BRANCH_SHORTCUT", "1") != "0"
+BRANCH_AUX = _streams.BRANCH and os.environ.get("GS_BRANCH_AUX", "1") != "0"
 BRANCH_SHORTCUT_MAX_GFLOP = float(os.environ.get("GS_BRANCH_SHORTCUT_MAX_GFLOP", "8"))
-SLOT_SHORTCUT, SLOT_AUX = 1, 2   # scratch slot / branch stream index (0 = the training stream)
-_branch_slot_of = {}     # raw stream handle -> slot (adopt_current_stream)
-_branch_cb_armed = False
-
-
-def _branch_stream(dev, slot):
-    st = _state(dev)
-    s = st.branch.get(slot)
-    if s is None:
-        s = st.branch[slot] = torch.cuda.Stream(device=dev)
-        _branch_slot_of[s.cuda_stream] = slot
-    return s
-
-
-def on_branch():
-    return _ws.slot != 0
-
-
-def prefork_branch(dev, slot):
-    """Make branch stream ``slot`` wait for what is queued on the current stream NOW; a later
-    ``branch_scope(..., forked=True)`` then starts from this point of the current stream instead of
-    from its tail at that time (the auxiliary head forks behind the backbone while the host goes on
-    to queue the decode head)."""
-    if not BRANCH or dev.type != "cuda" or on_branch():
-        return
-    br = _branch_stream(dev, slot)
-    st = _state(dev)
-    cur = current_stream_ptr()
-    _fork(cur, br.cuda_stream, dev)
-    st.origin[slot] = cur
-    st.branch_dirty.add(slot)
-
-
-def _enter_branch(dev, slot, fork=True):
-    """Fork: branch stream ``slot`` waits for everything queued on the current stream, then becomes
-    the current stream (with its own scratch buffers).  Returns the stream to go back to."""
-    flush_wgrads()            # (backward) queued weight gradients belong to the stream we leave
-    br = _branch_stream(dev, slot)
-    st = _state(dev)
-    prev = torch.cuda.current_stream(dev)
-    if fork or st.origin.get(slot) != prev.cuda_stream:
-        _fork(prev.cuda_stream, br.cuda_stream, dev)
-        st.origin[slot] = prev.cuda_stream
-    st.branch_dirty.add(slot)
-    torch.cuda.set_stream(br)
-    _ws.slot = slot
-    return prev
-
-
-def _leave_branch(prev):
-    flush_wgrads()
-    torch.cuda.set_stream(prev)
-    _ws.slot = 0
-
-
-def join_branch(dev, slot):
-    """The current stream waits for everything queued on branch stream ``slot`` so far."""
-    st = _state(dev)
-    if slot in st.branch_dirty:
-        _fork(st.branch[slot].cuda_stream, current_stream_ptr(), dev)
-
-
-def join_branch_streams():
-    """End of a step's backward: the stream the branches were forked from waits for them."""
-    global _branch_cb_armed
-    _branch_cb_armed = False
-    for st in _streams.values():
-        for slot, br in st.branch.items():
-            if slot in st.branch_dirty:
-                _fork(br.cuda_stream, st.origin[slot], br.device)
-        st.branch_dirty.clear()
-
-
-def adopt_current_stream():
-    """Entry of an autograd node's backward: autograd has made the node's forward stream current;
-    pick the matching scratch slot.  On a branch stream also arrange for the final join (nothing
-    else would order a later reader on the training stream behind, e.g., the auxiliary head's
-    BatchNorm gradients when no upstream node consumes a gradient of this one)."""
-    global _branch_cb_armed
-    prev = _ws.slot
-    if _branch_slot_of:
-        slot = _branch_slot_of.get(current_stream_ptr(), 0)
-        if slot != prev:
-            flush_wgrads()
-        _ws.slot = slot
-        if slot and not _branch_cb_armed:
-            _branch_cb_armed = True
-            torch.autograd.Variable._execution_engine.queue_callback(join_branch_streams)
-    return prev
-
-
-def restore_stream_slot(prev):
-    if _ws.slot != prev:
-        flush_wgrads()
-        _ws.slot = prev
-
-
-class branch_scope:
-    """``with ops.branch_scope(dev):`` evaluate a whole sub-model (the auxiliary head and its loss)
-    on a branch stream.  Its autograd nodes run their backward there too (autograd's stream
-    semantics); ``ops.join_branch(dev, slot)`` afterwards orders the current stream behind it.
-    ``forked``: the branch already waits for the right point of the current stream
-    (``prefork_branch``)."""
-
-    def __init__(self, dev, enabled=True, slot=SLOT_AUX, forked=False):
-        self.dev, self.slot, self.forked = dev, slot, forked
-        self.on = bool(enabled and BRANCH and dev.type == "cuda" and not on_branch())
-        self.prev = None
-
-    def __enter__(self):
-        if self.on:
-            self.prev = _enter_branch(self.dev, self.slot, fork=not self.forked)
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            _leave_branch(self.prev)
-        return False
-
-
-class Branch:
-    """A sub-chain of ONE tape evaluated on a branch stream.
-
-        br = Branch(tape, dev)
-        with br:                          # forward: fork; ops run (and record) on the branch
-            identity = shortcut(x)
-        a = conv1(x)
-        br.record_backward_join(tape)     # backward: everything recorded BEFORE this point runs
-                                          #           after the branch's backward has finished
-        b = conv2(a)
-        br.record_backward_body(tape)     # backward: fork here, replay the branch's closures
-        br.join()                         # forward: the current stream waits for the branch
-        out = conv3(b) + identity
-
-    Backward order on the host: conv3, [fork, branch body], conv2, [join], conv1 — the branch's data
-    gradient is the FIRST writer of x.g, conv1's accumulates onto it after the join.  With the
-    branch switched off the same closures run in the same order on one stream."""
-
-    __slots__ = ("tape", "dev", "on", "ops", "slot", "_saved", "_prev")
-
-    def __init__(self, tape, dev, enabled=True, slot=SLOT_SHORTCUT):
-        self.tape, self.dev, self.slot = tape, dev, slot
-        self.on = bool(enabled and BRANCH and dev.type == "cuda" and not on_branch())
-        self.ops = []
-        self._saved = self._prev = None
-
-    def __enter__(self):
-        self._saved = self.tape.ops
-        self.tape.ops = self.ops
-        if self.on:
-            self._prev = _enter_branch(self.dev, self.slot)
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            _leave_branch(self._prev)
-        self.tape.ops = self._saved
-        self._saved = self._prev = None
-        return False
-
-    def join(self):
-        if self.on:
-            join_branch(self.dev, self.slot)
-
-    def record_backward_join(self, tape):
-        if not self.on:
-            return
-        dev, slot = self.dev, self.slot
-        tape.record(lambda: join_branch(dev, slot))
-
-    def record_backward_body(self, tape):
-        body, dev, on, slot = self.ops, self.dev, self.on, self.slot
-
-        def backward():
-            prev = _enter_branch(dev, slot) if on else None
-            try:
-                for fn in reversed(body):
-                    fn()
-            finally:
-                if on:
-                    _leave_branch(prev)
-        if body:
-            tape.record(backward)
 
 
 def _L():
@@ -452,12 +68,6 @@ def ensure_grad(param):
         raise RuntimeError("gradient layout %s differs from parameter layout %s"
                            % (param.grad.stride(), param.stride()))
     return param.grad
-
-
-def _notify(param):
-    hook = param.__dict__.get("_gs_grad_ready")
-    if hook is not None:
-        hook(param)
 
 
 conv_out_size = _lib.conv_out_size
@@ -686,7 +296,7 @@ def conv2d(tape, x, weight, bias, co, stride=1, pad=0, dil=1, out=None, tag=None
         if weight.requires_grad:
             gw = ensure_grad(weight)
             if SIDE_WGRAD:
-                queue_wgrad(d, x, dy, weight, gw, need, dev)   # notifies when launched
+                _streams.queue_wgrad(d, x, dy, weight, gw, need, dev)   # notifies when launched
             else:
                 _lib.check(L.gs_conv2d_wgrad(ctypes.byref(d), x.ptr, dy.data_ptr(), gw.data_ptr(),
                                              ws_b.data_ptr(), ws_b.numel(), s), "gs_conv2d_wgrad")
@@ -776,12 +386,49 @@ def _active_width(x, param, what):
     return c
 
 
-def _param_grad(param, c, dev):
-    """where a kernel writes the gradient of the leading ``c`` channels of ``param``: param.grad, or
-    scratch for a frozen parameter (the kernels always produce it)"""
-    if param.requires_grad:
-        return ensure_grad(param)
-    return torch.empty(c, dtype=torch.float32, device=dev)
+def _input_grad(x):
+    """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
+    x.g already held a contribution, else 0 after allocating it (a channel slice's storage is
+    allocated, zeroed, on the buffer that owns it)."""
+    if x.g is not None:
+        return 1
+    root = x
+    while root.parent is not None:
+        root = root.parent
+    if root is x:
+        x.new_grad()
+    elif root.g is None:
+        root.new_grad().zero_()
+    return 0
+
+
+def _grad_target(x, sole=None):
+    """Where a kernel that always produces the gradient of its input ``x`` writes it -> (tensor,
+    accumulate flag).  An input that requires a gradient gets ``x.g`` (``_input_grad``); ``sole``
+    names an input whose kernel has no accumulate form, so this op must be its only consumer: a
+    gradient that is already held raises.  An input that needs none gets scratch with x's own
+    shape AND pitch (flag 0): a kernel that addresses the gradient with the descriptor's ``ldx`` may
+    rely on that, every other caller passes the ``stride(2)`` of what it got."""
+    if not x.requires_grad:
+        return Act.empty(x.N, x.H, x.W, x.C, x.t.device, ld=x.ld).t, 0
+    acc = _input_grad(x)
+    if acc and sole:
+        raise RuntimeError("%s has more than one consumer; unsupported" % sole)
+    return x.g, acc
+
+
+def _param_grad(param):
+    """Where a kernel that always produces the gradient of ``param`` writes it: param.grad, or scratch
+    with the parameter's layout for a frozen one (the kernels address it with the parameter's pitch).
+    ``_notify_params`` follows the launch."""
+    return ensure_grad(param) if param.requires_grad else torch.empty_like(param)
+
+
+def _notify_params(*params):
+    """After the launch that wrote them: the gradients of those ``params`` that take one are ready."""
+    for p in params:
+        if p is not None and p.requires_grad:
+            _notify(p)
 
 
 def layernorm(tape, x, weight, bias, eps=1e-6, out=None):
@@ -806,20 +453,13 @@ def layernorm(tape, x, weight, bias, eps=1e-6, out=None):
             return
         keep = stats  # noqa: F841 -- the closure owns the storage behind mean_ptr / rstd_ptr
         db = ctypes.byref(d)
-        gw, gb = _param_grad(weight, c, dev), _param_grad(bias, c, dev)
+        gw, gb = _param_grad(weight), _param_grad(bias)
         ws = _ws.get(L.gs_layernorm_workspace_bytes(db), dev)
-        if x.requires_grad:
-            acc = _input_grad(x)
-            dx = x.g
-        else:
-            acc, dx = 0, torch.empty_like(x.t)
+        dx, acc = _grad_target(x)   # (addressed with d.ldx)
         _lib.check(L.gs_layernorm_backward(db, x.ptr, dy.data_ptr(), weight.data_ptr(), mean_ptr, rstd_ptr,
                                            dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), acc, ws.data_ptr(),
                                            ws.numel(), current_stream_ptr()), "gs_layernorm_backward")
-        if weight.requires_grad:
-            _notify(weight)
-        if bias.requires_grad:
-            _notify(bias)
+        _notify_params(weight, bias)
 
     tape.record(backward)
     return out
@@ -875,23 +515,15 @@ def gelu_grn(tape, x, weight, bias, eps=1e-6, out=None):
         dy = out.g
         if dy is None:
             return
-        gw, gb = _param_grad(weight, c, dev), _param_grad(bias, c, dev)
-        if x.requires_grad:
-            if _input_grad(x):
-                raise RuntimeError("gelu_grn input has more than one consumer; unsupported")
-            dx = x.g
-        else:
-            dx = torch.empty_like(x.t)
+        gw, gb = _param_grad(weight), _param_grad(bias)
+        dx, _ = _grad_target(x, "gelu_grn input")
         d.lddy, d.lddx = dy.stride(2), dx.stride(2)
         db = ctypes.byref(d)
         ws = _ws.get(L.gs_gelu_grn_workspace_bytes(db), dev)
         _lib.check(L.gs_gelu_grn_backward(db, x.ptr, dy.data_ptr(), weight.data_ptr(), G.data_ptr(),
                                           dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), ws.data_ptr(),
                                           ws.numel(), current_stream_ptr()), "gs_gelu_grn_backward")
-        if weight.requires_grad:
-            _notify(weight)
-        if bias.requires_grad:
-            _notify(bias)
+        _notify_params(weight, bias)
 
     tape.record(backward)
     return out
@@ -931,13 +563,12 @@ def layer_scale_add(tape, identity, z, gamma, out=None):
         else:
             if _input_grad(z):
                 raise RuntimeError("layer-scaled branch has more than one consumer; unsupported")
-            gg = _param_grad(gamma, c, dev)
+            gg = _param_grad(gamma)
             ws = _ws.get(L.gs_layer_scale_workspace_bytes(rows, c), dev)
             _lib.check(L.gs_layer_scale_backward(dout.data_ptr(), z.ptr, gamma.data_ptr(), z.g.data_ptr(),
                                                  gg.data_ptr(), rows, c, dout.stride(2), z.ld, z.g.stride(2),
                                                  ws.data_ptr(), ws.numel(), s), "gs_layer_scale_backward")
-            if gamma.requires_grad:
-                _notify(gamma)
+            _notify_params(gamma)
         if identity.requires_grad:
             _pass_residual_grad(L, identity, dout, rows, c, s)
 
@@ -971,6 +602,27 @@ def _attention_setup(tape, what, q, k, v, heads, scale, out, f16):
     return q, k, v, out, lse, d, sfx
 
 
+def _qkv_grads(q, k, v):
+    """First half of the q / k / v gradient set-up that ``attention``, ``attention_kv`` and
+    ``window_attention`` share: the three gradients exist afterwards -> (held, accs) with ``held`` =
+    some gradient held a contribution before this call and ``accs`` = the ``_input_grad`` flag of each.
+    The two differ exactly when the three are column slices of one buffer that had no gradient yet:
+    allocating q's zeroes the parent, so k and v then report a (zero) gradient.  The backward kernels
+    take ONE accumulate flag for the three; each op derives it from this pair in its own way."""
+    held = any(t.g is not None for t in (q, k, v))
+    return held, [_input_grad(t) for t in (q, k, v)]
+
+
+def _qkv_start(d, q, k, v, dy, accs, acc):
+    """Second half, under the accumulate flag ``acc`` the op passes: with it set, the gradients that
+    start fresh are zeroed; the descriptor gets its four gradient pitches."""
+    if acc:
+        for t, a in zip((q, k, v), accs):
+            if not a:
+                t.g.zero_()
+    d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+
+
 def attention(tape, q, k, v, heads, scale, out=None, f16=False):
     """Multi-head softmax self-attention, head dimension 64: ``heads`` active heads in the leading
     64 * heads columns of q, k and v (token activations [B, 1, N, 64 * heads], each with its own pitch: three
@@ -989,16 +641,16 @@ def attention(tape, q, k, v, heads, scale, out=None, f16=False):
         dy = out.g
         if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad):
             return
-        accs = [_input_grad(t) for t in (q, k, v)]
-        if any(accs) and not all(accs):   # one flag for the three: start the fresh ones from zero
-            for t, acc in zip((q, k, v), accs):
-                if not acc:
-                    t.g.zero_()
-        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        _, accs = _qkv_grads(q, k, v)
+        # accumulate as soon as one of the three reports a gradient, slices of a just-zeroed buffer
+        # included (window_attention writes in that case; unifying the two changes what the kernel is
+        # asked to do and is left to a change of its own)
+        acc = 1 if any(accs) else 0
+        _qkv_start(d, q, k, v, dy, accs, acc)
         db = ctypes.byref(d)
         ws = _ws.get(ws_bytes(db), dev)
         _lib.check(bwd(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(), q.g.data_ptr(),
-                       k.g.data_ptr(), v.g.data_ptr(), 1 if any(accs) else 0, ws.data_ptr(), ws.numel(),
+                       k.g.data_ptr(), v.g.data_ptr(), acc, ws.data_ptr(), ws.numel(),
                        current_stream_ptr()), "gs_attention_backward" + sfx)
 
     tape.record(backward)
@@ -1030,18 +682,15 @@ def attention_kv(tape, q, k, v, heads, scale, out=None):
         dy = out.g
         if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad):
             return
-        accs = [_input_grad(t) for t in (q, k, v)]
-        if any(accs) and not all(accs):   # one flag for the three: start the fresh ones from zero
-            for t, acc in zip((q, k, v), accs):
-                if not acc:
-                    t.g.zero_()
-        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        _, accs = _qkv_grads(q, k, v)
+        acc = 1 if any(accs) else 0   # (as ``attention``: slices of a just-zeroed buffer accumulate)
+        _qkv_start(d, q, k, v, dy, accs, acc)
         db = ctypes.byref(d)
         ws = _ws.get(L.gs_attention_kv_workspace_bytes(db), dev)
         _lib.check(L.gs_attention_kv_backward(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(),
-                                              q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(),
-                                              1 if any(accs) else 0, ws.data_ptr(), ws.numel(),
-                                              current_stream_ptr()), "gs_attention_kv_backward")
+                                              q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(), acc,
+                                              ws.data_ptr(), ws.numel(), current_stream_ptr()),
+                   "gs_attention_kv_backward")
 
     tape.record(backward)
     return out
@@ -1077,25 +726,21 @@ def window_attention(tape, q, k, v, table, heads, ws, shift, scale, out=None):
         dy = out.g
         if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad or table.requires_grad):
             return
-        fresh = all(t.g is None for t in (q, k, v))   # nothing held a contribution: every output is written (=)
-        accs = [_input_grad(t) for t in (q, k, v)]
-        if not fresh and not all(accs):   # one flag for the three: start the fresh ones from zero
-            for t, acc in zip((q, k, v), accs):
-                if not acc:
-                    t.g.zero_()
-        acc = 0 if fresh else 1
-        gt = ensure_grad(table) if table.requires_grad else torch.empty_like(table)
+        held, accs = _qkv_grads(q, k, v)
+        # accumulate only where a gradient was held BEFORE this call: with nothing held every output is
+        # written (=), also into slices of a just-zeroed buffer (``attention`` accumulates there)
+        acc = 1 if held else 0
+        _qkv_start(d, q, k, v, dy, accs, acc)
+        gt = _param_grad(table)
         if acc:   # the flag covers the table too: its active columns start from zero
             gt[:, :heads].zero_()
-        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
         db = ctypes.byref(d)
         ws_buf = _ws.get(L.gs_window_attention_workspace_bytes(db), dev)
         _lib.check(L.gs_window_attention_backward(db, q.ptr, k.ptr, v.ptr, table.data_ptr(), out.ptr, lse.data_ptr(),
                                                   dy.data_ptr(), q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(),
                                                   gt.data_ptr(), acc, ws_buf.data_ptr(), ws_buf.numel(),
                                                   current_stream_ptr()), "gs_window_attention_backward")
-        if table.requires_grad:
-            _notify(table)
+        _notify_params(table)
 
     tape.record(backward)
     return out
@@ -1177,23 +822,15 @@ def cell_layernorm(tape, x, weight, bias, eps=1e-5, out=None):
             raise RuntimeError("cell_layernorm: the gradient's pitch %d differs from the output's %d"
                                % (dy.stride(2), d.ldy))
         db = ctypes.byref(d)
-        gw = ensure_grad(weight) if weight.requires_grad else torch.empty_like(weight)
-        gb = ensure_grad(bias) if bias.requires_grad else torch.empty_like(bias)
+        gw, gb = _param_grad(weight), _param_grad(bias)
         ws_buf = _ws.get(L.gs_cell_layernorm_workspace_bytes(db), dev)
-        if x.requires_grad:
-            acc = _input_grad(x)
-            dx = x.g
-        else:
-            acc, dx = 0, torch.empty_like(x.t)
-        if dx.stride(2) != d.ldx:
+        dx, acc = _grad_target(x)
+        if dx.stride(2) != d.ldx:   # (an installed gradient of another pitch; scratch has x's)
             raise RuntimeError("cell_layernorm: dx has pitch %d, x has %d" % (dx.stride(2), d.ldx))
         _lib.check(L.gs_cell_layernorm_backward(db, x.ptr, dy.data_ptr(), weight.data_ptr(), mean_ptr, rstd_ptr,
                                                 dx.data_ptr(), gw.data_ptr(), gb.data_ptr(), acc, ws_buf.data_ptr(),
                                                 ws_buf.numel(), current_stream_ptr()), "gs_cell_layernorm_backward")
-        if weight.requires_grad:
-            _notify(weight)
-        if bias.requires_grad:
-            _notify(bias)
+        _notify_params(weight, bias)
 
     tape.record(backward)
     return out
@@ -1284,21 +921,12 @@ def vit_tokens(tape, patches, cls_token, pos_embed):
         dx = out.g
         if dx is None:
             return
-        gc = _param_grad(cls_token, dch, dev)
-        gp = ensure_grad(pos_embed) if pos_embed.requires_grad else torch.empty_like(pos_embed)
-        if patches.requires_grad:
-            if _input_grad(patches):
-                raise RuntimeError("patch embedding has more than one consumer; unsupported")
-            dp = patches.g
-        else:
-            dp = torch.empty_like(patches.t)
+        gc, gp = _param_grad(cls_token), _param_grad(pos_embed)
+        dp, _ = _grad_target(patches, "patch embedding")
         _lib.check(L.gs_vit_tokens_backward(dx.data_ptr(), dx.stride(2), dp.data_ptr(), dp.stride(2),
                                             gc.data_ptr(), gp.data_ptr(), ldpos, b, t, dch,
                                             current_stream_ptr()), "gs_vit_tokens_backward")
-        if cls_token.requires_grad:
-            _notify(cls_token)
-        if pos_embed.requires_grad:
-            _notify(pos_embed)
+        _notify_params(cls_token, pos_embed)
 
     tape.record(backward)
     return out
@@ -1353,18 +981,12 @@ def fcu_tokens(tape, patches, cls_token):
         dx = out.g
         if dx is None:
             return
-        gc = _param_grad(cls_token, dch, dev)
-        if patches.requires_grad:
-            if _input_grad(patches):
-                raise RuntimeError("patch embedding has more than one consumer; unsupported")
-            dp = patches.g
-        else:
-            dp = torch.empty_like(patches.t)
+        gc = _param_grad(cls_token)
+        dp, _ = _grad_target(patches, "patch embedding")
         _lib.check(L.gs_fcu_tokens_backward(dx.data_ptr(), dx.stride(2), dp.data_ptr(), dp.stride(2),
                                             gc.data_ptr(), b, t, dch, current_stream_ptr()),
                    "gs_fcu_tokens_backward")
-        if cls_token.requires_grad:
-            _notify(cls_token)
+        _notify_params(cls_token)
 
     tape.record(backward)
     return out
@@ -1397,18 +1019,9 @@ def fcu_down(tape, z, x_t, ln):
         if dout is None:
             return
         keep = stats  # noqa: F841 -- the closure owns the storage behind mean_ptr / rstd_ptr
-        gw, gb = _param_grad(weight, c, dev), _param_grad(bias, c, dev)
-        if z.requires_grad:
-            if _input_grad(z):
-                raise RuntimeError("fcu_down: the projected map has more than one consumer; unsupported")
-            dz = z.g
-        else:
-            dz = torch.empty_like(z.t)
-        if x_t.requires_grad:
-            acc = _input_grad(x_t)
-            dxt = x_t.g
-        else:
-            acc, dxt = 0, torch.empty_like(x_t.t)
+        gw, gb = _param_grad(weight), _param_grad(bias)
+        dz, _ = _grad_target(z, "fcu_down: the projected map")
+        dxt, acc = _grad_target(x_t)
         d.ldo, d.lddz, d.lddxt = dout.stride(2), dz.stride(2), dxt.stride(2)
         db = ctypes.byref(d)
         ws = _ws.get(L.gs_fcu_down_workspace_bytes(db), dev)
@@ -1416,10 +1029,7 @@ def fcu_down(tape, z, x_t, ln):
                                           mean_ptr, rstd_ptr, dz.data_ptr(), dxt.data_ptr(), gw.data_ptr(),
                                           gb.data_ptr(), acc, ws.data_ptr(), ws.numel(), current_stream_ptr()),
                    "gs_fcu_down_backward")
-        if weight.requires_grad:
-            _notify(weight)
-        if bias.requires_grad:
-            _notify(bias)
+        _notify_params(weight, bias)
 
     tape.record(backward)
     return out
@@ -1458,16 +1068,6 @@ def fcu_up_add(tape, x, r, s):
     return out
 
 
-def _grad_or_scratch(x, what):
-    """where a kernel that always produces the gradient of ``x`` writes it: ``x.g`` (first and only
-    contribution) or scratch with x's layout rules for an input that needs none"""
-    if not x.requires_grad:
-        return Act.empty(x.N, x.H, x.W, x.C, x.t.device).t
-    if _input_grad(x):
-        raise RuntimeError("%s has more than one consumer; unsupported" % what)
-    return x.g
-
-
 def ocr_gather(tape, feats, logits, scale=1.0):
     """OCRNet's soft object regions (mmseg's SpatialGatherModule): from the pixel features ``feats``
     [B, H, W, C] (possibly a channel slice of a wider buffer) and the previous head's ``logits`` [B, H, W, K]
@@ -1496,12 +1096,8 @@ def ocr_gather(tape, feats, logits, scale=1.0):
         dctx = out.g
         if dctx is None:
             return
-        dl = _grad_or_scratch(logits, "ocr_gather: the logits map")
-        if feats.requires_grad:
-            acc = _input_grad(feats)
-            df = feats.g
-        else:
-            acc, df = 0, torch.empty_like(feats.t)
+        dl, _ = _grad_target(logits, "ocr_gather: the logits map")
+        df, acc = _grad_target(feats)
         d.lddl, d.lddf, d.lddc = dl.stride(2), df.stride(2), dctx.stride(2)
         wsb = _ws.get(L.gs_ocr_gather_workspace_bytes(db), dev)
         _lib.check(L.gs_ocr_gather_backward(db, logits.ptr, feats.ptr, out.ptr, stats.data_ptr(),
@@ -1537,9 +1133,9 @@ def ocr_attend(tape, q, k, v):
         dout = out.g
         if dout is None:
             return
-        dq = _grad_or_scratch(q, "ocr_attend: the query map")
-        dk = _grad_or_scratch(k, "ocr_attend: the key map")
-        dv = _grad_or_scratch(v, "ocr_attend: the value map")
+        dq, _ = _grad_target(q, "ocr_attend: the query map")
+        dk, _ = _grad_target(k, "ocr_attend: the key map")
+        dv, _ = _grad_target(v, "ocr_attend: the value map")
         d.lddq, d.lddk, d.lddv, d.lddo = dq.stride(2), dk.stride(2), dv.stride(2), dout.stride(2)
         db = ctypes.byref(d)
         ws = _ws.get(L.gs_ocr_attend_workspace_bytes(db), dev)
@@ -1549,22 +1145,6 @@ def ocr_attend(tape, q, k, v):
 
     tape.record(backward)
     return out
-
-
-def _input_grad(x):
-    """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
-    x.g already held a contribution, else 0 after allocating it (a channel slice's storage is
-    allocated, zeroed, on the buffer that owns it)."""
-    if x.g is not None:
-        return 1
-    root = x
-    while root.parent is not None:
-        root = root.parent
-    if root is x:
-        x.new_grad()
-    elif root.g is None:
-        root.new_grad().zero_()
-    return 0
 
 
 def _pass_residual_grad(L, residual, src, rows, C, stream):
@@ -1739,10 +1319,7 @@ def batchnorm(tape, x, bn, relu=False, residual=None, out=None, inplace=False):
                                      x.g.stride(2), gw.data_ptr() if (wgrad and not synced) else None,
                                      gb.data_ptr() if (bgrad and not synced) else None, s),
                    "gs_bn_bwd_apply")
-        if wgrad:
-            _notify(bn.weight)
-        if bgrad:
-            _notify(bn.bias)
+        _notify_params(bn.weight, bn.bias)
         if residual is not None and residual.requires_grad:
             # dy: the masked (relu) or plain (no relu) upstream gradient
             _pass_residual_grad(L, residual, dy, rows, C, s)
@@ -1957,12 +1534,9 @@ def conv_bn(tape, x, weight, co, bn, stride=1, pad=0, dil=1, relu=False, residua
             if fuse.mode == 3:
                 BNBWD_FUSED_MASK_COUNT += 1
             x.bnb_sums = True        # x.g now holds the MASKED gradient of the producer's ReLU
-        if wgrad_bn:
-            _notify(bn.weight)
-        if bgrad_bn:
-            _notify(bn.bias)
+        _notify_params(bn.weight, bn.bias)
         if queued:
-            queue_wgrad(d, x, dy, weight, gw, need, dev)     # the side stream gets it in a batch
+            _streams.queue_wgrad(d, x, dy, weight, gw, need, dev)     # the side stream gets it in a batch
         elif gw is not None:
             _notify(weight)
         if residual is not None and residual.requires_grad:

@@ -1,4 +1,8 @@
-"""Execution runtime of the MI355X path: NHWC activations, a hand-run backward tape, workspaces.
+"""Execution runtime of the MI355X path: NHWC activations (``Act``) and a hand-run backward tape
+(``Tape``, ``tape_function``).  The streams the kernels run on and their scratch live below it in
+``streams`` (``current_stream_ptr`` and ``WORKSPACE`` are re-exported here for the many modules
+that launch kernels and import them from ``runtime``); the operators that fill a tape live above
+it in ``ops``.
 
 Design (MI355X-first, not a translation of the reference's per-op autograd graph):
 
@@ -14,17 +18,8 @@ Design (MI355X-first, not a translation of the reference's per-op autograd graph
 import torch
 
 from . import lib as _lib
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def current_stream_ptr():
-    """hipStream_t of torch's current stream on the current device (raw handle: this is called
-    once per kernel launch, torch.cuda.current_stream() costs ~9 us of host time each)."""
-    if _raw_stream is not None:
-        return _raw_stream(torch.cuda.current_device())
-    return torch.cuda.current_stream().cuda_stream
+from . import streams as _streams
+from .streams import WORKSPACE, current_stream_ptr  # noqa: F401  (re-exported)
 
 
 def require_gpu_tensor(t, what):
@@ -34,39 +29,6 @@ def require_gpu_tensor(t, what):
             "(there is no CPU fallback)" % (what, t.device))
     if t.dtype != torch.float32:
         raise TypeError("%s must be float32, got %s" % (what, t.dtype))
-
-
-class _Workspace:
-    """Grow-only scratch buffer per device and stream slot (split-K slabs, reduction partials).
-
-    All kernels of one in-order queue share a buffer.  ``slot`` selects the queue: 0 = the training
-    stream, 1 = the branch stream (hip/ops.py: projection shortcuts, the auxiliary head); whoever
-    switches the current stream switches the slot with it."""
-
-    def __init__(self):
-        self._buf = {}
-        self._retired = []   # outgrown buffers: captured step graphs may still point into them
-        self.slot = 0
-
-    def get(self, nbytes, device):
-        nbytes = max(int(nbytes), 256)
-        key = (device.type, device.index, self.slot)
-        buf = self._buf.get(key)
-        if buf is None or buf.numel() < nbytes:
-            # round up generously so later, larger requests rarely reallocate
-            size = max(nbytes, 1 << 20)
-            size = 1 << (size - 1).bit_length()
-            if buf is not None:
-                self._retired.append(buf)
-            buf = torch.empty(size, dtype=torch.uint8, device=device)
-            self._buf[key] = buf
-        return buf
-
-    def reserve(self, nbytes, device):
-        self.get(nbytes, device)
-
-
-WORKSPACE = _Workspace()
 
 
 def round_up(x, m):
@@ -211,11 +173,7 @@ class Tape:
         self.ops = []
         for fn in reversed(ops):
             fn()
-        from . import ops as _ops
-        if _ops._deferred is not None:
-            _ops.flush_wgrads()        # the caller joins (runner: after the early part of the SGD step)
-        else:
-            _ops.join_side_streams()   # weight gradients queued on the side stream
+        _streams.end_tape_backward()   # weight gradients queued on the side stream
 
 
 # While a training step is being captured into a HIP graph (core/runner.py) host-side effects that a
@@ -263,20 +221,12 @@ class _TapeFunction(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, *grads):
         # autograd runs a node's backward on the stream its forward ran on: a head evaluated on the
-        # branch stream (ops.branch_scope) comes back here with that stream current
-        from . import ops as _ops
-        prev_slot = _ops.adopt_current_stream()
-        try:
-            return _TapeFunction._backward_on_stream(ctx, *grads)
-        finally:
-            _ops.restore_stream_slot(prev_slot)
-
-    @staticmethod
-    def _backward_on_stream(ctx, *grads):
-        for o, g in zip(ctx.outs, grads):
-            if g is not None:
-                o.set_grad_from_nchw(g)
-        ctx.tape.backward()
+        # branch stream (streams.branch_scope) comes back here with that stream current
+        with _streams.adopt_current_stream():
+            for o, g in zip(ctx.outs, grads):
+                if g is not None:
+                    o.set_grad_from_nchw(g)
+            ctx.tape.backward()
         in_grads = []
         for a in ctx.acts_in:
             if a.requires_grad and a.g is not None:

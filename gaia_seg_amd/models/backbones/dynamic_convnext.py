@@ -15,7 +15,7 @@ import torch.nn as nn
 from ...core.bricks import (DynamicConv2d, DynamicLayerNorm, DynamicLinear, build_activation_layer,
                             build_conv_layer, build_norm_layer)
 from ...core.dynamic import DynamicMixin, unzip_meta
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import tape_function
 from ..builder import BACKBONES
 
@@ -195,7 +195,7 @@ class DynamicConvNeXt(nn.Module, DynamicMixin):
         for i in range(4):
             x = self.stage(i).forward_act(tape, x)
             if i == 0:
-                ops.side_checkpoint(tape)   # as DynamicResNet: later layers' gradients are ready first
+                streams.side_checkpoint(tape)   # as DynamicResNet: later layers' gradients are ready first
             if i in self.out_indices:
                 outs.append(self.out_norm(i).forward_act(tape, x))
             if i < 3:

@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from ...core.bricks import DynamicConv2d, DynamicLayerNorm, DynamicLinear, GELU
 from ...core.dynamic import DynamicMixin, unzip_meta
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import Act, tape_function
 from ..builder import BACKBONES
 
@@ -306,7 +306,7 @@ class DynamicMixVisionTransformer(nn.Module, DynamicMixin):
         for i, stage in enumerate(self.stages):
             x = stage.forward_act(tape, x)
             if i == 0:
-                ops.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
+                streams.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
             if i in self.out_indices:
                 outs.append(x)
         return outs

@@ -12,7 +12,7 @@ from torch.nn.modules.batchnorm import _BatchNorm
 from ...core.bricks import (DynamicBatchNorm2d, DynamicBottleneck, DynamicConv2d,
                             build_conv_layer, build_norm_layer, constant_init, conv_bn_act, kaiming_init)
 from ...core.dynamic import DynamicMixin, freeze, unzip_meta
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import tape_function
 from ..builder import BACKBONES
 from ..utils import DynamicResLayer
@@ -191,7 +191,7 @@ class DynamicResNet(nn.Module, DynamicMixin):
             if i == 0:
                 # backward crosses this point last-but-one: parameters of every later layer can be
                 # updated while the side stream finishes the stem / stage-1 weight gradients
-                ops.side_checkpoint(tape)
+                streams.side_checkpoint(tape)
             if i in self.out_indices:
                 outs.append(x)
         return outs

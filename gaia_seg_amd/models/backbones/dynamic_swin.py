@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from ...core.bricks import DynamicConv2d, DynamicLayerNorm, DynamicLinear, GELU
 from ...core.dynamic import DynamicMixin, unzip_meta
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import Act, tape_function
 from ..builder import BACKBONES
 
@@ -357,7 +357,7 @@ class DynamicSwinTransformer(nn.Module, DynamicMixin):
         for i, stage in enumerate(self.stages):
             x = stage.forward_blocks(tape, x)
             if i == 0:
-                ops.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
+                streams.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
             if i in self.out_indices:
                 outs.append(self.hidden_states_norms["stage%d" % (i + 1)].forward_act(tape, x))
             if stage.downsample is not None:

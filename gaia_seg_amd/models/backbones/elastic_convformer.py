@@ -46,7 +46,7 @@ from torch.nn.modules.batchnorm import _BatchNorm
 from ...core.bricks import (DynamicConv2d, DynamicLinear, build_activation_layer, build_conv_layer,
                             build_norm_layer, conv_bn_act)
 from ...core.dynamic import DynamicMixin, freeze
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import tape_function
 from ..builder import BACKBONES
 from .elastic_transformer import ElasticFFN, ElasticMHA, _leaf, _nest, _refuse_positive, ffn_width
@@ -528,7 +528,7 @@ class ElasticConvformer(nn.Module, DynamicMixin):
         for i, name in enumerate(self.layers):
             x, x_t = getattr(self, name).forward_act(tape, x, x_t, self.cls_token)
             if i == 0:
-                ops.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
+                streams.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
             outs.append(x)
         return outs
 

@@ -33,7 +33,7 @@ import torch.nn as nn
 from ...core.bricks import (DynamicLinear, build_activation_layer, build_conv_layer, build_norm_layer,
                             kaiming_init)
 from ...core.dynamic import DynamicMixin
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import Act, tape_function
 from ..builder import BACKBONES
 
@@ -402,7 +402,7 @@ class ElasticTransformer(nn.Module, DynamicMixin):
         for i, name in enumerate(self.layers):
             x = getattr(self, name).forward_act(tape, x, self.out_indices[i])
             if i == 0:
-                ops.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
+                streams.side_checkpoint(tape)   # as the other backbones: later layers' gradients are ready first
             if i in self.out_stages:
                 outputs.extend(x if isinstance(x, list) else [x])
             if isinstance(x, list):

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from ...hip import lib as _lib
 from ...hip.runtime import WORKSPACE, current_stream_ptr, require_gpu_tensor, round_up
+from ...hip.streams import adopt_current_stream
 from ..builder import LOSSES
 
 
@@ -73,12 +74,8 @@ class _FusedResizeCE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, grad_acc):
-        from ...hip import ops as _ops
-        prev_slot = _ops.adopt_current_stream()   # (the auxiliary head's loss runs on the branch stream)
-        try:
+        with adopt_current_stream():   # (the auxiliary head's loss runs on the branch stream)
             return _FusedResizeCE._backward(ctx, grad_loss)
-        finally:
-            _ops.restore_stream_slot(prev_slot)
 
     @staticmethod
     def _backward(ctx, grad_loss):

@@ -12,6 +12,7 @@ import torch
 
 from ...hip import lib as _lib
 from ...hip.runtime import WORKSPACE, current_stream_ptr, require_gpu_tensor, round_up
+from ...hip.streams import adopt_current_stream
 
 # the reference's defaults (dynamic_psp_head.py:196-200)
 KD_DEFAULTS = dict(T=2.0, distillation_weight=0.5, interpolation=False)
@@ -57,9 +58,7 @@ class _FusedKD(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        from ...hip import ops as _ops
-        prev_slot = _ops.adopt_current_stream()   # (the auxiliary head's loss runs on the branch stream)
-        try:
+        with adopt_current_stream():   # (the auxiliary head's loss runs on the branch stream)
             student, teacher, lse_s, lse_t = ctx.saved_tensors
             L = _lib.load()
             d = ctx.desc
@@ -73,8 +72,6 @@ class _FusedKD(torch.autograd.Function):
                        "gs_kd_backward")
             buf.mul_(grad_loss)   # the upstream scalar, on the device (no host sync)
             return buf[..., :c].permute(0, 3, 1, 2), None, None, None, None, None, None
-        finally:
-            _ops.restore_stream_slot(prev_slot)
 
 
 def kd_loss(student, teacher, label_hw, T=2.0, distillation_weight=0.5, divisor=1000.0,
@@ -128,9 +125,7 @@ class _TeacherDistill(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        from ...hip import ops as _ops
-        prev_slot = _ops.adopt_current_stream()
-        try:
+        with adopt_current_stream():
             student, teacher, lse_s, lse_t = ctx.saved_tensors
             L = _lib.load()
             d = ctx.desc
@@ -145,8 +140,6 @@ class _TeacherDistill(torch.autograd.Function):
                                              current_stream_ptr()), "gs_distill_backward")
             buf.mul_(grad_loss)   # the upstream scalar, on the device (no host sync)
             return buf[..., :c].permute(0, 3, 1, 2), None, None, None, None, None
-        finally:
-            _ops.restore_stream_slot(prev_slot)
 
 
 def teacher_distill_loss(student, teacher, out_hw, T=1, weight=1, align_corners=False):
@@ -217,9 +210,7 @@ class _Pairwise(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        from ...hip import ops as _ops
-        prev_slot = _ops.adopt_current_stream()
-        try:
+        with adopt_current_stream():
             student, save = ctx.saved_tensors
             L = _lib.load()
             d = ctx.desc
@@ -231,8 +222,6 @@ class _Pairwise(torch.autograd.Function):
                                               current_stream_ptr()), "gs_pairwise_backward")
             buf.mul_(grad_loss)   # the upstream scalar, on the device (no host sync)
             return buf[..., :c].permute(0, 3, 1, 2), None, None, None, None
-        finally:
-            _ops.restore_stream_slot(prev_slot)
 
 
 def pairwise_loss(student_feat, teacher_feat, window, T=1, weight=1):
@@ -287,9 +276,7 @@ class _ChannelDistill(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        from ...hip import ops as _ops
-        prev_slot = _ops.adopt_current_stream()
-        try:
+        with adopt_current_stream():
             student, teacher, lse_s, lse_t = ctx.saved_tensors
             L = _lib.load()
             n, c, h, w = student.shape
@@ -300,8 +287,6 @@ class _ChannelDistill(torch.autograd.Function):
                                          ld, current_stream_ptr()), "gs_cwd_backward")
             buf.mul_(grad_loss)   # the upstream scalar, on the device (no host sync)
             return buf[..., :c].permute(0, 3, 1, 2), None, None, None
-        finally:
-            _ops.restore_stream_slot(prev_slot)
 
 
 def channel_distill_loss(student, teacher, T=1, weight=1):

@@ -17,7 +17,7 @@ and a checkpoint holds the student alone under the keys of a DynamicEncoderDecod
 import numpy as np  # noqa: F401  (the window is drawn from numpy's global state: losses/distill_loss.py)
 import torch
 
-from ...hip import ops
+from ...hip import ops, streams
 from ..builder import SEGMENTORS, build_segmentor
 from ..losses.distill_loss import (channel_distill_loss, draw_pairwise_window, pairwise_loss,
                                    teacher_distill_loss)
@@ -100,7 +100,7 @@ class DynamicDistiller(DynamicEncoderDecoder):
         dev = img.device
         branch = self.with_auxiliary_head and ops.BRANCH_AUX and dev.type == "cuda"
         if branch:   # the auxiliary head(s) beside the decode head, as in EncoderDecoder.forward_train
-            ops.prefork_branch(dev, ops.SLOT_AUX)
+            streams.prefork_branch(dev, streams.SLOT_AUX)
         seg_logits = self.decode_head.forward(x)
         losses = self.decode_head.losses(seg_logits, gt_semantic_seg)
         if distill and self.has_distill_loss:
@@ -119,9 +119,9 @@ class DynamicDistiller(DynamicEncoderDecoder):
                 seg_logits, teacher_logits, T=self.channel_loss_temperature,
                 weight=self.channel_loss_weight)
         if self.with_auxiliary_head:
-            with ops.branch_scope(dev, branch, forked=True):
+            with streams.branch_scope(dev, branch, forked=True):
                 loss_aux = self._auxiliary_head_forward_train(x, img_metas, gt_semantic_seg)
             if branch:
-                ops.join_branch(dev, ops.SLOT_AUX)
+                streams.join_branch(dev, streams.SLOT_AUX)
             losses.update(loss_aux)
         return losses

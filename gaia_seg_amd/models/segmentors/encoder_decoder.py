@@ -13,7 +13,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ...hip import ops
+from ...hip import ops, streams
 from ...hip.runtime import Act, tape_function
 from .. import builder
 
@@ -148,12 +148,12 @@ class EncoderDecoder(nn.Module):
         dev = img.device
         branch = ops.BRANCH_AUX and dev.type == "cuda"
         if branch:
-            ops.prefork_branch(dev, ops.SLOT_AUX)
+            streams.prefork_branch(dev, streams.SLOT_AUX)
         losses.update(self._decode_head_forward_train(x, img_metas, gt_semantic_seg, **kwargs))
-        with ops.branch_scope(dev, branch, forked=True):
+        with streams.branch_scope(dev, branch, forked=True):
             loss_aux = self._auxiliary_head_forward_train(x, img_metas, gt_semantic_seg, **kwargs)
         if branch:
-            ops.join_branch(dev, ops.SLOT_AUX)     # whoever sums the losses reads both
+            streams.join_branch(dev, streams.SLOT_AUX)     # whoever sums the losses reads both
             if kwargs.get("return_logits"):
                 # the auxiliary logits were allocated on the branch stream and are read by later
                 # sandwich members on this one: complete (the join above) and kept alive until then

@@ -263,6 +263,34 @@ def test_layernorm_forward_with_a_large_common_offset(hip_lib, rows, c):
     assert err < TOL
 
 
+def test_layernorm_op_on_a_frozen_channel_slice(hip_lib):
+    """ops.layernorm (the tape op) on the leading 8 channels of a 16-wide buffer that needs no gradient:
+    the kernel still produces dx and addresses it with the input's pitch, so its scratch must have that
+    pitch (ops._grad_target); the parameter gradients against the fp32 formula on the CPU."""
+    from gaia_seg_amd.hip import ops
+    from gaia_seg_amd.hip.runtime import Act, Tape
+    gen = torch.Generator().manual_seed(53)
+    xc, dy = torch.randn(1, 2, 3, 8, generator=gen), torch.randn(1, 2, 3, 8, generator=gen)
+    wc, bc = torch.randn(8, generator=gen), torch.randn(8, generator=gen)
+    buf = padded(xc, 16, SENTINEL)
+    x = Act(buf[..., :8], requires_grad=False)
+    weight, bias = torch.nn.Parameter(wc.to(DEV)), torch.nn.Parameter(bc.to(DEV))
+    tape = Tape()
+    out = ops.layernorm(tape, x, weight, bias, EPS)
+    out.new_grad().copy_(dy.to(DEV))
+    tape.backward()
+    torch.cuda.synchronize()
+    wr, br = wc.clone().requires_grad_(True), bc.clone().requires_grad_(True)
+    y_r = F.layer_norm(xc, (8,), wr, br, EPS)
+    y_r.backward(dy)
+    assert x.g is None
+    assert torch.equal(active(buf, 0, 8, "x"), xc)               # the input buffer is as it was
+    for name, a, r in (("y", out.t, y_r), ("dweight", weight.grad, wr.grad), ("dbias", bias.grad, br.grad)):
+        err = rel_err(a, r)
+        print("ln op on a frozen slice: %s rel_err %.3g" % (name, err))
+        assert err < TOL, name
+
+
 # ---- GELU and layer scale ----------------------------------------------------------------------------
 PW_SHAPES = [(105, 8), (19, 260)]
 
