@@ -9,9 +9,10 @@ DEFER_*: whether an op uses the side stream, a branch stream or a deferred Batch
 themselves, their scratch and the scopes that switch them are ``streams``; ``Act`` and the tape are
 ``runtime``.  Imports go one way: lib <- streams <- runtime <- ops.
 
-Every backward closure gets the buffers its kernel writes from three helpers: ``_grad_target`` (the
-gradient of an input activation), ``_param_grad`` (of a parameter, followed by ``_notify_params``
-after the launch) and ``_qkv_grads`` (the three gradients of an attention op, which share one flag).
+Every backward closure gets the buffers its kernel writes from shared helpers: ``_input_grad`` /
+``_grad_target`` (the gradient of an input activation, and the ONE rule for the accumulate flag),
+``_sole_grad`` (of an input whose kernel has no accumulate form) and ``_param_grad`` (of a parameter,
+followed by ``_notify_params`` after the launch).  ``_qkv_attention`` is the body of the q / k / v ops.
 """
 import ctypes
 import os
@@ -387,9 +388,14 @@ def _active_width(x, param, what):
 
 
 def _input_grad(x):
-    """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it: 1 when
-    x.g already held a contribution, else 0 after allocating it (a channel slice's storage is
-    allocated, zeroed, on the buffer that owns it)."""
+    """Make sure ``x.g`` exists and return the accumulate flag of the kernel that writes it.
+
+    THE RULE, for every tape op: the flag is "the target held something before this call" -- 1 when
+    x.g already existed, else 0 after allocating it.  No op overrides it.  It is right for a channel
+    slice too: the gradient of the buffer that owns the slice is allocated zeroed, and the slices of an
+    activation are disjoint column ranges, so no kernel has written this slice's columns yet and a
+    plain write (which does not read the old gradient) leaves the siblings' zeros alone.  A slice whose
+    sibling already allocated the owner's gradient reports 1 and accumulates onto those zeros."""
     if x.g is not None:
         return 1
     root = x
@@ -402,18 +408,27 @@ def _input_grad(x):
     return 0
 
 
+def _sole_grad(x, sole):
+    """``x.g``, fresh, for a kernel with no accumulate form: this op must be the only consumer of the
+    input that ``sole`` names, so a gradient that is already held raises (before anything is
+    allocated).  Not exact for slices, on the safe side: a sibling slice that allocated the owner's
+    gradient makes it raise as well."""
+    if _input_grad(x):
+        raise RuntimeError("%s has more than one consumer; unsupported" % sole)
+    return x.g
+
+
 def _grad_target(x, sole=None):
     """Where a kernel that always produces the gradient of its input ``x`` writes it -> (tensor,
-    accumulate flag).  An input that requires a gradient gets ``x.g`` (``_input_grad``); ``sole``
-    names an input whose kernel has no accumulate form, so this op must be its only consumer: a
-    gradient that is already held raises.  An input that needs none gets scratch with x's own
-    shape AND pitch (flag 0): a kernel that addresses the gradient with the descriptor's ``ldx`` may
-    rely on that, every other caller passes the ``stride(2)`` of what it got."""
+    accumulate flag).  An input that requires a gradient gets ``x.g`` with the flag of
+    ``_input_grad``, or with ``sole`` given the fresh one of ``_sole_grad``.  An input that needs none
+    gets scratch with x's own shape AND pitch (flag 0): a kernel that addresses the gradient with the
+    descriptor's ``ldx`` may rely on that, every other caller passes the ``stride(2)`` of what it got."""
     if not x.requires_grad:
         return Act.empty(x.N, x.H, x.W, x.C, x.t.device, ld=x.ld).t, 0
+    if sole:
+        return _sole_grad(x, sole), 0
     acc = _input_grad(x)
-    if acc and sole:
-        raise RuntimeError("%s has more than one consumer; unsupported" % sole)
     return x.g, acc
 
 
@@ -480,10 +495,9 @@ def gelu(tape, x, out=None):
         dy = out.g
         if dy is None or not x.requires_grad:
             return
-        if _input_grad(x):
-            raise RuntimeError("GELU input has more than one consumer; unsupported")
-        _lib.check(L.gs_gelu_backward(x.ptr, dy.data_ptr(), x.g.data_ptr(), x.rows, x.C, x.ld, dy.stride(2),
-                                      x.g.stride(2), current_stream_ptr()), "gs_gelu_backward")
+        dx = _sole_grad(x, "GELU input")
+        _lib.check(L.gs_gelu_backward(x.ptr, dy.data_ptr(), dx.data_ptr(), x.rows, x.C, x.ld, dy.stride(2),
+                                      dx.stride(2), current_stream_ptr()), "gs_gelu_backward")
 
     tape.record(backward)
     return out
@@ -561,12 +575,11 @@ def layer_scale_add(tape, identity, z, gamma, out=None):
                 _lib.check(L.gs_copy2d(dout.data_ptr(), dout.stride(2), z.g.data_ptr(), z.g.stride(2), rows, c,
                                        1.0, acc, s), "gs_copy2d")
         else:
-            if _input_grad(z):
-                raise RuntimeError("layer-scaled branch has more than one consumer; unsupported")
+            dz = _sole_grad(z, "layer-scaled branch")
             gg = _param_grad(gamma)
             ws = _ws.get(L.gs_layer_scale_workspace_bytes(rows, c), dev)
-            _lib.check(L.gs_layer_scale_backward(dout.data_ptr(), z.ptr, gamma.data_ptr(), z.g.data_ptr(),
-                                                 gg.data_ptr(), rows, c, dout.stride(2), z.ld, z.g.stride(2),
+            _lib.check(L.gs_layer_scale_backward(dout.data_ptr(), z.ptr, gamma.data_ptr(), dz.data_ptr(),
+                                                 gg.data_ptr(), rows, c, dout.stride(2), z.ld, dz.stride(2),
                                                  ws.data_ptr(), ws.numel(), s), "gs_layer_scale_backward")
             _notify_params(gamma)
         if identity.requires_grad:
@@ -602,25 +615,44 @@ def _attention_setup(tape, what, q, k, v, heads, scale, out, f16):
     return q, k, v, out, lse, d, sfx
 
 
-def _qkv_grads(q, k, v):
-    """First half of the q / k / v gradient set-up that ``attention``, ``attention_kv`` and
-    ``window_attention`` share: the three gradients exist afterwards -> (held, accs) with ``held`` =
-    some gradient held a contribution before this call and ``accs`` = the ``_input_grad`` flag of each.
-    The two differ exactly when the three are column slices of one buffer that had no gradient yet:
-    allocating q's zeroes the parent, so k and v then report a (zero) gradient.  The backward kernels
-    take ONE accumulate flag for the three; each op derives it from this pair in its own way."""
-    held = any(t.g is not None for t in (q, k, v))
-    return held, [_input_grad(t) for t in (q, k, v)]
+def _qkv_attention(tape, stem, sfx, d, q, k, v, out, lse, table=None):
+    """The body ``attention``, ``attention_kv`` and ``window_attention`` share once the op has checked its
+    shapes and filled its descriptor ``d``: the call of <stem>_forward<sfx> and the recorded backward
+    (<stem>_backward<sfx> with a pooled workspace of <stem>_workspace_bytes<sfx>).  The backward kernels take
+    ONE accumulate flag for the three gradients: some gradient of q, k, v was held before this call (the
+    rule of ``_input_grad``); with it set, those that start fresh are zeroed.  q, k and v are distinct
+    activations or disjoint slices.  ``table``: window_attention's bias table, passed after v; its
+    gradient goes after dv, its active columns start from zero under the flag, and it is notified."""
+    L = _L()
+    fwd, bwd, ws_bytes = (getattr(L, "%s_%s%s" % (stem, e, sfx)) for e in ("forward", "backward", "workspace_bytes"))
+    dev = q.t.device
+    inputs = (q, k, v) if table is None else (q, k, v, table)
+    _lib.check(fwd(ctypes.byref(d), q.ptr, k.ptr, v.ptr, *(t.data_ptr() for t in inputs[3:]), out.ptr,
+                   lse.data_ptr(), current_stream_ptr()), "%s_forward%s" % (stem, sfx))
 
-
-def _qkv_start(d, q, k, v, dy, accs, acc):
-    """Second half, under the accumulate flag ``acc`` the op passes: with it set, the gradients that
-    start fresh are zeroed; the descriptor gets its four gradient pitches."""
-    if acc:
-        for t, a in zip((q, k, v), accs):
-            if not a:
+    def backward():
+        dy = out.g
+        if dy is None or not any(t.requires_grad for t in inputs):
+            return
+        acc = 1 if any(t.g is not None for t in (q, k, v)) else 0
+        for t in (q, k, v):
+            if not _input_grad(t) and acc:
                 t.g.zero_()
-    d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        d.lddq, d.lddk, d.lddv, d.lddo = q.g.stride(2), k.g.stride(2), v.g.stride(2), dy.stride(2)
+        grads = [q.g, k.g, v.g]
+        if table is not None:
+            grads.append(_param_grad(table))
+            if acc:   # the flag covers the table too: its active columns start from zero
+                grads[3][:, :d.heads].zero_()
+        db = ctypes.byref(d)
+        ws = _ws.get(ws_bytes(db), dev)
+        _lib.check(bwd(db, q.ptr, k.ptr, v.ptr, *(t.data_ptr() for t in inputs[3:]), out.ptr, lse.data_ptr(),
+                       dy.data_ptr(), *(g.data_ptr() for g in grads), acc, ws.data_ptr(), ws.numel(),
+                       current_stream_ptr()), "%s_backward%s" % (stem, sfx))
+        _notify_params(table)
+
+    tape.record(backward)
+    return out
 
 
 def attention(tape, q, k, v, heads, scale, out=None, f16=False):
@@ -629,32 +661,8 @@ def attention(tape, q, k, v, heads, scale, out=None, f16=False):
     column slices of one buffer are fine).  No N x N matrix is stored; the log-sum-exp of every query row is
     kept for the backward, which recomputes the probabilities.  ``f16`` (opt-in, honoured only in an fp16
     mode): fp16 MFMA operands with fp32 accumulation, forward and backward."""
-    L = _L()
     q, k, v, out, lse, d, sfx = _attention_setup(tape, "attention", q, k, v, heads, scale, out, f16)
-    fwd, bwd = getattr(L, "gs_attention_forward" + sfx), getattr(L, "gs_attention_backward" + sfx)
-    ws_bytes = getattr(L, "gs_attention_workspace_bytes" + sfx)
-    dev = q.t.device
-    _lib.check(fwd(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), current_stream_ptr()),
-               "gs_attention_forward" + sfx)
-
-    def backward():
-        dy = out.g
-        if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad):
-            return
-        _, accs = _qkv_grads(q, k, v)
-        # accumulate as soon as one of the three reports a gradient, slices of a just-zeroed buffer
-        # included (window_attention writes in that case; unifying the two changes what the kernel is
-        # asked to do and is left to a change of its own)
-        acc = 1 if any(accs) else 0
-        _qkv_start(d, q, k, v, dy, accs, acc)
-        db = ctypes.byref(d)
-        ws = _ws.get(ws_bytes(db), dev)
-        _lib.check(bwd(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(), q.g.data_ptr(),
-                       k.g.data_ptr(), v.g.data_ptr(), acc, ws.data_ptr(), ws.numel(),
-                       current_stream_ptr()), "gs_attention_backward" + sfx)
-
-    tape.record(backward)
-    return out
+    return _qkv_attention(tape, "gs_attention", sfx, d, q, k, v, out, lse)
 
 
 def attention_kv(tape, q, k, v, heads, scale, out=None):
@@ -663,7 +671,6 @@ def attention_kv(tape, q, k, v, heads, scale, out=None):
     reduced map; two column slices of one buffer are fine).  fp32 operands in every precision mode (there is
     no fp16-operand form).  No Nq x Nk matrix is stored; the backward's workspace (delta and, where the dK /
     dV kernel splits the queries, the slabs' partials) comes from the pool."""
-    L = _L()
     q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
     c = _lib.ATTENTION_HEAD_DIM * heads
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -675,25 +682,7 @@ def attention_kv(tape, q, k, v, heads, scale, out=None):
         out = Act.empty(b, q.H, q.W, c, dev)
     lse = torch.empty(b * heads * nq, dtype=torch.float32, device=dev)
     d = _lib.attention_kv_desc(b, nq, nk, heads, scale, ldq=q.ld, ldk=k.ld, ldv=v.ld, ldo=out.ld)
-    _lib.check(L.gs_attention_kv_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(),
-                                         current_stream_ptr()), "gs_attention_kv_forward")
-
-    def backward():
-        dy = out.g
-        if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad):
-            return
-        _, accs = _qkv_grads(q, k, v)
-        acc = 1 if any(accs) else 0   # (as ``attention``: slices of a just-zeroed buffer accumulate)
-        _qkv_start(d, q, k, v, dy, accs, acc)
-        db = ctypes.byref(d)
-        ws = _ws.get(L.gs_attention_kv_workspace_bytes(db), dev)
-        _lib.check(L.gs_attention_kv_backward(db, q.ptr, k.ptr, v.ptr, out.ptr, lse.data_ptr(), dy.data_ptr(),
-                                              q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(), acc,
-                                              ws.data_ptr(), ws.numel(), current_stream_ptr()),
-                   "gs_attention_kv_backward")
-
-    tape.record(backward)
-    return out
+    return _qkv_attention(tape, "gs_attention_kv", "", d, q, k, v, out, lse)
 
 
 def window_attention(tape, q, k, v, table, heads, ws, shift, scale, out=None):
@@ -703,7 +692,6 @@ def window_attention(tape, q, k, v, table, heads, ws, shift, scale, out=None):
     and get a gradient (written like every parameter gradient, then notified).  The roll, the window
     partition, the bias gather and the region mask happen inside the kernel; fp32 operands in every precision
     mode.  lse is kept for the backward, whose workspace (the table partials) comes from the pool."""
-    L = _L()
     q, k, v = materialize(tape, q), materialize(tape, k), materialize(tape, v)
     c = _lib.WINDOW_ATTENTION_HEAD_DIM * heads
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -719,31 +707,7 @@ def window_attention(tape, q, k, v, table, heads, ws, shift, scale, out=None):
     lse = torch.empty(b * heads * q.H * q.W, dtype=torch.float32, device=dev)
     d = _lib.window_attention_desc(b, q.H, q.W, ws, shift, heads, ld_table=table.stride(0), scale=scale, ldq=q.ld,
                                    ldk=k.ld, ldv=v.ld, ldo=out.ld)
-    _lib.check(L.gs_window_attention_forward(ctypes.byref(d), q.ptr, k.ptr, v.ptr, table.data_ptr(), out.ptr,
-                                             lse.data_ptr(), current_stream_ptr()), "gs_window_attention_forward")
-
-    def backward():
-        dy = out.g
-        if dy is None or not (q.requires_grad or k.requires_grad or v.requires_grad or table.requires_grad):
-            return
-        held, accs = _qkv_grads(q, k, v)
-        # accumulate only where a gradient was held BEFORE this call: with nothing held every output is
-        # written (=), also into slices of a just-zeroed buffer (``attention`` accumulates there)
-        acc = 1 if held else 0
-        _qkv_start(d, q, k, v, dy, accs, acc)
-        gt = _param_grad(table)
-        if acc:   # the flag covers the table too: its active columns start from zero
-            gt[:, :heads].zero_()
-        db = ctypes.byref(d)
-        ws_buf = _ws.get(L.gs_window_attention_workspace_bytes(db), dev)
-        _lib.check(L.gs_window_attention_backward(db, q.ptr, k.ptr, v.ptr, table.data_ptr(), out.ptr, lse.data_ptr(),
-                                                  dy.data_ptr(), q.g.data_ptr(), k.g.data_ptr(), v.g.data_ptr(),
-                                                  gt.data_ptr(), acc, ws_buf.data_ptr(), ws_buf.numel(),
-                                                  current_stream_ptr()), "gs_window_attention_backward")
-        _notify_params(table)
-
-    tape.record(backward)
-    return out
+    return _qkv_attention(tape, "gs_window_attention", "", d, q, k, v, out, lse, table)
 
 
 def map_pad(tape, x, hp, wp, out=None):
@@ -761,8 +725,6 @@ def map_pad(tape, x, hp, wp, out=None):
         if dy is None or not x.requires_grad:
             return
         acc = _input_grad(x)
-        if not acc and x.parent is not None:
-            acc = 1   # a slice of a zeroed buffer
         _lib.check(L.gs_map_crop(dy.data_ptr(), dy.stride(2), x.g.data_ptr(), x.g.stride(2), b, h, w, hp, wp, c, acc,
                                  current_stream_ptr()), "gs_map_crop")
 
@@ -785,7 +747,7 @@ def map_crop(tape, x, h, w, out=None):
         dy = out.g
         if dy is None or not x.requires_grad:
             return
-        acc = 1 if (_input_grad(x) or x.parent is not None) else 0
+        acc = _input_grad(x)
         _lib.check(L.gs_map_pad(dy.data_ptr(), dy.stride(2), x.g.data_ptr(), x.g.stride(2), b, h, w, hp, wp, c, acc,
                                 current_stream_ptr()), "gs_map_pad")
 
@@ -1150,11 +1112,11 @@ def ocr_attend(tape, q, k, v):
 def _pass_residual_grad(L, residual, src, rows, C, stream):
     """Hand the gradient ``src`` of an identity edge to ``residual``: aliased as residual.g when it
     is the first contribution and the layouts match, else copied (added where residual.g holds a
-    contribution or is a slice of a zeroed buffer)."""
+    contribution)."""
     if residual.g is None and residual.parent is None and src.stride() == residual.t.stride():
         residual.g = src
         return
-    acc = 1 if (_input_grad(residual) or residual.parent is not None) else 0
+    acc = _input_grad(residual)
     _lib.check(L.gs_copy2d(src.data_ptr(), src.stride(2), residual.g.data_ptr(),
                            residual.g.stride(2), rows, C, 1.0, acc, stream), "gs_copy2d")
 
@@ -1310,13 +1272,11 @@ def batchnorm(tape, x, bn, relu=False, residual=None, out=None, inplace=False):
                 gb[:C].copy_(bsums[:C])
             dist.all_reduce(bsums, group=bn.process_group)
         mask_apply = 0 if want_g else mask  # dy already masked in place
-        if x.g is not None:
-            raise RuntimeError("BN input has more than one consumer; unsupported")
-        _input_grad(x)
+        dx = _sole_grad(x, "BN input")
         _lib.check(L.gs_bn_bwd_apply(dy.data_ptr(), dy.stride(2), x.ptr, x.ld, out.ptr, out.ld,
                                      rows, C, coeffs_ptr, bsums.data_ptr(), bcount,
-                                     mask_apply, 1 if use_batch else 0, x.g.data_ptr(),
-                                     x.g.stride(2), gw.data_ptr() if (wgrad and not synced) else None,
+                                     mask_apply, 1 if use_batch else 0, dx.data_ptr(),
+                                     dx.stride(2), gw.data_ptr() if (wgrad and not synced) else None,
                                      gb.data_ptr() if (bgrad and not synced) else None, s),
                    "gs_bn_bwd_apply")
         _notify_params(bn.weight, bn.bias)
@@ -1702,12 +1662,9 @@ def dropout2d(tape, x, p, training, generator=None):
         dy = out.g
         if dy is None or not x.requires_grad:
             return
-        if x.g is not None:
-            raise RuntimeError("dropout input has more than one consumer; unsupported")
-        _input_grad(x)
+        dx = _sole_grad(x, "dropout input")
         _lib.check(L.gs_scale_nc(dy.data_ptr(), dy.stride(2), mask.data_ptr(), x.N, ppi, x.C,
-                                 x.g.data_ptr(), x.g.stride(2), current_stream_ptr()),
-                   "gs_scale_nc")
+                                 dx.data_ptr(), dx.stride(2), current_stream_ptr()), "gs_scale_nc")
 
     tape.record(backward)
     return out

@@ -16,7 +16,8 @@ ROOT = os.path.dirname(HERE)
 FIXTURE = os.path.join(HERE, "golden", "ref_convformer_ctors.json")
 CONFIG = os.path.join(ROOT, "configs", "supernet", "upernet_elastic_convformer_adamw.py")
 OK, BADARG, ALIGN, WORKSPACE, NULL = 0, -1, -2, -3, -4
-P = 4096    # a non-null, 16-byte aligned address; no call below gets as far as using it
+P = 4096    # a non-null, 16-byte aligned address; every call below that gets it is asserted to be refused, and the
+            # library refuses before it launches
 
 
 def build(**kw):

@@ -10,7 +10,8 @@ from gaia_seg_amd.hip import lib
 import util_convnext as U
 
 GS_E_BADARG, GS_E_ALIGN, GS_E_WORKSPACE, GS_E_NULL = -1, -2, -3, -4
-P = 0x10000          # a 16-byte aligned, non-null address: never dereferenced, no launch happens
+P = 0x10000          # a 16-byte aligned, non-null address.  It is never dereferenced because every call that gets it is
+                     # asserted to return a refusal code, and the library refuses before it launches
 CONFIG = lib.REPO_ROOT + "/configs/supernet/upernet_convnext_t2b.py"
 
 
@@ -165,13 +166,18 @@ def test_dwconv7_workspace_query(hip_lib):
     assert q(ctypes.byref(lib.dwconv_desc(2, 13, 17, 8, pad=1))) == 2 * 9 * 8 * 4
 
 
-def ln_calls(L, d, x=P, w=P, b=P, y=P, mean=P, rstd=P, dx=P, dw=P, db=P, ws=P, ws_bytes=1 << 30):
-    r = ctypes.byref(d) if d is not None else None
-    return (L.gs_layernorm_forward(r, x, w, b, y, mean, rstd, None),
-            L.gs_layernorm_backward(r, x, y, w, mean, rstd, dx, dw, db, 0, ws, ws_bytes, None))
+def ln_fwd(L, d, x=P, w=P, b=P, y=P, mean=P, rstd=P):
+    return L.gs_layernorm_forward(ctypes.byref(d) if d is not None else None, x, w, b, y, mean, rstd, None)
+
+
+def ln_bwd(L, d, x=P, y=P, w=P, mean=P, rstd=P, dx=P, dw=P, db=P, ws=P, ws_bytes=1 << 30):
+    return L.gs_layernorm_backward(ctypes.byref(d) if d is not None else None, x, y, w, mean, rstd, dx, dw, db,
+                                   0, ws, ws_bytes, None)
 
 
 def test_layernorm_argument_checks(hip_lib):
+    # (one entry per call, each with exactly one thing wrong and its refusal asserted: a call with nothing
+    # wrong would launch on P)
     q = hip_lib.gs_layernorm_workspace_bytes
     for change, code in [(dict(C=6), GS_E_ALIGN), (dict(ldx=10), GS_E_ALIGN), (dict(ldy=14), GS_E_ALIGN),
                          (dict(rows=0), GS_E_BADARG), (dict(C=0), GS_E_BADARG), (dict(ldx=4), GS_E_BADARG),
@@ -179,23 +185,23 @@ def test_layernorm_argument_checks(hip_lib):
         d = lib.layernorm_desc(105, 8, 1e-6, ldx=16, ldy=12)
         for k, v in change.items():
             setattr(d, k, v)
-        assert ln_calls(hip_lib, d) == (code, code), change
+        assert (ln_fwd(hip_lib, d), ln_bwd(hip_lib, d)) == (code, code), change
         assert q(ctypes.byref(d)) == 0
     d = lib.layernorm_desc(105, 8, 1e-6, ldx=16, ldy=12)
-    assert ln_calls(hip_lib, None) == (GS_E_NULL, GS_E_NULL) and q(None) == 0
+    assert (ln_fwd(hip_lib, None), ln_bwd(hip_lib, None)) == (GS_E_NULL, GS_E_NULL) and q(None) == 0
     for name in ("x", "w", "y", "mean", "rstd"):
-        assert ln_calls(hip_lib, d, **{name: None}) == (GS_E_NULL, GS_E_NULL), name
-    assert ln_calls(hip_lib, d, b=None)[0] == GS_E_NULL
+        assert (ln_fwd(hip_lib, d, **{name: None}), ln_bwd(hip_lib, d, **{name: None})) == (GS_E_NULL, GS_E_NULL), name
+    assert ln_fwd(hip_lib, d, b=None) == GS_E_NULL
     for name in ("dx", "dw", "db", "ws"):
-        assert ln_calls(hip_lib, d, **{name: None})[1] == GS_E_NULL, name
+        assert ln_bwd(hip_lib, d, **{name: None}) == GS_E_NULL, name
     for name in ("x", "w", "y"):
-        assert ln_calls(hip_lib, d, **{name: P + 4}) == (GS_E_ALIGN, GS_E_ALIGN), name
-    assert ln_calls(hip_lib, d, b=P + 8)[0] == GS_E_ALIGN
+        assert (ln_fwd(hip_lib, d, **{name: P + 4}), ln_bwd(hip_lib, d, **{name: P + 4})) == (GS_E_ALIGN, GS_E_ALIGN), name
+    assert ln_fwd(hip_lib, d, b=P + 8) == GS_E_ALIGN
     for name in ("dx", "dw", "db", "ws"):
-        assert ln_calls(hip_lib, d, **{name: P + 4})[1] == GS_E_ALIGN, name
+        assert ln_bwd(hip_lib, d, **{name: P + 4}) == GS_E_ALIGN, name
     need = q(ctypes.byref(d))
     assert need == 2 * 8 * 4                                  # one run of up to 256 rows, [2][C]
-    assert ln_calls(hip_lib, d, ws_bytes=need - 1)[1] == GS_E_WORKSPACE
+    assert ln_bwd(hip_lib, d, ws_bytes=need - 1) == GS_E_WORKSPACE
     big = lib.layernorm_desc(257, 1024, 1e-6)
     assert q(ctypes.byref(big)) == 2 * 2 * 1024 * 4
 

@@ -13,7 +13,8 @@ from gaia_seg_amd.hip import lib
 import util_convnextv2 as U
 
 GS_E_BADARG, GS_E_ALIGN, GS_E_WORKSPACE, GS_E_NULL = -1, -2, -3, -4
-P = 0x10000          # a 16-byte aligned, non-null address: never dereferenced, no launch happens
+P = 0x10000          # a 16-byte aligned, non-null address.  It is never dereferenced because every call that gets it is
+                     # asserted to return a refusal code, and the library refuses before it launches
 CONFIG = lib.REPO_ROOT + "/configs/supernet/upernet_convnextv2_n2b_adamw.py"
 
 
@@ -206,10 +207,19 @@ def test_binding_and_header(hip_lib):
     assert "gs_gelu_grn_desc" in header
 
 
-def grn_calls(L, d, x=P, w=P, b=P, y=P, G=P, dx=P, dw=P, db=P, ws=P, ws_bytes=1 << 30):
-    r = ctypes.byref(d) if d is not None else None
-    return (L.gs_gelu_grn_forward(r, x, w, b, y, G, ws, ws_bytes, None),
-            L.gs_gelu_grn_backward(r, x, y, w, G, dx, dw, db, ws, ws_bytes, None))
+def grn_fwd(L, d, x=P, w=P, b=P, y=P, G=P, ws=P, ws_bytes=1 << 30):
+    return L.gs_gelu_grn_forward(ctypes.byref(d) if d is not None else None, x, w, b, y, G, ws, ws_bytes, None)
+
+
+def grn_bwd(L, d, x=P, y=P, w=P, G=P, dx=P, dw=P, db=P, ws=P, ws_bytes=1 << 30):
+    return L.gs_gelu_grn_backward(ctypes.byref(d) if d is not None else None, x, y, w, G, dx, dw, db, ws, ws_bytes,
+                                  None)
+
+
+def grn_calls(L, d, **kw):
+    """Both entries under a fault that both see (an argument of one entry alone goes to grn_fwd / grn_bwd: the
+    other entry, with nothing wrong, would launch on P)."""
+    return grn_fwd(L, d, **kw), grn_bwd(L, d, **kw)
 
 
 def test_gelu_grn_argument_checks(hip_lib):
@@ -231,10 +241,10 @@ def test_gelu_grn_argument_checks(hip_lib):
     for name in ("x", "w", "y", "G", "ws"):
         assert grn_calls(hip_lib, d, **{name: None}) == (GS_E_NULL, GS_E_NULL), name
         assert grn_calls(hip_lib, d, **{name: P + 4}) == (GS_E_ALIGN, GS_E_ALIGN), name
-    assert grn_calls(hip_lib, d, b=None)[0] == GS_E_NULL and grn_calls(hip_lib, d, b=P + 8)[0] == GS_E_ALIGN
+    assert grn_fwd(hip_lib, d, b=None) == GS_E_NULL and grn_fwd(hip_lib, d, b=P + 8) == GS_E_ALIGN
     for name in ("dx", "dw", "db"):
-        assert grn_calls(hip_lib, d, **{name: None})[1] == GS_E_NULL, name
-        assert grn_calls(hip_lib, d, **{name: P + 4})[1] == GS_E_ALIGN, name
+        assert grn_bwd(hip_lib, d, **{name: None}) == GS_E_NULL, name
+        assert grn_bwd(hip_lib, d, **{name: P + 4}) == GS_E_ALIGN, name
     need = q(ctypes.byref(d))
     assert need == 3 * 8 * (2 * 1 + 4) * 4                       # one run per sample: [2][C], and [4][C] per sample
     assert grn_calls(hip_lib, d, ws_bytes=need - 1) == (GS_E_WORKSPACE, GS_E_WORKSPACE)

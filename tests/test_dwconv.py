@@ -9,15 +9,29 @@ import torch
 from gaia_seg_amd.hip import lib
 
 GS_E_BADARG, GS_E_ALIGN, GS_E_WORKSPACE, GS_E_NULL = -1, -2, -3, -4
-P = 0x10000          # a 16-byte aligned, non-null address: never dereferenced, no launch happens
+P = 0x10000          # a 16-byte aligned, non-null address.  It is never dereferenced because every call that gets it is
+                     # asserted to return a refusal code, and the library refuses before it launches
 
 
-def calls(L, d, x=P, w=P, y=P, dx=P, dw=P, ws=P, ws_bytes=1 << 30):
-    """the return codes of forward, dgrad and wgrad for one descriptor and set of pointers"""
-    db = ctypes.byref(d) if d is not None else None
-    return (L.gs_dwconv2d_forward(db, x, w, None, y, None),
-            L.gs_dwconv2d_dgrad(db, y, w, dx, 0, None),
-            L.gs_dwconv2d_wgrad(db, x, y, dw, ws, ws_bytes, None))
+def _ref(d):
+    return ctypes.byref(d) if d is not None else None
+
+
+def fwd(L, d, x=P, w=P, y=P):
+    return L.gs_dwconv2d_forward(_ref(d), x, w, None, y, None)
+
+
+def dgrad(L, d, y=P, w=P, dx=P):
+    return L.gs_dwconv2d_dgrad(_ref(d), y, w, dx, 0, None)
+
+
+def wgrad(L, d, x=P, y=P, dw=P, ws=P, ws_bytes=1 << 30):
+    return L.gs_dwconv2d_wgrad(_ref(d), x, y, dw, ws, ws_bytes, None)
+
+
+def calls(L, d, **kw):
+    """the return codes of forward, dgrad and wgrad under a fault all three see (the descriptor, or y)"""
+    return fwd(L, d, **kw), dgrad(L, d, **kw), wgrad(L, d, **kw)
 
 
 def test_binding_and_header(hip_lib):
@@ -47,23 +61,24 @@ def test_bad_descriptors_are_refused_before_any_launch(hip_lib, change, code):
 
 
 def test_null_and_misaligned_pointers(hip_lib):
-    d = lib.dwconv_desc(2, 9, 11, 8, pad=1)
-    assert calls(hip_lib, None) == (GS_E_NULL,) * 3
-    assert calls(hip_lib, d, x=None)[0::2] == (GS_E_NULL, GS_E_NULL)
-    assert calls(hip_lib, d, w=None)[:2] == (GS_E_NULL, GS_E_NULL)
-    assert calls(hip_lib, d, y=None) == (GS_E_NULL,) * 3
-    assert calls(hip_lib, d, dx=None)[1] == GS_E_NULL
-    assert calls(hip_lib, d, dw=None)[2] == GS_E_NULL
-    assert calls(hip_lib, d, ws=None)[2] == GS_E_NULL
-    assert calls(hip_lib, d, x=P + 4)[0::2] == (GS_E_ALIGN, GS_E_ALIGN)
-    assert calls(hip_lib, d, w=P + 8)[:2] == (GS_E_ALIGN, GS_E_ALIGN)
-    assert calls(hip_lib, d, y=P + 4) == (GS_E_ALIGN,) * 3
-    assert calls(hip_lib, d, dx=P + 12)[1] == GS_E_ALIGN
-    assert calls(hip_lib, d, dw=P + 4)[2] == GS_E_ALIGN
-    assert calls(hip_lib, d, ws=P + 4)[2] == GS_E_ALIGN
-    assert hip_lib.gs_dwconv2d_forward(ctypes.byref(d), P, P, P + 4, P, None) == GS_E_ALIGN   # bias
-    need = hip_lib.gs_dwconv2d_workspace_bytes(ctypes.byref(d))
-    assert need > 0 and calls(hip_lib, d, ws_bytes=need - 1)[2] == GS_E_WORKSPACE
+    # (an argument goes only to the entries that take it: an entry with nothing wrong would launch on P)
+    L, d = hip_lib, lib.dwconv_desc(2, 9, 11, 8, pad=1)
+    assert calls(L, None) == (GS_E_NULL,) * 3
+    assert (fwd(L, d, x=None), wgrad(L, d, x=None)) == (GS_E_NULL, GS_E_NULL)
+    assert (fwd(L, d, w=None), dgrad(L, d, w=None)) == (GS_E_NULL, GS_E_NULL)
+    assert calls(L, d, y=None) == (GS_E_NULL,) * 3
+    assert dgrad(L, d, dx=None) == GS_E_NULL
+    assert wgrad(L, d, dw=None) == GS_E_NULL
+    assert wgrad(L, d, ws=None) == GS_E_NULL
+    assert (fwd(L, d, x=P + 4), wgrad(L, d, x=P + 4)) == (GS_E_ALIGN, GS_E_ALIGN)
+    assert (fwd(L, d, w=P + 8), dgrad(L, d, w=P + 8)) == (GS_E_ALIGN, GS_E_ALIGN)
+    assert calls(L, d, y=P + 4) == (GS_E_ALIGN,) * 3
+    assert dgrad(L, d, dx=P + 12) == GS_E_ALIGN
+    assert wgrad(L, d, dw=P + 4) == GS_E_ALIGN
+    assert wgrad(L, d, ws=P + 4) == GS_E_ALIGN
+    assert L.gs_dwconv2d_forward(ctypes.byref(d), P, P, P + 4, P, None) == GS_E_ALIGN   # bias
+    need = L.gs_dwconv2d_workspace_bytes(ctypes.byref(d))
+    assert need > 0 and wgrad(L, d, ws_bytes=need - 1) == GS_E_WORKSPACE
 
 
 def test_workspace_query_is_monotone_in_the_pixel_count(hip_lib):

@@ -13,7 +13,8 @@ import util_ocr as U
 from util_models import arch_meta
 
 GS_E_BADARG, GS_E_ALIGN, GS_E_WORKSPACE, GS_E_NULL = -1, -2, -3, -4
-P = 0x10000          # a 16-byte aligned, non-null address: never dereferenced, no launch happens
+P = 0x10000          # a 16-byte aligned, non-null address.  It is never dereferenced because every call that gets it is
+                     # asserted to return a refusal code, and the library refuses before it launches
 CONFIG = lib.REPO_ROOT + "/configs/supernet/ocrnet_ar50to101_v1c_os8.py"
 
 OCR_HEAD_KEYS = [
@@ -273,7 +274,8 @@ def test_null_pointers_alignment_and_short_workspaces(hip_lib):
     assert gather_calls(L, g, ws_bytes=need_g - 1) == (GS_E_WORKSPACE, GS_E_WORKSPACE)
     need_a = L.gs_ocr_attend_workspace_bytes(ctypes.byref(a))
     assert need_a == 4 * (2 * 2 * 221 * 20 + 2 * 2 * 19 * 8)
-    assert attend_calls(L, a, ws_bytes=need_a - 1)[1] == GS_E_WORKSPACE
+    # (the backward alone: the forward takes no workspace and, with nothing wrong, would launch on P)
+    assert L.gs_ocr_attend_backward(ctypes.byref(a), P, P, P, P, P, P, P, P, P, P, need_a - 1, None) == GS_E_WORKSPACE
     # the queries need no device and grow with the pixels
     big = lib.ocr_gather_desc(2, 64 * 128, 19, 512)
     assert L.gs_ocr_gather_workspace_bytes(ctypes.byref(big)) > need_g

@@ -4,9 +4,11 @@ tests/golden/tape_call_trace.json holds, for every case of tools/dump_tape_call_
 input size), what tests/host_dry_run.py --trace reports for two consecutive train steps with every
 library entry stubbed: the number of calls, the calls per entry and the SHA-256 of the canonical call
 lines (entry, every scalar argument, null-ness of every pointer, every descriptor field by field).
-It was dumped from the commit BEFORE the stream state moved from hip/ops.py to hip/streams.py and the
-ops' gradient set-up was folded into shared helpers; the Python layer must reproduce it call for
-call.  A change of what an op passes to a kernel has to regenerate the file, in the open.
+It was dumped from the tree that gave the tape ops one accumulate rule (ops._input_grad); the Python
+layer must reproduce it call for call.  (The dump before it came from the commit BEFORE the stream state
+moved from hip/ops.py to hip/streams.py; the rule changed no call count, and of the arguments only the
+accumulate flag of the attention backwards of three cases, 1 -> 0.)  A change of what an op passes to a
+kernel has to regenerate the file, in the open.
 
 What the stubbed run cannot see:
   * stream order (every stream handle is 0 under the stub);

@@ -4,8 +4,11 @@ For every case below, tests/host_dry_run.py --trace steps the config's model twi
 with every library entry stubbed, and reports the number of calls, the calls per entry and the
 SHA-256 of the canonical call lines (arguments, null-ness of every pointer, every descriptor field).
 tests/test_tape_call_trace.py runs the same cases and compares.  The golden file was dumped from the
-commit BEFORE the stream state moved out of hip/ops.py (tests/host_dry_run.py of this tree copied
-into a checkout of that commit):
+tree that gave the tape ops one accumulate rule (ops._input_grad).  Against the dump before it, taken
+from the commit BEFORE the stream state moved out of hip/ops.py, the calls and the calls per entry are the
+same for every case; the digests of the ViT, Convformer and SegFormer cases differ, in the accumulate flag
+of gs_attention_backward / gs_attention_kv_backward alone (1 -> 0, profiles/r27_accumulate_rule.md).
+--root dumps from another checkout (with tests/host_dry_run.py of this tree copied into it):
 
     python tools/dump_tape_call_trace.py [--root CHECKOUT] > tests/golden/tape_call_trace.json
 
