@@ -265,6 +265,69 @@ class DynamicLinear(DynamicConv2d):
         return _nhwc_tape_call(self.forward_act, x)
 
 
+class DynamicDepthwiseConv2d(nn.Module, DynamicMixin):
+    """The parameters of one depthwise filter of any shape, e.g. SegNeXt's 5x5, 1xK and Kx1 filters:
+    ``F.conv2d(x, W[:x.size(1)], b[:x.size(1)], padding=padding, groups=x.size(1))``.
+
+    It holds the weight (state dict [C, 1, KH, KW]; stored channel-contiguous [KH][KW][1][C_ld], as the
+    depthwise form of DynConv2d) and the bias, nothing else: the filters of a spatial gating unit run
+    together in one operator (ops.msca), so this brick has no forward of its own."""
+    search_space = {"width"}
+
+    def __init__(self, channels, kernel_size, padding=0):
+        super().__init__()
+        kh, kw = _pair(kernel_size)
+        self.in_channels = self.out_channels = self.groups = channels
+        self.kernel_size, self.padding = (kh, kw), _pair(padding)
+        co_ld = round_up(channels, 4)
+        self.weight = nn.Parameter(hwio_logical_view(torch.zeros(kh, kw, 1, co_ld), channels))
+        self.bias = nn.Parameter(torch.zeros(co_ld)[:channels])
+        self.init_state(width=channels)
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        relayout_conv_params(self)
+
+    def extra_repr(self):
+        return "%d, kernel_size=%s, padding=%s, width=%s" % (self.out_channels, self.kernel_size,
+                                                            self.padding, self.width_state)
+
+    def manipulate_width(self, width):
+        if not 0 < width <= self.out_channels:
+            raise ValueError("width %s out of range (1..%d)" % (width, self.out_channels))
+        self.width_state = width
+
+    def check_layout(self):
+        if not is_hwio(self.weight) or self.bias.data_ptr() % 16:
+            relayout_conv_params(self)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        relayout_conv_params(self)
+
+    def _apply(self, fn, recurse=True):
+        out = super()._apply(fn, recurse)
+        relayout_conv_params(self)
+        return out
+
+    def forward(self, x):
+        raise NotImplementedError("DynamicDepthwiseConv2d holds parameters only; its filter runs inside "
+                                  "ops.msca")
+
+    def _deploy_slice(self, c):
+        """Physically prune to the first c channels (tools/extract_subnet.py semantics)."""
+        if self.weight.shape[0] == c:
+            return
+        w, b = self.weight.data[:c].clone(), self.bias.data[:c].clone()
+        self.in_channels = self.out_channels = self.groups = self.width_state = c
+        kh, kw = self.kernel_size
+        view = hwio_logical_view(torch.zeros((kh, kw, 1, round_up(c, 4)), dtype=w.dtype, device=w.device), c)
+        view.copy_(w)
+        self.weight = nn.Parameter(view, requires_grad=self.weight.requires_grad)
+        pb = torch.zeros(round_up(c, 4), dtype=b.dtype, device=b.device)
+        pb[:c].copy_(b)
+        self.bias = nn.Parameter(pb[:c], requires_grad=self.bias.requires_grad)
+        relayout_conv_params(self)
+
+
 def build_conv_layer(cfg, *args, **kwargs):
     """mmcv.cnn.build_conv_layer: cfg None -> a plain (fixed-width) conv, which here is the same
     kernel-backed class."""

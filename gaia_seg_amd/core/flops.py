@@ -21,7 +21,12 @@ upsample and adds count 0, and the conv-to-token projection counts on the pooled
 The DynamicMixVisionTransformer (SegFormer) counts its patch embeddings, reduction convs, linears and the
 depthwise 3x3 of the Mix-FFN as the convs they are, and its attention -- Nq tokens of the stage against the Nk
 tokens of the reduced map -- 2 x 2 * Nq * Nk * 64 * heads per block and image; the DynamicSegformerHead counts
-its 1x1 convs at the sizes they run at."""
+its 1x1 convs at the sizes they run at.
+
+The DynamicMSCAN (SegNeXt) counts its patch embeddings, 1x1 convs and the depthwise 3x3 of the feed-forward
+as the convs they are, and the seven depthwise filters of the spatial gating unit as the depthwise convs they
+are (2 * KH * KW * C * H * W each, "same" padding); BatchNorm, LayerNorm, GELU, the gate and the layer scales
+count 0."""
 from ..hip.ops import conv_out_size
 from .bricks import DynamicConv2d
 
@@ -125,6 +130,38 @@ def mit_backbone_flops(backbone, h, w, in_channels=3):
             total += attention_kv_flops(h * w, hk * wk, att.num_heads)
             f1, p1, hidden, _, _ = _conv(blk.mlp.fc1, c, h, w)
             fd, pd, _, _, _ = _conv(blk.mlp.dwconv.dwconv, hidden, h, w)
+            f2, p2, _, _, _ = _conv(blk.mlp.fc2, hidden, h, w)
+            total += f1 + fd + f2
+            params += p1 + pd + p2
+        if i in backbone.out_indices:
+            feats.append((c, h, w))
+    return total, params, 0.0, feats
+
+
+def mscan_backbone_flops(backbone, h, w, in_channels=3):
+    """backbone_flops for a DynamicMSCAN: (flops per image, params, 0.0, feature shapes).  Params are those of
+    the active subnet: active slices, active blocks, BatchNorm and LayerNorm affines, layer scales."""
+    total, params, c, feats = 0.0, 0.0, in_channels, []
+    for i in range(4):
+        embed, _, _ = backbone.stage(i)
+        for conv in ((embed.proj[0], embed.proj[3]) if i == 0 else (embed.proj,)):
+            f, p, c, h, w = _conv(conv, c, h, w)
+            total += f
+            params += p + 2 * c                           # + the BatchNorm behind it
+        params += 2 * c                                   # norm{i}
+        for blk in backbone.active_blocks(i):
+            sgu = blk.attn.spatial_gating_unit
+            params += 2 * 2 * c + 2 * c                   # norm1, norm2, the two layer scales
+            for conv in (blk.attn.proj_1, sgu.conv3, blk.attn.proj_2):
+                f, p, _, _, _ = _conv(conv, c, h, w)
+                total += f
+                params += p
+            for dw in sgu.depthwise():
+                kh, kw = dw.kernel_size
+                total += 2.0 * kh * kw * c * h * w
+                params += kh * kw * c + c
+            f1, p1, hidden, _, _ = _conv(blk.mlp.fc1, c, h, w)
+            fd, pd, _, _, _ = _conv(blk.mlp.dwconv, hidden, h, w)
             f2, p2, _, _, _ = _conv(blk.mlp.fc2, hidden, h, w)
             total += f1 + fd + f2
             params += p1 + pd + p2
@@ -261,6 +298,8 @@ def backbone_flops(backbone, h, w, in_channels=3):
         return mit_backbone_flops(backbone, h, w, in_channels)
     if type(backbone).__name__ == "DynamicSwinTransformer":
         return swin_backbone_flops(backbone, h, w, in_channels)
+    if type(backbone).__name__ == "DynamicMSCAN":
+        return mscan_backbone_flops(backbone, h, w, in_channels)
     total = params = k3 = 0.0
     c = in_channels
     if backbone.deep_stem:

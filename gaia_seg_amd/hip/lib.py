@@ -16,7 +16,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libgaiaseg_hip.so")
 CSRC_DIR = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class HipLibraryError(RuntimeError):
@@ -75,6 +75,39 @@ def dwconv_desc(n, h, w, c, pad, dil=1, c_ld=None, ldx=None, ldy=None, k=3, stri
     d.stride, d.pad, d.dil = stride, pad, dil
     d.ldx, d.ldy = c if ldx is None else ldx, c if ldy is None else ldy
     return d
+
+
+class MscaDesc(Structure):
+    """Mirror of ``gs_msca_desc``."""
+    _fields_ = ([(k, c_int32) for k in ("N", "H", "W", "C", "C_ld", "K0")] + [("K", c_int32 * 3)]
+                + [("ldx", c_int32), ("lds", c_int32)])
+
+
+class MscaFilters(Structure):
+    """Mirror of ``gs_msca_filters`` and of ``gs_msca_filter_grads`` (the same 14 addresses)."""
+    _fields_ = [("w0", c_void_p), ("b0", c_void_p), ("w_row", c_void_p * 3), ("b_row", c_void_p * 3),
+                ("w_col", c_void_p * 3), ("b_col", c_void_p * 3)]
+
+
+def msca_desc(n, h, w, c, c_ld=None, ldx=None, lds=None, k0=5, k=(7, 11, 21)):
+    """A ``MscaDesc`` for a packed-NHWC map [n, h, w, c] (pixel pitch ``ldx`` of x / dx and ``lds`` of
+    s / ds, default c) and filters of tap pitch ``c_ld`` (default c)."""
+    d = MscaDesc()
+    d.N, d.H, d.W, d.C = n, h, w, c
+    d.C_ld = c if c_ld is None else c_ld
+    d.K0 = k0
+    d.K[0], d.K[1], d.K[2] = k
+    d.ldx, d.lds = c if ldx is None else ldx, c if lds is None else lds
+    return d
+
+
+def msca_filters(w0, b0, w_row, b_row, w_col, b_col):
+    """A ``MscaFilters`` of 14 addresses (ints or None): the filters, or their gradients."""
+    f = MscaFilters()
+    f.w0, f.b0 = w0, b0
+    for i in range(3):
+        f.w_row[i], f.b_row[i], f.w_col[i], f.b_col[i] = w_row[i], b_row[i], w_col[i], b_col[i]
+    return f
 
 
 class LayerNormDesc(Structure):
@@ -388,6 +421,7 @@ _CD, _CE, _BN, _KD = POINTER(ConvDesc), POINTER(CeDesc), POINTER(BnArgs), POINTE
 _DD, _PW, _CW = POINTER(DistillDesc), POINTER(PairwiseDesc), POINTER(CwdDesc)
 _DW = POINTER(DwConvDesc)
 _LN = POINTER(LayerNormDesc)
+_MS, _MF = POINTER(MscaDesc), POINTER(MscaFilters)
 _GG = POINTER(GeluGrnDesc)
 _AT = POINTER(AttentionDesc)
 _AK = POINTER(AttentionKvDesc)
@@ -409,6 +443,12 @@ PROTOTYPES = {
     "gs_dwconv2d_forward": (_i32, [_DW, _P, _P, _P, _P, _P]),
     "gs_dwconv2d_dgrad": (_i32, [_DW, _P, _P, _P, _i32, _P]),
     "gs_dwconv2d_wgrad": (_i32, [_DW, _P, _P, _P, _P, _sz, _P]),
+    "gs_msca_saved_bytes": (_sz, [_MS]),
+    "gs_msca_workspace_bytes": (_sz, [_MS]),
+    "gs_msca_forward": (_i32, [_MS, _P, _MF, _P, _P, _P]),
+    "gs_msca_backward": (_i32, [_MS, _P, _P, _MF, _P, _P, _i32, _MF, _P, _sz, _P]),
+    "gs_gate_mul_forward": (_i32, [_P, _P, _P, _i64, _i32, _i32, _i32, _i32, _P]),
+    "gs_gate_mul_backward": (_i32, [_P, _P, _P, _P, _P, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _P]),
     "gs_deconv2x2_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "gs_deconv2x2_forward": (_i32, [_P, _i32, _i32, _i32, _i32, _i32, _P, _i32, _P, _P, _i32, _P, _sz, _P]),
     "gs_layernorm_forward": (_i32, [_LN, _P, _P, _P, _P, _P, _P, _P]),

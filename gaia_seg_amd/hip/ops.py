@@ -589,6 +589,92 @@ def layer_scale_add(tape, identity, z, gamma, out=None):
     return out
 
 
+def msca(tape, x, unit, out=None):
+    """SegNeXt's multi-scale convolutional attention without its 1x1 conv, one operator (gs_msca_*):
+
+        a = conv0(x);  s = a + conv0_2(conv0_1(a)) + conv1_2(conv1_1(a)) + conv2_2(conv2_1(a))
+
+    all depthwise, on the x.C active channels.  ``unit.filters()`` gives the 14 max-size Parameters in the
+    order of gs_msca_filters: w0, b0, the three 1xK weights, their biases, the three Kx1 weights, their
+    biases (logical [C_max, 1, KH, KW], physical HWIO).  a and the three row results are kept for the
+    backward; the input's gradient is added to where it already holds one (x also feeds the gate)."""
+    L = _L()
+    x = materialize(tape, x)
+    params = tuple(unit.filters())
+    w0 = params[0]
+    c = x.C
+    if c > w0.shape[0]:
+        raise ValueError("input has %d channels, msca supports at most %d" % (c, w0.shape[0]))
+    if c % 4:
+        raise ValueError("msca needs a channel count that is a multiple of 4, got %d" % c)
+    c_ld = w0.stride(1)
+    if any(p.stride(1) != c_ld for p in params[2:5] + params[8:11]):
+        raise ValueError("msca: the filters differ in their channel pitch")
+    dev = x.t.device
+    if out is None:
+        out = Act.empty(x.N, x.H, x.W, c, dev)
+    d = _lib.msca_desc(x.N, x.H, x.W, c, c_ld=c_ld, ldx=x.ld, lds=out.ld, k0=w0.shape[2],
+                       k=tuple(p.shape[3] for p in params[2:5]))
+    db = ctypes.byref(d)
+
+    def table(ts):
+        ptrs = [t.data_ptr() for t in ts]
+        return _lib.msca_filters(ptrs[0], ptrs[1], ptrs[2:5], ptrs[5:8], ptrs[8:11], ptrs[11:14])
+
+    filters = table(params)
+    saved = torch.empty(L.gs_msca_saved_bytes(db), dtype=torch.uint8, device=dev)
+    _lib.check(L.gs_msca_forward(db, x.ptr, ctypes.byref(filters), out.ptr, saved.data_ptr(),
+                                 current_stream_ptr()), "gs_msca_forward")
+
+    def backward():
+        ds = out.g
+        if ds is None:
+            return
+        if ds.stride(2) != d.lds:
+            raise RuntimeError("msca: the output gradient's pitch %d differs from the output's %d"
+                               % (ds.stride(2), d.lds))
+        grads = [_param_grad(p) for p in params]
+        gtable = table(grads)
+        ws = _ws.get(L.gs_msca_workspace_bytes(db), dev)
+        dx, acc = _grad_target(x)   # (addressed with d.ldx)
+        _lib.check(L.gs_msca_backward(db, x.ptr, ds.data_ptr(), ctypes.byref(filters), saved.data_ptr(),
+                                      dx.data_ptr(), acc, ctypes.byref(gtable), ws.data_ptr(), ws.numel(),
+                                      current_stream_ptr()), "gs_msca_backward")
+        _notify_params(*params)
+
+    tape.record(backward)
+    return out
+
+
+def gate_mul(tape, g, u, out=None):
+    """The gate of SegNeXt's attention: y = g * u, elementwise.  The backward writes g's gradient and adds
+    u's to where it already holds one (u also feeds the convolutions that produced g)."""
+    L = _L()
+    g, u = materialize(tape, g), materialize(tape, u)
+    c, rows = g.C, g.rows
+    if u.C != c or u.rows != rows:
+        raise ValueError("gate_mul: %s and %s differ" % (tuple(g.t.shape), tuple(u.t.shape)))
+    if c % 4:
+        raise ValueError("gate_mul needs a channel count that is a multiple of 4, got %d" % c)
+    if out is None:
+        out = Act.empty(g.N, g.H, g.W, c, g.t.device)
+    _lib.check(L.gs_gate_mul_forward(g.ptr, u.ptr, out.ptr, rows, c, g.ld, u.ld, out.ld,
+                                     current_stream_ptr()), "gs_gate_mul_forward")
+
+    def backward():
+        dy = out.g
+        if dy is None or not (g.requires_grad or u.requires_grad):
+            return
+        dg, _ = _grad_target(g, "gate_mul's first input")
+        du, acc = _grad_target(u)
+        _lib.check(L.gs_gate_mul_backward(dy.data_ptr(), g.ptr, u.ptr, dg.data_ptr(), du.data_ptr(), rows, c,
+                                          dy.stride(2), g.ld, u.ld, dg.stride(2), du.stride(2), acc,
+                                          current_stream_ptr()), "gs_gate_mul_backward")
+
+    tape.record(backward)
+    return out
+
+
 def _attention_f16(f16):
     """Whether an attention op called with ``f16`` takes the fp16-operand entries: only inside an fp16 mode
     (the forward switch, or the library's train precision).  In fp32 modes the flag does nothing."""

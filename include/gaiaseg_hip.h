@@ -150,6 +150,77 @@ int gs_dwconv2d_wgrad(const gs_dwconv_desc* d, const float* x, const float* dy, 
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* SegNeXt: multi-scale convolutional attention (MSCAN's strip convolutions) and its gate       */
+/* ------------------------------------------------------------------------------------------ */
+/* The depthwise chain of mmseg's MSCAAttention in one operator, on an NHWC map x [N,H,W,C]:
+ *   a   = dwconv K0xK0 (x, w0) + b0                                     (K0 = 5, padding K0/2)
+ *   r_i = dwconv 1xK_i (a, w_row[i]) + b_row[i],   i = 0..2             (K = 7, 11, 21, padding K_i/2)
+ *   s   = a + sum_i ( dwconv K_ix1 (r_i, w_col[i]) + b_col[i] )
+ * stride 1, no dilation, zero padding ("same"), so s has the shape of x.  x / dx have the pixel pitch
+ * ldx and s / ds the pitch lds (channel slices of wider buffers are legal).  Every filter is the
+ * physical HWIO tensor with I = 1 ([K0][K0][1][C_ld], [1][K][1][C_ld], [K][1][1][C_ld]: channel-contiguous
+ * taps with pitch C_ld) and every bias a vector; only their leading C channels are read, and only the
+ * leading C channels of the gradients are written.  fp32 in every precision mode.  The kernels are
+ * bandwidth-bound: one thread per float4 channel quad over a strip of 8 positions along the filter's
+ * axis, taps in the padding skipped.  No float atomics: every sum has a fixed order (per output the taps
+ * in their order, the branches i in theirs; filter gradients per run of at most 256 pixels, then the runs
+ * in order), so two runs are bit-identical.
+ * Checked on the host before any launch: GS_E_NULL (descriptor, tensor, a filter struct or one of its
+ * 14 pointers), GS_E_BADARG (a size <= 0, K0 even or outside 1..7, a K[i] even or outside 1..21, a pitch
+ * or C_ld below C, more than 2^31 - 1 pixels), GS_E_ALIGN (C, C_ld or a pitch no multiple of 4, a pointer
+ * not 16-byte aligned), GS_E_WORKSPACE. */
+typedef struct gs_msca_desc {
+  int32_t N, H, W;        /* batch and spatial size of x and s                               */
+  int32_t C, C_ld;        /* ACTIVE channels; channel pitch of every filter's taps (>= C)    */
+  int32_t K0;             /* size of the square filter (odd, <= 7)                           */
+  int32_t K[3];           /* lengths of the three strip pairs (odd, <= 21)                   */
+  int32_t ldx, lds;       /* pixel strides of x / dx and of s / ds                           */
+} gs_msca_desc;
+typedef struct gs_msca_filters {
+  const float* w0;
+  const float* b0;
+  const float* w_row[3];  /* 1 x K[i] */
+  const float* b_row[3];
+  const float* w_col[3];  /* K[i] x 1 */
+  const float* b_col[3];
+} gs_msca_filters;
+typedef struct gs_msca_filter_grads {
+  float* w0;
+  float* b0;
+  float* w_row[3];
+  float* b_row[3];
+  float* w_col[3];
+  float* b_col[3];
+} gs_msca_filter_grads;
+/* bytes the forward keeps for the backward (0 for a descriptor the calls would refuse): a and the three
+ * row results r_i, packed [N*H*W][C] each -- four tensors of the map's size per call.  (Keeping a alone
+ * and recomputing r_i would save three of them for one more pass of the row kernel in the backward.) */
+size_t gs_msca_saved_bytes(const gs_msca_desc* d);
+/* bytes of scratch gs_msca_backward needs (0 for a descriptor it would refuse): the gradients of a and
+ * of the r_i (four tensors) and the per-run partials of the 14 parameter gradients.  A function of
+ * N*H*W, C and the filter sizes alone, non-decreasing in N*H*W. */
+size_t gs_msca_workspace_bytes(const gs_msca_desc* d);
+/* s as above; `saved` (gs_msca_saved_bytes(d) bytes, 16-byte aligned) is filled for the backward.
+ * Three launches, ten passes over a tensor of the map's size. */
+int gs_msca_forward(const gs_msca_desc* d, const float* x, const gs_msca_filters* filters, float* s,
+                    void* saved, void* stream);
+/* dx[..., :C] (= or +=, accumulate != 0 adds: x usually has a second consumer, the gate) and all 14
+ * parameter gradients, written into the max-size gradient tensors (channels C.. are never written).
+ * Gradient pointers are never NULL: pass scratch for a frozen parameter.  Seven launches. */
+int gs_msca_backward(const gs_msca_desc* d, const float* x, const float* ds, const gs_msca_filters* filters,
+                     const void* saved, float* dx, int accumulate, const gs_msca_filter_grads* grads,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* The gate on rows x C views with a pixel pitch per operand: y = g * u. */
+int gs_gate_mul_forward(const float* g, const float* u, float* y, int64_t rows, int32_t C, int32_t ldg,
+                        int32_t ldu, int32_t ldy, void* stream);
+/* dg = dy * u (written) and du (= or +=, accumulate != 0 adds) dy * g.  dg may be dy's buffer.
+ * GS_E_BADARG (rows or C <= 0, a pitch below C), GS_E_ALIGN (C or a pitch no multiple of 4, a pointer not
+ * 16-byte aligned), GS_E_NULL, for the forward alike. */
+int gs_gate_mul_backward(const float* dy, const float* g, const float* u, float* dg, float* du,
+                         int64_t rows, int32_t C, int32_t lddy, int32_t ldg, int32_t ldu, int32_t lddg,
+                         int32_t lddu, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* ConvNeXt block operators: LayerNorm over channels, GELU, layer scale + residual              */
 /* ------------------------------------------------------------------------------------------ */
 /* All on NHWC fp32 "rows x C" views: rows = N*H*W pixels, C ACTIVE channels, a pixel pitch ld >= C per
